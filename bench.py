@@ -10,12 +10,26 @@ RCCL gradient all-reduce when N > 1) over one synthetic FULL batch already resid
 Workload at every N: BASELINE.json configs[1] per GPU -- fp32, batch 256 x seq 64, vocab 8192,
 dim_emb 512, latent 128, 3 layers (weak scaling: the per-GPU batch is fixed, global batch 256 N).
 
-Extra objects on the JSON line (N = 1, rank 0):
+A plain run sets up, warms up, times --steps steps and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = wall time of the timed region / steps, plus the per-step spread).  Everything else it can measure runs only
+with --full.
+
+--dump-outputs DIR  after the timed steps, writes what the last timed step hands its caller (rank 0): losses.npy
+                    (loss_gen, loss_kld, loss) and params.npy (the parameters its Adam update left, sampled at
+                    DUMP_SAMPLE fixed positions, numpy default_rng(0)), float32.  Inputs are seeded, so two builds can
+                    be compared file by file.  The gradient buffer is not written: Adam consumes it inside the step, and
+                    late in a run it is a small difference of large terms -- the float-atomic order of the backward sums
+                    moves it by ~1e-4 relative between runs, where parameters and losses agree to rounding.
+
+Extra objects on the JSON line with --full (N = 1, rank 0):
   roofline      the kernel class with the largest share of the step, its EXECUTED FLOPs per launch (2MNK, a GEMM
                 whose row count is a device-side count priced at that count) divided by its mean launch duration from HIP events recorded on the launch stream
                 during the timed steps, against the fp32 MFMA peak (157.3 TFLOP/s).
   cpu_baseline  the torch-CPU restatement (oracle/vae_torch.py, "port": the reference's TF graph has
                 a GPU-only CudnnGRU and TensorFlow is absent) timed on a bounded sample.
+  table_l1_0, enc_top1_0, graph_as_written, ragged, dp_overlap_rehearsal, f32s, configs
+                the same model with work eliminations off, RAGGED batches, the data-parallel rehearsal, the
+                split-bf16 mode and the other BASELINE configurations (see main()).
 """
 import argparse
 import json
@@ -32,6 +46,7 @@ PEAK_F32_MFMA = 157.3      # TFLOP/s, MI355X_MICROARCH.md chip table
 PEAK_BF16_MFMA = 2500.0    # TFLOP/s dense (same table)
 STAMP_EVERY = 8            # every n-th timed step carries the per-launch HIP-event stamps of the roofline leg
 PMC_TAG = 'r04'            # the committed rocprofv3 --pmc passes `traffic` / `mfma_busy` are read from (quoted only for the same sources: pmc_summary)
+DUMP_SAMPLE = 1 << 23      # positions of the parameter vector --dump-outputs writes (22.1 M at the headline: 32 MiB)
 
 
 def pmc_summary(name):
@@ -134,12 +149,30 @@ def side_config(label, dtype, b, s, steps=3, warmup=2, pmc=None, ragged=None, **
     return out
 
 
+def dump_outputs(path, model, losses):
+    """--dump-outputs: the losses of the last timed step and the parameters its Adam update left, as float32 .npy files; the
+    parameter vector is sampled at DUMP_SAMPLE fixed positions (numpy default_rng(0), sorted)"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = model.params.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    ix = torch.as_tensor(idx).to(model.device)
+    np.save(os.path.join(path, 'losses.npy'), np.asarray(losses, dtype=np.float32))
+    np.save(os.path.join(path, 'params.npy'), model.params[ix].cpu().numpy())
+
+
 def main():
     global B, S
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help="also the roofline stamps, the CPU baseline, the elimination / ragged / rehearsal legs, the f32s leg and the "
+                         "other BASELINE configurations (the --no-* options below trim this set)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's losses and the parameters it left (sampled) to DIR/*.npy")
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--dtype', default='f32', choices=('f32', 'f32s', 'bf16'),
                     help="f32 = exact-fp32 MFMA (headline); f32s = fp32 GEMMs on the bf16 matrix cores by 3-way operand "
@@ -215,10 +248,11 @@ def main():
     for i in range(A.warmup):
         one(i)
     fence()
-    timing = world == 1 and not A.no_timing
+    timing = world == 1 and A.full and not A.no_timing
     # HIP-event stamps around every GEMM / GRU launch cost ~8 us of stream gap each (0.5 ms per step when
     # every step is stamped), so only every 8th step of the timed region is stamped (3 of the default 20): the
-    # roofline figures are live measurements over the timed region, `value` is perturbed by < 0.4 %
+    # roofline figures are live measurements over the timed region, `value` is perturbed by < 0.4 % (--full only: a plain run
+    # stamps nothing)
     stamped = [i for i in range(A.steps) if i % STAMP_EVERY == 0] if timing else []
     if timing:
         model.set_option('timing', 1)          # resets the stamp list
@@ -244,6 +278,8 @@ def main():
         dt = float(t.item())
     losses = model.losses()
     assert A.gru_ablate or all(x == x and abs(x) < 1e6 for x in losses), losses
+    if A.dump_outputs and rank == 0:                    # before any --full leg steps the model further
+        dump_outputs(A.dump_outputs, model, losses)
 
     if rank == 0:
         out = {
@@ -262,7 +298,7 @@ def main():
             "loss": losses[2],
             "step_ms": {"median": per_step[len(per_step) // 2], "min": per_step[0], "max": per_step[-1],
                         "what": "device time between consecutive step boundaries of the timed region (HIP events on the launch stream, rank 0; "
-                                "stamped steps carry ~0.5 ms of event gaps)"},
+                                "with --full, stamped steps carry ~0.5 ms of event gaps)"},
         }
         if dp:
             # what the collective layer really did, so that a scaling record can be checked: the world size the process group
@@ -393,7 +429,7 @@ def main():
                             "written), fenced before each persistent GRU launch: the cost of side-stream traffic beside backward, NOT a multi-GPU measurement"}
             if not A.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and A.dtype == 'f32' and not A.no_alt and headline:
+        if world == 1 and A.full and A.dtype == 'f32' and not A.no_alt and headline:
             # same workload, same steps, GEMMs on the bf16 matrix cores with fp32-accurate operand splitting
             # (opt-in mode, held to the fp32 tolerances by the parity tests): reported beside the headline, never as it
             del model
@@ -413,7 +449,7 @@ def main():
             out["f32s"] = {"value": B * A.steps / dt2, "unit": "sentences/sec", "ms_per_step": 1e3 * dt2 / A.steps, "loss": l2[2],
                            "dtype": "f32 in / f32 accumulate / f32 out; GEMM operands split into 3 x bf16 in registers, 6 partial "
                                     "products on v_mfma_f32_32x32x16_bf16 (VAE(dtype='f32s'), compute_dtype 2)"}
-        if world == 1 and headline and A.dtype == 'f32' and not A.no_configs:
+        if world == 1 and A.full and headline and A.dtype == 'f32' and not A.no_configs:
             # the other single-GPU BASELINE configurations, labelled; never the headline value
             try:
                 del m2

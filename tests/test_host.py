@@ -279,22 +279,20 @@ def test_bench_quotes_committed_counters_only_for_the_sources_they_were_taken_on
     assert pm is None and 'other kernel sources' in why
 
 
-REF_POSTS = '/root/reference/docs/results_iac/clustering.csv'
+REF_POSTS = os.path.join(GOLD, 'iac_posts.json.xz')        # the `post` column of clustering.csv (make_iac_posts_golden.py)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_POSTS), reason="the reference tree (its docs hold the only real corpus) is not on this machine")
 def test_data_prep_iac_on_the_reference_posts(tmp_path):
-    """SURVEY 8f item 3 on REAL text (build container only: the GPU box has no reference tree): the 1 901 cleaned IAC posts of the
-    reference's docs/results_iac/clustering.csv, laid out as fourforums discussion files (post field 3 = text, data_iac.py:18-27), go
+    """SURVEY 8f item 3 on REAL text: the 1 901 cleaned IAC posts of the reference's docs/results_iac/clustering.csv (committed as
+    tests/golden/iac_posts.json.xz), laid out as fourforums discussion files (post field 3 = text, data_iac.py:18-27), go
     through prep_iac: an 8192-piece SentencePiece model with the reference's ids (util_sp.py:17-39), train.txt = the DECODE of every
     post capped to 64 pieces at a sentence boundary (data_iac.py:37-41, util_sp.py:42-63), valid.npy = capped validation posts packed
     with eos (data_iac.py:43-46).  Checked: piece ids, every training line re-encodes to at most 64 pieces, the rows of valid.npy are the
     capped encodings, and the committed configs[0] ids (tests/golden/configs0_ids.npz) are what this flow produces for the same posts."""
-    import csv, json
+    import json, lzma
     from argsim_amd import data_prep, util_sp
-    csv.field_size_limit(1 << 30)
-    with open(REF_POSTS, newline='') as f:
-        posts = [r['post'].replace('\n', ' ').strip() for r in csv.DictReader(f)]
+    with lzma.open(REF_POSTS) as f:
+        posts = [p.replace('\n', ' ').strip() for p in json.loads(f.read().decode('utf-8'))]
     posts = [p for p in posts if p]
     raw = tmp_path / 'discussions'; raw.mkdir()
     for i in range(0, len(posts), 100):          # 20 "discussions" of 100 posts: [id, side, author, text, annotations, parent, category, time]
