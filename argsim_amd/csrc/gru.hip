@@ -441,6 +441,7 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_item_kernel(GruArgs a)
 // reads its operand like any other step; h_t lands in slot pos + 1.  The state h itself stays fp32: every gate thread keeps
 // the h_{t-1} of its (row, unit) in a register (one per row block) instead of picking it out of the exchanged operand; the
 // gate math and everything saved stay fp32.
+constexpr int kFwdTeamLdsBytes = (96 * 256 + 48 * 256 + 4 * 256) * 4 + 128;      // dynamic LDS of gru_fwd_team_kernel: Wl | part | hps | sync
 template <bool DIAG, bool PIPE, int T, bool BF = false, bool CMP = false>      // CMP: compact external arrays / phantom rows (GruArgs::rowmap, Bx)
 __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
 {
@@ -1065,6 +1066,7 @@ __global__ __launch_bounds__(256, 2) void gru_bwd_kernel(GruArgs a)
 // probe of the register-form D = 512 path above, with a ring of NB 24-register pieces (128-register budget at 4 waves
 // per SIMD) whose first NB pieces are in flight before the MFMAs start.  A job with dh0 (decoder layers) gets the
 // tail item p = -1: dh0 = carry + dgh_0 R.  Teams synchronise through monotonic LDS counters, never s_barrier.
+constexpr int kBwdTeamLdsBytes = (4 * 24 * 256 + 16 * 256 + 64) * 4 + 64;      // dynamic LDS of gru_bwd_team_kernel: Wl | part | red | sync
 template <int NB, bool PIPE, int T, bool DIAG = false, bool BF = false, bool CMP = false>   // CMP: compact external arrays / phantom rows (GruArgs::rowmap, Bx); PIPE: several row blocks per workgroup; T teams of 16 / T waves; BF: bf16 operands (see the forward)
 __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
 {
@@ -1620,11 +1622,12 @@ static hipError_t fill_sentinel2d(hipStream_t st, float* base, size_t rows, size
 
 // sentinel-fill the exchanged buffer of every job and zero the sync words; jobs that tile whole rows side
 // by side (the two encoder directions) are covered by ONE linear fill
-static hipError_t prepare_exchange(hipStream_t st, const GruArgs& a, bool fwd, bool team)
+static hipError_t prepare_exchange(hipStream_t st, const GruArgs& a, bool fwd, const GruPlan& p)
 {
-    const size_t Bg = team && a.Bx > a.B ? a.Bx : a.B;          // (team kernels: the launch geometry's rows)
+    const bool team = p.form == GruForm::team, bf = team && a.bf16 && !p.diag;      // (bf: the kernel exchanges 16-bit values)
+    const size_t Bg = p.Bg;          // (the launch geometry's rows: B but for the team kernels' phantom rows)
     const size_t rows = (size_t)a.S * Bg, width = fwd ? a.D : 3 * (size_t)a.D, ld = fwd ? a.ldh : a.ldg;
-    if (team && fwd && a.bf16) {
+    if (bf && fwd) {
         GruH0 h0s{};
         for (int i = 0; i < a.njobs; ++i) h0s.p[i] = a.job[i].h0;
         const size_t chunks_per_job = ((size_t)a.S + 1) * Bg * a.D / 8;
@@ -1635,7 +1638,7 @@ static hipError_t prepare_exchange(hipStream_t st, const GruArgs& a, bool fwd, b
     if (team) {       // team kernels exchange through the tiled scratch buffer: one linear fill over every job's part
         const size_t n16 = (size_t)a.njobs * rows * width / 4;             // (bf16 mode, backward: the exchange holds 16-bit values)
         hipLaunchKernelGGL(gru_prepare_kernel, dim3(2048), dim3(256), 0, st, a.counters, kGruSyncWords,
-                           reinterpret_cast<uint4*>(a.xbuf), (!fwd && a.bf16) ? n16 / 2 : n16);
+                           reinterpret_cast<uint4*>(a.xbuf), bf ? n16 / 2 : n16);
         return hipGetLastError();
     }
     float* base0 = fwd ? a.job[0].hs : a.job[0].dgh;
@@ -1689,10 +1692,9 @@ int gru_team_batch(int B)
         if (team_rows(1, bx, &T, &C) && team_rows(2, bx, &T, &C)) return bx;
     return 0;
 }
-static bool team_geometry(const GruArgs& a, bool fwd, int* T, int* C)
+static bool team_geometry(const GruArgs& a, bool fwd, int Bg, int* T, int* C)
 {
     if (a.D != 512 || a.njobs > 2 || a.p_begin != 0) return false;
-    const int Bg = a.Bx > a.B ? a.Bx : a.B;
     // the tiled exchange scratch: present, 16-byte aligned, large enough, addressable with 32-bit byte offsets per job
     const size_t per_job = (size_t)a.S * Bg * a.D * (fwd ? 1 : 3);
     if (!a.xbuf || (((uintptr_t)a.xbuf) & 15) || a.xbuf_floats < per_job * a.njobs || per_job * 4 >= (1ull << 32)) return false;
@@ -1702,136 +1704,108 @@ static bool team_geometry(const GruArgs& a, bool fwd, int* T, int* C)
     return team_rows(a.njobs, Bg, T, C);
 }
 
-static bool forward_team(const GruArgs& a, bool persistent, int* T, int* C)
+// The one place that decides the kernel form (kernels.h GruPlan).  The diagnostic build runs its timing experiments with gru_ablate
+// bits 16 | 128 | 256 alone on the team kernels as well (the forward with 4 teams only), never in the reduce-scatter form; the forward
+// with any of them and the backward with bit 128 on the diagnostic instantiation (fp32 over the padded layout: no 16-bit operands,
+// compact layout or phantom rows).
+GruPlan gru_plan(const GruArgs& a, bool fwd, bool persistent)
 {
-    if (!(persistent && a.p_end - a.p_begin > 1)) return false;
-    bool team = team_geometry(a, true, T, C) && a.item_pipeline == 2;
-#ifdef AVAE_DIAG
-    if (a.ablate && ((a.ablate & ~(16 | 128 | 256)) || *T != 4)) team = false;
-#else
-    if (a.ablate) team = false;
-#endif
-    return team;
+    GruPlan p{};
+    p.Bg = a.Bx > a.B ? a.Bx : a.B;
+    if (!persistent || (fwd && a.p_end - a.p_begin < 2)) { p.form = GruForm::stepwise; return p; }
+    const bool ablate_ok = !a.ablate || (kDiagBuild && !(a.ablate & ~(16 | 128 | 256)));
+    int T = 0, C = 0;
+    if (!(team_geometry(a, fwd, p.Bg, &T, &C) && a.item_pipeline == 2 && ablate_ok && (!fwd || !a.ablate || T == 4))) {
+        // benchmark geometry (D = 512, two full 16-row chunks per workgroup): the software-pipelined forward kernel
+        const bool item = fwd && a.D == 512 && a.rows_per_group == 32 && a.B % 32 == 0 && a.G * 32 == a.B && !a.ablate && a.item_pipeline;
+        p.form = item ? GruForm::item : GruForm::persistent;
+        return p;
+    }
+    // the reduce-scatter BPTT takes a whole-sequence fp32 launch (team_geometry: p_begin = 0) whose scratch holds its ring
+    const bool rs = !fwd && a.bwd_rs && !a.bf16 && !a.ablate && a.p_end == a.S && a.xbuf_floats >= gru_bwd_rs_xbuf_floats(a.njobs, p.Bg);
+    p.form = rs ? GruForm::team_rs : GruForm::team;
+    p.T = T; p.C = C; p.cpj = C / a.njobs;
+    p.pipe = a.njobs * (p.Bg / (16 * T)) > C;
+    p.diag = kDiagBuild && (fwd ? a.ablate != 0 : (a.ablate & 128) != 0);
+    return p;
 }
-bool gru_forward_uses_team(const GruArgs& a, bool persistent) { int T = 0, C = 0; return forward_team(a, persistent, &T, &C); }
+
+// the operands only some forms honour
+static hipError_t check_operands(const GruArgs& a, const GruPlan& p, bool fwd)
+{
+    const bool team = p.team(), bf = p.full() && a.bf16;      // (16-bit operands: the bf16 team kernels only)
+    bool ok = (!a.sv16 || bf) && (!(a.rowmap || a.Bx > a.B) || p.full())      // compact layout / phantom rows: team kernels only,
+              && (a.Bx <= a.B || (a.slens && a.perm && a.rowmap));         // and phantom rows exist through the row order and the row map only
+    for (int i = 0; i < a.njobs; ++i) {
+        const GruJob& j = a.job[i];
+        ok = ok && (!j.hp16 || bf) && (fwd ? (!j.hs16 || bf) && (!j.gi_rows || team) : (!(j.dgi16 || j.dgh16) || bf));
+    }
+    return ok ? hipSuccess : hipErrorInvalidValue;
+}
 
 hipError_t gru_forward(hipStream_t st, const GruArgs& a, bool persistent)
 {
     int grid; hipError_t e = check(a, &grid); if (e != hipSuccess) return e;
-    int T = 0, C = 0;
-    const bool team = forward_team(a, persistent, &T, &C);
-    if (a.sv16 && !(team && a.bf16)) return hipErrorInvalidValue;      // 16-bit saved gates: the bf16 team kernels only
-    for (int i = 0; i < a.njobs; ++i) if ((a.job[i].hs16 || a.job[i].hp16) && !(team && a.bf16)) return hipErrorInvalidValue;
-    for (int i = 0; i < a.njobs; ++i) if (a.job[i].gi_rows && !team) return hipErrorInvalidValue;      // only the team kernels index gi through gi_rows
-    if ((a.rowmap || a.Bx > a.B) && !team) return hipErrorInvalidValue;                                // ... and know the compact layout / phantom rows
-    if (a.Bx > a.B && (!a.slens || !a.perm || !a.rowmap)) return hipErrorInvalidValue;                 // (phantom rows exist through the row order and the row map only)
-    if (persistent && a.p_end - a.p_begin > 1) {
+    const GruPlan p = gru_plan(a, true, persistent);
+    e = check_operands(a, p, true); if (e != hipSuccess) return e;
+    if (p.form == GruForm::stepwise) {
+        for (int q = a.p_begin; q < a.p_end; ++q) {
+            GruArgs b = a; b.p_begin = q; b.p_end = q + 1;
+            e = launch<true>(st, b, grid, false); if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+    e = prepare_exchange(st, a, true, p); if (e != hipSuccess) return e;
+    switch (p.form) {
+    case GruForm::team: {
         // D = 512: independent 16-row teams sharing one LDS-resident weight slice per CU, the row blocks of a workgroup
         // interleaved item by item (team_geometry picks 4 teams x 4 waves or 2 teams x 8 waves)
-        e = prepare_exchange(st, a, true, team); if (e != hipSuccess) return e;
-        if (team) {
-            const int lds_bytes = (96 * 256 + 48 * 256 + 4 * 256) * 4 + 128;
-            const bool pipe = a.njobs * ((a.Bx > a.B ? a.Bx : a.B) / (16 * T)) > C;      // several row blocks per workgroup
-            const bool cmp = a.rowmap != nullptr;                                          // the instantiation that knows the compact layout
-#ifdef AVAE_DIAG
-            if (a.ablate) {
-                return pipe ? launch_team(st, gru_fwd_team_kernel<true, true, 4>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<true, false, 4>, a, lds_bytes, C);
-            } else
-#endif
-            {
-                if (a.bf16) {
-                    if (T == 4) return pipe ? (cmp ? launch_team(st, gru_fwd_team_kernel<false, true, 4, true, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, true, 4, true, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_fwd_team_kernel<false, false, 4, true, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, false, 4, true, false>, a, lds_bytes, C));
-                    return pipe ? (cmp ? launch_team(st, gru_fwd_team_kernel<false, true, 2, true, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, true, 2, true, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_fwd_team_kernel<false, false, 2, true, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, false, 2, true, false>, a, lds_bytes, C));
-                }
-                if (T == 4) return pipe ? (cmp ? launch_team(st, gru_fwd_team_kernel<false, true, 4, false, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, true, 4, false, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_fwd_team_kernel<false, false, 4, false, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, false, 4, false, false>, a, lds_bytes, C));
-                return pipe ? (cmp ? launch_team(st, gru_fwd_team_kernel<false, true, 2, false, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, true, 2, false, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_fwd_team_kernel<false, false, 2, false, true>, a, lds_bytes, C) : launch_team(st, gru_fwd_team_kernel<false, false, 2, false, false>, a, lds_bytes, C));
-            }
-        }
-        // benchmark geometry (D = 512, two full 16-row chunks per workgroup): software-pipelined kernel
-        if (a.D == 512 && a.rows_per_group == 32 && a.B % 32 == 0 && a.G * 32 == a.B && !a.ablate && a.item_pipeline) {
-            e = resident(gru_fwd_item_kernel, 256, 0, grid); if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(gru_fwd_item_kernel, dim3(grid), dim3(256), 0, st, a);
-            return hipGetLastError();
-        }
+        return team_dispatch(p.T, [&](auto T, auto PIPE, auto BF, auto CMP) {
+            if constexpr (kDiagBuild && T == 4 && !BF && !CMP) if (p.diag) return launch_team(st, gru_fwd_team_kernel<true, PIPE, 4>, a, kFwdTeamLdsBytes, p.C);
+            return launch_team(st, gru_fwd_team_kernel<false, PIPE, T, BF, CMP>, a, kFwdTeamLdsBytes, p.C);
+        }, p.pipe, a.bf16 && !p.diag, a.rowmap != nullptr);
+    }
+    case GruForm::item:
+        e = resident(gru_fwd_item_kernel, 256, 0, grid); if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(gru_fwd_item_kernel, dim3(grid), dim3(256), 0, st, a);
+        return hipGetLastError();
+    default:
         return launch<true>(st, a, grid, true);
     }
-    for (int p = a.p_begin; p < a.p_end; ++p) {
-        GruArgs b = a; b.p_begin = p; b.p_end = p + 1;
-        e = launch<true>(st, b, grid, false); if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
 }
-
-bool gru_team_shape(const GruArgs& a, bool fwd, bool persistent, int* T, int* cpj, int* nrb)
-{
-    int C = 0;
-    if (fwd ? !forward_team(a, persistent, T, &C) : !(persistent && team_geometry(a, false, T, &C) && !a.ablate && a.item_pipeline == 2)) return false;
-    *cpj = C / a.njobs;
-    *nrb = ((a.Bx > a.B ? a.Bx : a.B) / (16 * *T)) / *cpj;
-    return *cpj >= 1 && *nrb >= 1 && *nrb <= 4;
-}
-bool gru_backward_uses_team(const GruArgs& a, bool persistent)
-{
-    int T = 0, C = 0;
-    return persistent && team_geometry(a, false, &T, &C) && !a.ablate && a.item_pipeline == 2;
-}
-
-// the reduce-scatter form takes a whole-sequence fp32 launch of the team geometry whose scratch holds its ring
-static bool backward_rs(const GruArgs& a)
-{
-    const int Bg = a.Bx > a.B ? a.Bx : a.B;
-    return a.bwd_rs && !a.bf16 && !a.ablate && a.p_begin == 0 && a.p_end == a.S && a.xbuf_floats >= gru_bwd_rs_xbuf_floats(a.njobs, Bg);
-}
-bool gru_backward_uses_rs(const GruArgs& a, bool persistent) { return gru_backward_uses_team(a, persistent) && backward_rs(a); }
 
 hipError_t gru_backward(hipStream_t st, const GruArgs& a, bool persistent)
 {
-    if (a.sv16 && !(a.bf16 && gru_backward_uses_team(a, persistent))) return hipErrorInvalidValue;
-    for (int i = 0; i < a.njobs; ++i) if (a.job[i].hp16 && !(a.bf16 && gru_backward_uses_team(a, persistent))) return hipErrorInvalidValue;
-    for (int i = 0; i < a.njobs; ++i)      // 16-bit gate gradients are written by the bf16 team kernels only
-        if ((a.job[i].dgi16 || a.job[i].dgh16) && !(a.bf16 && gru_backward_uses_team(a, persistent))) return hipErrorInvalidValue;
-
     int grid; hipError_t e = check(a, &grid); if (e != hipSuccess) return e;
-    if ((a.rowmap || a.Bx > a.B) && !gru_backward_uses_team(a, persistent)) return hipErrorInvalidValue;      // compact layout / phantom rows: team kernels only
-    if (a.Bx > a.B && (!a.slens || !a.perm || !a.rowmap)) return hipErrorInvalidValue;
-    if (persistent) {
-        int T = 0, C = 0;
-        const bool team = team_geometry(a, false, &T, &C) && !(a.ablate & ~(16 | 128 | 256)) && a.item_pipeline == 2;
-        if (team && backward_rs(a)) {
-            // reduce-scatter form (gru_rs.hip): the exchange is a two-slot ring of partial dH tiles, filled with 1-bits (the tag the
-            // first use of a slot does NOT expect)
-            const size_t Bg = a.Bx > a.B ? a.Bx : a.B;
-            hipLaunchKernelGGL(gru_prepare_kernel, dim3(2048), dim3(256), 0, st, a.counters, kGruSyncWords,
-                               reinterpret_cast<uint4*>(a.xbuf), gru_bwd_rs_xbuf_floats(a.njobs, (int)Bg) / 4);
-            e = hipGetLastError(); if (e != hipSuccess) return e;
-            return gru_bwd_rs_launch(st, a, T, C, a.njobs * ((int)Bg / (16 * T)) > C, a.rowmap != nullptr);
-        }
-        e = prepare_exchange(st, a, false, team); if (e != hipSuccess) return e;
-        if (team) {
-            const int lds_bytes = (4 * 24 * 256 + 16 * 256 + 64) * 4 + 64;
-            const bool pipe = a.njobs * ((a.Bx > a.B ? a.Bx : a.B) / (16 * T)) > C;
-            const bool cmp = a.rowmap != nullptr;
-#ifdef AVAE_DIAG
-            if (a.ablate & 128) {
-                if (T == 4) return pipe ? launch_team(st, gru_bwd_team_kernel<2, true, 4, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, false, 4, true>, a, lds_bytes, C);
-                return pipe ? launch_team(st, gru_bwd_team_kernel<2, true, 2, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, false, 2, true>, a, lds_bytes, C);
-            }
-#endif
-            if (a.bf16) {
-                if (T == 4) return pipe ? (cmp ? launch_team(st, gru_bwd_team_kernel<2, true, 4, false, true, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, true, 4, false, true, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_bwd_team_kernel<2, false, 4, false, true, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, false, 4, false, true, false>, a, lds_bytes, C));
-                return pipe ? (cmp ? launch_team(st, gru_bwd_team_kernel<2, true, 2, false, true, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, true, 2, false, true, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_bwd_team_kernel<2, false, 2, false, true, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, false, 2, false, true, false>, a, lds_bytes, C));
-            }
-            if (T == 4) return pipe ? (cmp ? launch_team(st, gru_bwd_team_kernel<2, true, 4, false, false, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, true, 4, false, false, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_bwd_team_kernel<2, false, 4, false, false, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, false, 4, false, false, false>, a, lds_bytes, C));
-            return pipe ? (cmp ? launch_team(st, gru_bwd_team_kernel<2, true, 2, false, false, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, true, 2, false, false, false>, a, lds_bytes, C)) : (cmp ? launch_team(st, gru_bwd_team_kernel<2, false, 2, false, false, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_team_kernel<2, false, 2, false, false, false>, a, lds_bytes, C));
-        }
+    const GruPlan p = gru_plan(a, false, persistent);
+    e = check_operands(a, p, false); if (e != hipSuccess) return e;
+    switch (p.form) {
+    case GruForm::team_rs:
+        // reduce-scatter form (gru_rs.hip): the exchange is a two-slot ring of partial dH tiles, filled with 1-bits (the tag the
+        // first use of a slot does NOT expect)
+        hipLaunchKernelGGL(gru_prepare_kernel, dim3(2048), dim3(256), 0, st, a.counters, kGruSyncWords,
+                           reinterpret_cast<uint4*>(a.xbuf), gru_bwd_rs_xbuf_floats(a.njobs, p.Bg) / 4);
+        e = hipGetLastError(); if (e != hipSuccess) return e;
+        return gru_bwd_rs_launch(st, a, p);
+    case GruForm::team: {
+        e = prepare_exchange(st, a, false, p); if (e != hipSuccess) return e;
+        return team_dispatch(p.T, [&](auto T, auto PIPE, auto BF, auto CMP) {
+            if constexpr (kDiagBuild && !BF && !CMP) if (p.diag) return launch_team(st, gru_bwd_team_kernel<2, PIPE, T, true>, a, kBwdTeamLdsBytes, p.C);
+            return launch_team(st, gru_bwd_team_kernel<2, PIPE, T, false, BF, CMP>, a, kBwdTeamLdsBytes, p.C);
+        }, p.pipe, a.bf16 && !p.diag, a.rowmap != nullptr);
+    }
+    case GruForm::persistent:
+        e = prepare_exchange(st, a, false, p); if (e != hipSuccess) return e;
         return launch<false>(st, a, grid, true);
+    default:
+        break;
     }
     // one launch per step (descending); the dh0 tail (p = -1) is its own launch
-    for (int p = a.p_end - 1; p >= a.p_begin; --p) {
-        GruArgs b = a; b.p_begin = p; b.p_end = p + 1;
+    for (int q = a.p_end - 1; q >= a.p_begin; --q) {
+        GruArgs b = a; b.p_begin = q; b.p_end = q + 1;
         for (int i = 0; i < b.njobs; ++i) b.job[i].dh0 = nullptr;
         e = launch<false>(st, b, grid, false); if (e != hipSuccess) return e;
-        if (p == 0) {
+        if (q == 0) {
             bool any = false; for (int i = 0; i < a.njobs; ++i) any |= a.job[i].dh0 != nullptr;
             if (any) {
                 GruArgs d = a; d.p_begin = 0; d.p_end = 0;   // loop runs p = -1 only

@@ -2,6 +2,7 @@
 // "not yet written" check, buffer-instruction wrappers, bounded spins, the same-XCD rendezvous, the tiled exchange index maps,
 // team barriers and the team-kernel workgroup map.  Internal; not part of the C ABI.
 #pragma once
+#include <type_traits>
 #include "kernels.h"
 
 namespace avae {
@@ -464,5 +465,21 @@ static hipError_t launch_team(hipStream_t st, K kernel, const GruArgs& a, int ld
     return hipGetLastError();
 }
 
+// the team-kernel instantiation of a runtime T in {2, 4} and runtime flags (pipe, bf16, cmp, ...): f(T, FLAG...) called with
+// std::integral_constant arguments, so each combination names its template arguments once
+template <class F>
+static hipError_t with_flags(F&& f) { return f(); }
+template <class F, class... Bs>
+static hipError_t with_flags(F&& f, bool b, Bs... rest)
+{
+    return b ? with_flags([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : with_flags([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+template <class F, class... Bs>
+static hipError_t team_dispatch(int T, F&& f, Bs... flags)
+{
+    return T == 4 ? with_flags([&](auto... c) { return f(std::integral_constant<int, 4>{}, c...); }, flags...)
+                  : with_flags([&](auto... c) { return f(std::integral_constant<int, 2>{}, c...); }, flags...);
+}
 
 }  // namespace avae

@@ -45,6 +45,7 @@ constexpr int kRsBlock = 8192;        // floats per (slot, 16-row block, consume
 
 __device__ __forceinline__ unsigned tag_bit(unsigned v, unsigned tag) { return (v & ~1u) | tag; }
 
+template <int T> constexpr int kRsLdsBytes = (96 * 256 + T * 2 * 16 * 52 + 64) * 4 + 64;      // dynamic LDS of gru_bwd_rs_kernel: Wl | Aimg | red | sync
 template <bool PIPE, int T, bool CMP>
 __global__ __launch_bounds__(1024, 4) void gru_bwd_rs_kernel(GruArgs a)
 {
@@ -338,16 +339,11 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_rs_kernel(GruArgs a)
 
 size_t gru_bwd_rs_xbuf_floats(int njobs, int rows) { return (size_t)njobs * (size_t)rows * (4 * kRsBlock); }
 
-// fill value of the ring: every tag bit set (the first use of a slot expects 0)
-hipError_t gru_bwd_rs_launch(hipStream_t st, const GruArgs& a, int T, int C, bool pipe, bool cmp)
+hipError_t gru_bwd_rs_launch(hipStream_t st, const GruArgs& a, const GruPlan& p)
 {
-    const int lds_bytes = (96 * 256 + T * 2 * 16 * 52 + 64) * 4 + 64;
-    if (T == 4) {
-        if (pipe) return cmp ? launch_team(st, gru_bwd_rs_kernel<true, 4, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_rs_kernel<true, 4, false>, a, lds_bytes, C);
-        return cmp ? launch_team(st, gru_bwd_rs_kernel<false, 4, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_rs_kernel<false, 4, false>, a, lds_bytes, C);
-    }
-    if (pipe) return cmp ? launch_team(st, gru_bwd_rs_kernel<true, 2, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_rs_kernel<true, 2, false>, a, lds_bytes, C);
-    return cmp ? launch_team(st, gru_bwd_rs_kernel<false, 2, true>, a, lds_bytes, C) : launch_team(st, gru_bwd_rs_kernel<false, 2, false>, a, lds_bytes, C);
+    return team_dispatch(p.T, [&](auto T, auto PIPE, auto CMP) {
+        return launch_team(st, gru_bwd_rs_kernel<PIPE, T, CMP>, a, kRsLdsBytes<T>, p.C);
+    }, p.pipe, a.rowmap != nullptr);
 }
 
 }  // namespace avae

@@ -88,7 +88,7 @@ struct GruJob {
     float* dgi;           // (S,B,ldg) G16 columns (+ job offset)
     float* dgh;           // (S,B,ldg)
     unsigned short* dgi16; // optional, bf16 team kernels only: dgi / dgh as bf16 (S,B,ldg) row-major INSTEAD of the fp32 arrays
-    unsigned short* dgh16; //   (gru_backward_uses_team tells whether the launch will honour them)
+    unsigned short* dgh16; //   (honoured where gru_plan gives a team form)
     float* dh0;           // (B,D) or nullptr
     float* carry;         // (B,D) scratch: dH_{p+1} * u_{p+1}
     int dgi_by_pos;       // with GruArgs::rowmap: dgi / dgi16 keep the padded (pos * B + row) layout, zeros at padding (a table-fed layer: summed by token id)
@@ -128,19 +128,24 @@ struct GruArgs {
     int bwd_rs;           // 1: the backward runs the reduce-scatter team kernel (gru_rs.hip) where the team geometry applies and xbuf holds its ring
     int ablate;           // timing experiments only: 1 no MFMA/A loads, 2 no gate-phase loads, 4 no saves, 8 cheap activations, 16 no sync
 };
+// The kernel form of a launch, from its shape alone (geometry, Bx, xbuf / xbuf_floats, p_begin / p_end, bf16, bwd_rs, ablate,
+// item_pipeline): callers plan before they attach slens / perm / rowmap and the job pointers.  gi_rows, slens / perm: team forms only.
+enum class GruForm { stepwise, persistent, item, team, team_rs };     // item: forward only (gru_fwd_item_kernel); team_rs: backward only (gru_rs.hip)
+struct GruPlan {
+    GruForm form;
+    int T, C, cpj, Bg;      // team forms: T teams of 16 rows per 16 T-row block, C workgroups per hidden tile (cpj per job); Bg = max(B, Bx)
+    bool pipe, diag;        // pipe: several row blocks per workgroup; diag: the DIAG build's timing instantiation (fp32, padded layout)
+    bool team() const { return form == GruForm::team || form == GruForm::team_rs; }
+    bool full() const { return team() && !diag; }      // a team form that honours the 16-bit operands, rowmap and phantom rows too
+};
+GruPlan gru_plan(const GruArgs& a, bool fwd, bool persistent);
 hipError_t gru_forward(hipStream_t st, const GruArgs& a, bool persistent);
-bool gru_forward_uses_team(const GruArgs& a, bool persistent);      // true: the launch runs the LDS-weight team kernels (gi_rows honoured)
 hipError_t gru_backward(hipStream_t st, const GruArgs& a, bool persistent);
-// geometry of the team kernels a launch of this shape would run: T teams of 16 rows per 16 T-row block, cpj chain groups
-// (workgroups) per job and hidden tile, nrb row blocks per workgroup; false: another kernel form runs (no slens / perm)
-bool gru_team_shape(const GruArgs& a, bool fwd, bool persistent, int* T, int* cpj, int* nrb);
 int gru_team_batch(int B);        // smallest row count >= B (within 256) the team kernels have a geometry for with one job and with two; 0: none
-bool gru_backward_uses_team(const GruArgs& a, bool persistent);     // true: the launch runs the LDS-weight team kernels (dgi16 / dgh16 honoured in bf16 mode)
 bool gru_dim_supported(int D);
 // reduce-scatter form of the backward team kernels (gru_rs.hip): floats of exchange scratch it needs for njobs jobs over `rows` slots
 size_t gru_bwd_rs_xbuf_floats(int njobs, int rows);
-hipError_t gru_bwd_rs_launch(hipStream_t st, const GruArgs& a, int T, int C, bool pipe, bool cmp);
-bool gru_backward_uses_rs(const GruArgs& a, bool persistent);     // true: the launch runs the reduce-scatter form
+hipError_t gru_bwd_rs_launch(hipStream_t st, const GruArgs& a, const GruPlan& p);
 // one GRU step from a zero state for B rows (the top encoder layer's backward direction: gru.hip "one step from a zero
 // state"): gi (B, 3D) / bR G16; h -> h_out[b * ldo + j]; sv (B, D, 4) = r, u, n, hn or nullptr
 hipError_t gru_first_step_fwd(hipStream_t st, const float* gi, const float* bR, float* h_out, int ldo, float* sv, int B, int D, const int32_t* lens = nullptr);      // lens: rows of length 0 get h = 0

@@ -610,41 +610,47 @@ Sched schedule(const avae_ctx* h)
 // direction alone.  Same values as the full form (option enc_top1 = 0), a sixth of the encoder's work not executed.
 static bool top_one_step(const avae_ctx* h) { return h->enc_top1 && h->cfg.rnn_layers >= 2; }
 
-// The share of the padded source positions that are real, as the host last saw it (the asynchronous hint of build_row_orders;
-// 1.0 while nothing has arrived).  Shapes launches only, never a value.
-static double expected_fill(const avae_ctx* h)
+// The asynchronous fill hint of build_row_orders: real source positions and padded rows of an EARLIER call (no synchronisation;
+// real < 0 or rows <= 0 while nothing has arrived).  Both words in ONE 8-byte load: the copy that lands them is 8 bytes, so a
+// pair is never half of one call and half of another.  Shapes launches only, never a value.
+struct FillHint { int32_t real, rows; };
+static FillHint fill_hint(const avae_ctx* h)
 {
     const uint64_t pair = h->hint_host ? *reinterpret_cast<const volatile uint64_t*>(h->hint_host) : 0xffffffffull;
-    const int32_t real = (int32_t)(uint32_t)(pair & 0xffffffffull), rows = (int32_t)(uint32_t)(pair >> 32);
-    return (real > 0 && rows > 0) ? std::min(1.0, (double)real / (double)rows) : 1.0;
+    return {(int32_t)(uint32_t)(pair & 0xffffffffull), (int32_t)(uint32_t)(pair >> 32)};
+}
+// the share of the padded source positions that are real, as the host last saw it (1.0 while nothing has arrived)
+static double expected_fill(const avae_ctx* h)
+{
+    const FillHint f = fill_hint(h);
+    return (f.real > 0 && f.rows > 0) ? std::min(1.0, (double)f.real / (double)f.rows) : 1.0;
 }
 // Which BPTT team kernel a launch takes (option bwd_rs = 2).  The reduce-scatter form stores 64 KB per live row and step where the other
 // form stores 6 KB, and wins only where a workgroup's teams run out of rows at different times so that most steps belong to one or two
 // lone chains -- a ragged batch with a long tail.  Measured: batch 100 x 512 ragged (fill 0.30) -8 % of the step; RAGGED 256 x 64 (fill
 // 0.44) a tie; FULL batches lose at every size (64 x 64 +1.8 %, 128 x 64 +4.7 %, 100 x 512 +2.3 %, 256 x 64 +5 %).  So the fill decides,
 // not the row count.
-static int rs_pick(const avae_ctx* h, int njobs, int B)
+static int rs_pick(const avae_ctx* h)
 {
-    (void)njobs; (void)B;
     if (h->bwd_rs != 2) return h->bwd_rs;
     return expected_fill(h) < 0.40 ? 1 : 0;
 }
 // the same regime in the exchange of every team kernel (option gru_spec = 2): a consumer's first operand load goes out without a probe
 // round trip in front of it (GruArgs::spec): RAGGED 256 x 64 (fill 0.44) -1.5 %; forced on, a FULL 100 x 512 batch loses 1 %.
-static int spec_pick(const avae_ctx* h, int njobs, int B)
+static int spec_pick(const avae_ctx* h)
 {
-    (void)njobs; (void)B;
     if (h->gru_spec != 2) return h->gru_spec;
     return expected_fill(h) < 0.60 ? 1 : 0;
 }
 
 // -------------------------------------------------------------------------------- forward pieces
 // GRU launch arguments common to every call site
-static void gru_common(avae_ctx* h, const Ws& w, GruArgs& a, int njobs, int S, int B, int ldg, int ldh, const int32_t* lens)
+// (Bx: the launch geometry's rows where the compact layout is in place, 0 elsewhere; w.Bx for a plan that assumes it)
+static void gru_common(avae_ctx* h, const Ws& w, GruArgs& a, int njobs, int S, int B, int ldg, int ldh, const int32_t* lens, int Bx)
 {
     const int D = h->cfg.dim_emb;
     a.njobs = njobs; a.S = S; a.B = B; a.D = D; a.ldg = ldg; a.ldh = ldh; a.lens = lens;
-    a.Bx = w.Bx;        // (shape queries: the geometry the team kernels would run with the row order and the compact layout in place)
+    a.Bx = Bx;
     gru_geometry(D, njobs, B, &a.G, &a.rows_per_group);
     a.p_begin = 0; a.p_end = S; a.counters = h->counters; a.err = h->errw; a.ablate = h->gru_ablate; a.force_slow = h->gru_force_slow;
     a.bf16 = h->cfg.compute_dtype == 1 && h->gru_bf16; a.stagger = h->gru_stagger; a.item_pipeline = h->gru_item;
@@ -660,11 +666,11 @@ int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec)
     RowOrder ord[3]; int n = 0, which[3];
     auto want = [&](int k, int njobs, int S, int ldg, int ldh, const int32_t* lens, int add) {
         GruArgs a{};
-        gru_common(h, w, a, njobs, S, B, ldg, ldh, lens);
-        int Tm = 0, cpj = 0, nrb = 0;
-        if (S < 2 || !gru_team_shape(a, true, true, &Tm, &cpj, &nrb)) return;
-        ord[n] = RowOrder{lens, add, Tm, cpj, w.ord_perm[k], w.ord_slens[k]};
-        which[n++] = k; w.ord_T[k] = Tm; w.ord_cpj[k] = cpj;
+        gru_common(h, w, a, njobs, S, B, ldg, ldh, lens, w.Bx);
+        const GruPlan p = gru_plan(a, true, true);
+        if (p.form != GruForm::team) return;
+        ord[n] = RowOrder{lens, add, p.T, p.cpj, w.ord_perm[k], w.ord_slens[k]};
+        which[n++] = k; w.ord_T[k] = p.T; w.ord_cpj[k] = p.cpj;
     };
     want(0, 2, Ss, 6 * D, 2 * D, w.lens_src, 0);          // (every layer but a one-step top layer carries both directions)
     if (top_one_step(h)) want(1, 1, Ss, 6 * D, 2 * D, w.lens_src, 0);
@@ -689,17 +695,13 @@ int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec)
 // gates, h_prev) and on to the GEMMs (h, gate gradients) can be 16-bit.
 static bool both_team_bf16(avae_ctx* h, const GruArgs& a, bool train)
 {
-    int T = 0, cpj = 0, nrb = 0;
-    GruArgs q = a; q.sv16 = 0; q.slens = nullptr; q.perm = nullptr;
-    for (int i = 0; i < q.njobs; ++i) { q.job[i].dgi16 = nullptr; q.job[i].dgh16 = nullptr; q.job[i].gi_rows = nullptr; q.job[i].hs16 = nullptr; q.job[i].hp16 = nullptr; }
-    q.p_begin = 0; q.p_end = q.S;
-    return train && a.bf16 && a.S > 1 && gru_team_shape(q, true, h->persistent != 0, &T, &cpj, &nrb) && gru_team_shape(q, false, h->persistent != 0, &T, &cpj, &nrb);
+    return train && a.bf16 && gru_plan(a, true, h->persistent != 0).full() && gru_plan(a, false, h->persistent != 0).full();
 }
 static void attach_sv16(avae_ctx* h, GruArgs& a, bool train) { a.sv16 = h->bf16_sv && both_team_bf16(h, a, train); }
 static void attach_order(avae_ctx* h, const Ws& w, GruArgs& a, bool fwd, int k)
 {
-    int T = 0, cpj = 0, nrb = 0;
-    if (!w.ord_ok[k] || !gru_team_shape(a, fwd, h->persistent != 0, &T, &cpj, &nrb) || T != w.ord_T[k] || cpj != w.ord_cpj[k]) return;
+    const GruPlan p = gru_plan(a, fwd, h->persistent != 0);
+    if (!w.ord_ok[k] || !p.team() || p.T != w.ord_T[k] || p.cpj != w.ord_cpj[k]) return;
     a.slens = w.ord_slens[k]; a.perm = w.ord_perm[k];
 }
 
@@ -716,37 +718,30 @@ int build_compact(avae_ctx* h, Ws& w, int B, int Ss, int T, bool train)
     if (phantom && !(w.ord_ok[0] && (w.ord_ok[1] || !top_one_step(h)))) return 0;
     if (h->compact == 2 && !phantom) {
         // auto: the layout pays where a good share of the padded positions is padding; on FULL batches the static row counts shape
-        // the GEMM launches a little better (16.48 vs 16.71 ms at configs[1]; break-even at a fill of 0.93).  The hint is an EARLIER call's count (no synchronisation).
-        // (both words in ONE 8-byte load: the copy that lands them is 8 bytes, so a pair is never half of one call and half of another)
-        const uint64_t pair = h->hint_host ? *reinterpret_cast<const volatile uint64_t*>(h->hint_host) : 0xffffffffull;
-        const int32_t real = (int32_t)(uint32_t)(pair & 0xffffffffull), rows = (int32_t)(uint32_t)(pair >> 32);
-        if (real < 0 || rows <= 0 || (double)real >= 0.92 * (double)rows) return 0;
+        // the GEMM launches a little better (16.48 vs 16.71 ms at configs[1]; break-even at a fill of 0.93).  Nothing arrived yet: no layout.
+        const FillHint f = fill_hint(h);
+        if (f.real < 0 || f.rows <= 0 || (double)f.real >= 0.92 * (double)f.rows) return 0;
     }
     const int D = h->cfg.dim_emb;
-    for (int njobs = 1; njobs <= 2; ++njobs) {
-        if (njobs == 1 && !top_one_step(h)) continue;
+    // every launch of the stack on the team kernels (training: the BPTT too)
+    auto team = [&](int njobs, int S, int ldg, int ldh, const int32_t* lens) {
         GruArgs q{};
-        gru_common(h, w, q, njobs, Ss, B, 6 * D, 2 * D, w.lens_src);
-        int T = 0, cpj = 0, nrb = 0;
-        if (!gru_team_shape(q, true, true, &T, &cpj, &nrb) || (train && !gru_team_shape(q, false, true, &T, &cpj, &nrb))) return 0;
-    }
+        gru_common(h, w, q, njobs, S, B, ldg, ldh, lens, w.Bx);
+        return gru_plan(q, true, true).full() && (!train || gru_plan(q, false, true).full());
+    };
+    if (!team(2, Ss, 6 * D, 2 * D, w.lens_src) || (top_one_step(h) && !team(1, Ss, 6 * D, 2 * D, w.lens_src))) return 0;
     AV_CHECK(row_map(h->stream, w.lens_src, 0, Ss, B, w.map_src, w.nact_src, w.nsrc));
     w.compact = true;
-    {   // the fill the host last saw, scaled to this call's rows: shapes the launches of the GEMMs over the compact rows
-        const uint64_t pair = h->hint_host ? *reinterpret_cast<const volatile uint64_t*>(h->hint_host) : 0xffffffffull;
-        const int32_t real = (int32_t)(uint32_t)(pair & 0xffffffffull), rows = (int32_t)(uint32_t)(pair >> 32);
-        const double fill = (real > 0 && rows > 0) ? std::min(1.0, (double)real / (double)rows) : 0.0;
+    {   // the fill the host last saw, scaled to this call's rows: shapes the launches of the GEMMs over the compact rows (0: unknown)
+        const FillHint f = fill_hint(h);
+        const double fill = (f.real > 0 && f.rows > 0) ? std::min(1.0, (double)f.real / (double)f.rows) : 0.0;
         h->expect_ptr[0] = w.nsrc; h->expect_val[0] = (int)(fill * Ss * B);
         h->expect_ptr[1] = w.ntgt; h->expect_val[1] = (int)(fill * T * B);
         h->expect_ptr[2] = w.ntok; h->expect_val[2] = (int)(fill * T * B);      // (the unmasked decoder tokens: the same share of T x B for prefix masks)
     }
     // the decoder stack the same way (training / evaluation calls: T > 1): a row's steps end one behind its last non-eos target id
     if (T < 2 || !use_table(h, T * B, B) || h->compact == 3) return 0;      // (3: the encoder alone, for measurements)
-    if (phantom && !w.ord_ok[2]) return 0;
-    GruArgs q{};
-    gru_common(h, w, q, 1, T, B, 3 * D, D, nullptr);
-    int Tm = 0, cpj = 0, nrb = 0;
-    if (!gru_team_shape(q, true, true, &Tm, &cpj, &nrb) || (train && !gru_team_shape(q, false, true, &Tm, &cpj, &nrb))) return 0;
+    if ((phantom && !w.ord_ok[2]) || !team(1, T, 3 * D, D, nullptr)) return 0;
     AV_CHECK(row_map(h->stream, w.lens_tgt, 1, T, B, w.map_tgt, w.nact_tgt, w.ntgt));
     w.compact_d = true;
     return 0;
@@ -780,13 +775,10 @@ int run_encoder(avae_ctx* h, Ws& w, int B, int Ss, bool save)
         h->keep_a16 = nullptr;
         }
         GruArgs a{};
-        a.njobs = top1 ? 1 : 2; a.S = Ss; a.B = B; a.D = D; a.ldg = 6 * D; a.ldh = 2 * D; a.lens = w.lens_src;
-        a.Bx = w.bx_enc();
-        gru_geometry(D, a.njobs, B, &a.G, &a.rows_per_group);
-        a.p_begin = 0; a.p_end = Ss; a.counters = h->counters; a.err = h->errw; a.ablate = h->gru_ablate; a.force_slow = h->gru_force_slow; a.bf16 = h->cfg.compute_dtype == 1 && h->gru_bf16; a.stagger = h->gru_stagger; a.item_pipeline = h->gru_item; a.xbuf = w.xbuf; a.xbuf_floats = w.xbuf_floats; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.bwd_rs = h->bwd_rs != 0;
+        gru_common(h, w, a, top1 ? 1 : 2, Ss, B, 6 * D, 2 * D, w.lens_src, w.bx_enc());
         // table-fed layer: the team kernels read gi straight out of the per-id projection through a row index per token;
         // the other kernel forms get a per-token copy
-        const bool table0 = i == 0 && table, indirect = table0 && gru_forward_uses_team(a, h->persistent != 0);
+        const bool table0 = i == 0 && table, indirect = table0 && gru_plan(a, true, h->persistent != 0).form == GruForm::team;
         if (indirect) AV_CHECK(rank_rows(h->stream, w.tokrow_src, w.src_tm, id_groups_rank(w.grp_src, rs, V), rs, V));
         else if (table0) AV_CHECK(rows_gather_ranked(h->stream, w.e_gi[0], w.ew, w.src_tm, id_groups_rank(w.grp_src, rs, V), rs, 6 * D, V));
         for (int d = 0; d < a.njobs; ++d) {
@@ -808,7 +800,7 @@ int run_encoder(avae_ctx* h, Ws& w, int B, int Ss, bool save)
         }
         attach_order(h, w, a, true, top1 ? 1 : 0);
         a.rowmap = cmap;
-        a.spec = spec_pick(h, a.njobs, B);
+        a.spec = spec_pick(h);
         { Timed t(h, 1, 2.0 * a.njobs * Ss * (double)B * D * 3 * D);
           DeviceTurn turn(h);
           AV_GRU(gru_forward(h->stream, a, h->persistent != 0)); }
@@ -868,12 +860,9 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
         h->keep_a16 = nullptr;
         }
         GruArgs a{};
-        a.njobs = 1; a.S = T; a.B = B; a.D = D; a.ldg = 3 * D; a.ldh = D; a.lens = nullptr;
-        a.Bx = compact ? w.Bx : 0;
-        gru_geometry(D, 1, B, &a.G, &a.rows_per_group);
-        a.p_begin = 0; a.p_end = T; a.counters = h->counters; a.err = h->errw; a.ablate = h->gru_ablate; a.force_slow = h->gru_force_slow; a.bf16 = h->cfg.compute_dtype == 1 && h->gru_bf16; a.stagger = h->gru_stagger; a.item_pipeline = h->gru_item; a.xbuf = w.xbuf; a.xbuf_floats = w.xbuf_floats; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.bwd_rs = h->bwd_rs != 0;
+        gru_common(h, w, a, 1, T, B, 3 * D, D, nullptr, compact ? w.Bx : 0);
         GruJob& j = a.job[0];
-        const bool table0 = i == 0 && ids0, indirect = table0 && gru_forward_uses_team(a, h->persistent != 0);
+        const bool table0 = i == 0 && ids0, indirect = table0 && gru_plan(a, true, h->persistent != 0).form == GruForm::team;
         if (indirect) AV_CHECK(rank_rows(h->stream, w.tokrow_tgt, ids0, id_groups_rank(w.grp_tgt, rt, h->cfg.dim_tgt), rt, h->cfg.dim_tgt));
         else if (table0) AV_CHECK(rows_gather_ranked(h->stream, w.d_gi[0], w.ew, ids0, id_groups_rank(w.grp_tgt, rt, h->cfg.dim_tgt), rt, 3 * D, h->cfg.dim_tgt));
         j.gi = indirect ? w.ew : w.d_gi[i]; j.gi_rows = indirect ? w.tokrow_tgt : nullptr;
@@ -890,7 +879,7 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
         }
         if (T > 1) attach_order(h, w, a, true, 2);
         a.rowmap = cmap;
-        a.spec = spec_pick(h, 1, B);
+        a.spec = spec_pick(h);
         { Timed t(h, 1, 2.0 * T * (double)B * D * 3 * D);
           DeviceTurn turn(h);
           AV_GRU(gru_forward(h->stream, a, h->persistent != 0)); }
@@ -1008,10 +997,7 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
     for (int i = L - 1; i >= 0; --i) {
         const GruP& p = h->dec[i];
         GruArgs a{};
-        a.njobs = 1; a.S = T; a.B = B; a.D = D; a.ldg = 3 * D; a.ldh = D; a.lens = nullptr;
-        a.Bx = w.bx_dec();
-        gru_geometry(D, 1, B, &a.G, &a.rows_per_group);
-        a.p_begin = 0; a.p_end = T; a.counters = h->counters; a.err = h->errw; a.ablate = h->gru_ablate; a.force_slow = h->gru_force_slow; a.bf16 = h->cfg.compute_dtype == 1 && h->gru_bf16; a.stagger = h->gru_stagger; a.item_pipeline = h->gru_item; a.xbuf = w.xbuf; a.xbuf_floats = w.xbuf_floats; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.bwd_rs = h->bwd_rs != 0;
+        gru_common(h, w, a, 1, T, B, 3 * D, D, nullptr, w.bx_dec());
         GruJob& j = a.job[0];
         j.R = P + p.R; j.sv = w.d_sv[i]; j.hp = w.d_hp[i]; j.reverse = 0;
         j.dh_out = w.dhd[cur]; j.dgi = w.dgi_d; j.dgh = w.dgh_d;
@@ -1019,9 +1005,10 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
         j.dbW = G + p.bW; j.dbR = G + p.bR;
         // bf16 mode: the team kernels write the gate gradients as bf16, the operand of the three GEMMs below as it stands
         // (a table-fed layer keeps fp32: its gradients are summed by id first)
-        const bool g16 = tn16_ok(h, 3 * D, D) && a.bf16 && !(i == 0 && use_table(h, rt, B)) && gru_backward_uses_team(a, h->persistent != 0);
+        const bool team16 = tn16_ok(h, 3 * D, D) && a.bf16 && gru_plan(a, false, h->persistent != 0).full();
+        const bool g16 = team16 && !(i == 0 && use_table(h, rt, B));
         // (a table-fed layer: dgh alone as bf16 -- its dR GEMM reads it and the bf16 h_prev as they stand; dgi stays fp32 for the sum by id)
-        const bool gh16 = !g16 && w.dgh16_d && tn16_ok(h, 3 * D, D) && a.bf16 && w.acth_d[i] && gru_backward_uses_team(a, h->persistent != 0);
+        const bool gh16 = !g16 && w.dgh16_d && team16 && w.acth_d[i];
         if (g16) { j.dgi16 = w.dgi16_d; j.dgh16 = w.dgh16_d; }
         if (gh16) j.dgh16 = w.dgh16_d;
         if (!g16 && !gh16 && w.acth_d[i]) return fail(h, "internal: the forward kept this layer's h_prev as bf16 only and the backward cannot read it");
@@ -1030,7 +1017,7 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
         attach_order(h, w, a, false, 2);
         a.rowmap = dmap;
         if (dmap && i == 0) j.dgi_by_pos = 1;       // (table-fed: its gate gradients are summed by token id)
-        a.bwd_rs = rs_pick(h, 1, B); a.spec = spec_pick(h, 1, B);
+        a.bwd_rs = rs_pick(h); a.spec = spec_pick(h);
         hook_fence(h);
         { Timed t(h, 2, 2.0 * T * (double)B * D * 3 * D);
           DeviceTurn turn(h);
@@ -1105,10 +1092,7 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
             AV_CHECK(colsum(st, w.dghb, B, 3 * D, 3 * D, G + p.bR + 3 * D, nullptr));
         }
         GruArgs a{};
-        a.njobs = top1 ? 1 : 2; a.S = Ss; a.B = B; a.D = D; a.ldg = 6 * D; a.ldh = 2 * D; a.lens = w.lens_src;
-        a.Bx = w.bx_enc();
-        gru_geometry(D, a.njobs, B, &a.G, &a.rows_per_group);
-        a.p_begin = 0; a.p_end = Ss; a.counters = h->counters; a.err = h->errw; a.ablate = h->gru_ablate; a.force_slow = h->gru_force_slow; a.bf16 = h->cfg.compute_dtype == 1 && h->gru_bf16; a.stagger = h->gru_stagger; a.item_pipeline = h->gru_item; a.xbuf = w.xbuf; a.xbuf_floats = w.xbuf_floats; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.bwd_rs = h->bwd_rs != 0;
+        gru_common(h, w, a, top1 ? 1 : 2, Ss, B, 6 * D, 2 * D, w.lens_src, w.bx_enc());
         for (int d = 0; d < a.njobs; ++d) {
             GruJob& j = a.job[d];
             j.R = P + p.R + (int64_t)d * 3 * D * D; j.sv = w.e_sv[d][i]; j.hp = w.e_hp[d][i]; j.reverse = d;
@@ -1116,8 +1100,9 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
             j.dh0 = nullptr; j.carry = w.carry + (size_t)d * w.Bx * D;
             j.dbW = G + p.bW + d * 3 * D; j.dbR = G + p.bR + d * 3 * D;
         }
-        const bool g16 = tn16_ok(h, 3 * D, D) && a.bf16 && !(i == 0 && use_table(h, rs, B)) && gru_backward_uses_team(a, h->persistent != 0);
-        const bool gh16 = !g16 && w.dgh16_e && tn16_ok(h, 3 * D, D) && a.bf16 && w.acth_e[i] && gru_backward_uses_team(a, h->persistent != 0);      // (table-fed layer: see the decoder)
+        const bool team16 = tn16_ok(h, 3 * D, D) && a.bf16 && gru_plan(a, false, h->persistent != 0).full();
+        const bool g16 = team16 && !(i == 0 && use_table(h, rs, B));
+        const bool gh16 = !g16 && w.dgh16_e && team16 && w.acth_e[i];      // (table-fed layer: see the decoder)
         if (g16) for (int d = 0; d < a.njobs; ++d) { a.job[d].dgi16 = w.dgi16_e + d * 3 * D; a.job[d].dgh16 = w.dgh16_e + d * 3 * D; }
         if (gh16) for (int d = 0; d < a.njobs; ++d) a.job[d].dgh16 = w.dgh16_e + d * 3 * D;
         if (!g16 && !gh16 && w.acth_e[i]) return fail(h, "internal: the forward kept this layer's h_prev as bf16 only and the backward cannot read it");
@@ -1126,7 +1111,7 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
         attach_order(h, w, a, false, top1 ? 1 : 0);
         a.rowmap = cmap;
         if (cmap && i == 0) for (int d = 0; d < a.njobs; ++d) a.job[d].dgi_by_pos = 1;      // (table-fed: its gate gradients are summed by token id)
-        a.bwd_rs = rs_pick(h, a.njobs, B); a.spec = spec_pick(h, a.njobs, B);
+        a.bwd_rs = rs_pick(h); a.spec = spec_pick(h);
         hook_fence(h);
         { Timed t(h, 2, 2.0 * a.njobs * (Ss - 1) * (double)B * D * 3 * D);
           DeviceTurn turn(h);
