@@ -111,12 +111,19 @@ __device__ __forceinline__ void p8_whole_lines(f32x4 x, f32x4 y, int odd, f32x4&
 constexpr bool p8_of_a(int piece) { return piece == AE || piece == AL; }
 struct P8Item { int m0, n0, kt0, nkt, z, tl; };
 
-// two floats -> one dword of two fp16 (round to nearest even)
+// two floats -> one dword of two fp16 (round to nearest even), saturated to +-65504: a logit beyond the fp16 range becomes the
+// largest finite value, not inf (an inf in the panel turns the softmax row into inf - inf = NaN).  A NaN stays NaN (a diverged step
+// must still show in the loss): IEEE-754-2019 maximum / minimum propagate a NaN operand (v_maximum3_f32 / v_minimum3_f32, two VALU
+// operations), where fmaxf / fminf -- and v_med3_f32 -- would return the bound.
+__device__ __forceinline__ float p8_sat_f16(float x)
+{
+    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -65504.f), 65504.f);
+}
 __device__ __forceinline__ unsigned p8_pk_f16(float a, float b)
 {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     typedef float f2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, h2));
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{p8_sat_f16(a), p8_sat_f16(b)}, h2));
 }
 
 // H16: the output tile leaves as fp16 (P8Args::C16; no bias, no accumulate, no K split): half the bytes of the store drain that a K = 512 tile waits for

@@ -231,6 +231,9 @@ struct CeArgs {
     unsigned short* grad16;   // optional (N,V) bf16: with write_grad the gradient goes HERE (the bf16 GEMM's operand panel) and the logits stay
     int logits16;             // the logits are the fp16 panel the GEMM left IN grad16 (GemmArgs::c16): read from there, overwritten in place by the bf16 gradient
 };
+// the kernel form softmax_ce launches for a: 0 the register form (V <= 8192), 1 the fp16-panel form (logits16, V <= 8192, V % 8 == 0),
+// 2 the streaming form (V > 8192); -1 where softmax_ce refuses the arguments
+int softmax_ce_form(const CeArgs& a);
 hipError_t softmax_ce(hipStream_t st, const CeArgs& a);
 // pred[i] = argmax_j logits[i, j]  (first max), rows < n
 hipError_t argmax_rows(hipStream_t st, const float* logits, int32_t* pred, int n, int V);

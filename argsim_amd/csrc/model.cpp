@@ -919,7 +919,7 @@ int forward(avae_ctx* h, Ws& w, const int32_t* src, const int32_t* tgt, int B, i
     if (train && h->cfg.compute_dtype == 1 && (V & 7) == 0) {      // bf16 mode: the gradient is written as the backward GEMMs' bf16 operand
         AV_TRY(grow_bf16(h, &h->bfP, &h->bfP_cap, (size_t)rt * V));
         c.grad16 = h->bfP;
-        // ... and where the phased GEMM takes the whole product, the logits themselves go THERE as fp16 (2^-12 relative, finer than the bf16
+        // ... and where the phased GEMM takes the whole product, the logits themselves go THERE as fp16 (2^-11 relative, finer than the bf16
         // gradient they become): no fp32 logits are written or read -- 4.3 GB of 10.8 GB at configs[2]
         GemmArgs probe{nullptr, nullptr, nullptr, nullptr, rt, V, D, D, D, V, 1.f, 0, 1, w.ntok, 1, 0, 0, nullptr, nullptr, nullptr, nullptr};
         probe.nt8 = h->bf16_nt8;
@@ -1561,6 +1561,30 @@ int avae_debug_gemm_tn16(avae_handle h, const float* A, const float* Bm, float* 
 {
     if (!h) return 1;
     return gemm_tn16(h, nullptr, A, lda, nullptr, Bm, ldb, Cm, ldc, M, N, K, alpha, nullptr);
+}
+// test hook: softmax_ce (ops.hip) on caller buffers, enqueued on the handle's stream.  logits (n_max x V fp32) and panel (n_max x V,
+// 2-byte) as CeArgs::logits / grad16: with write_grad the gradient goes to panel as bf16 when panel is given, else over the logits;
+// logits16 reads the logits from panel as fp16.  *form_out = softmax_ce_form (0 register, 1 fp16 panel, 2 streaming, -1 refused).
+int avae_debug_softmax_ce(avae_handle h, float* logits, unsigned short* panel, int logits16, const int32_t* gold, const int32_t* cidx,
+                          const int32_t* n_dev, int n_max, int V, int write_grad, float inv_n, float* loss_samp, float* errt,
+                          int32_t* pred, int* form_out)
+{
+    if (!h || !form_out) return 1;
+    CeArgs c{};
+    c.logits = logits; c.gold = gold; c.cidx = cidx; c.n_dev = n_dev; c.n_max = n_max; c.V = V;
+    c.write_grad = write_grad; c.inv_n = inv_n;
+    c.loss_samp = loss_samp; c.errt_samp = errt; c.pred = pred; c.loss_acc = nullptr;
+    c.grad16 = panel; c.logits16 = logits16;
+    *form_out = softmax_ce_form(c);
+    AV_CHECK(softmax_ce(h->stream, c));
+    return 0;
+}
+// test hook: argmax_rows (ops.hip, the stepwise decode's first-maximum) on caller buffers, enqueued on the handle's stream
+int avae_debug_argmax_rows(avae_handle h, const float* logits, int32_t* pred, int n, int V)
+{
+    if (!h) return 1;
+    AV_CHECK(argmax_rows(h->stream, logits, pred, n, V));
+    return 0;
 }
 int avae_bucket_count(avae_handle h) { return h ? (int)h->buckets.size() : 0; }
 int avae_bucket_info(avae_handle h, int i, int64_t* offset, int64_t* count)

@@ -1028,14 +1028,21 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(CeArgs a)
     __syncthreads();
     if (tid == 0 && a.loss_acc) atomicAdd(a.loss_acc, s_acc);
 }
+int softmax_ce_form(const CeArgs& a)
+{
+    if (a.V & 3) return -1;
+    if (a.logits16 && (!a.grad16 || !a.write_grad)) return -1;      // (the fp16 panel is read where the bf16 gradient is written)
+    if (a.logits16 && a.V <= 8192 && (a.V & 7) == 0 && !a.loss_acc) return 1;
+    return a.V <= 8192 ? 0 : 2;
+}
 hipError_t softmax_ce(hipStream_t st, const CeArgs& a)
 {
     if (a.n_max <= 0) return hipSuccess;
-    if (a.V & 3) return hipErrorInvalidValue;
-    if (a.logits16 && (!a.grad16 || !a.write_grad)) return hipErrorInvalidValue;      // (the fp16 panel is read where the bf16 gradient is written)
-    if (a.logits16 && a.V <= 8192 && (a.V & 7) == 0 && !a.loss_acc) hipLaunchKernelGGL(softmax_ce_h16_kernel, dim3(min(a.n_max, 8192)), dim3(256), 0, st, a);
-    else if (a.V <= 8192) hipLaunchKernelGGL(softmax_ce_reg_kernel, dim3(min(a.n_max, 8192)), dim3(256), 0, st, a);
-    else             hipLaunchKernelGGL(softmax_ce_kernel, dim3(min(a.n_max, 8192)), dim3(256), 0, st, a);
+    const int form = softmax_ce_form(a);
+    if (form < 0) return hipErrorInvalidValue;
+    if (form == 1)      hipLaunchKernelGGL(softmax_ce_h16_kernel, dim3(min(a.n_max, 8192)), dim3(256), 0, st, a);
+    else if (form == 0) hipLaunchKernelGGL(softmax_ce_reg_kernel, dim3(min(a.n_max, 8192)), dim3(256), 0, st, a);
+    else                hipLaunchKernelGGL(softmax_ce_kernel, dim3(min(a.n_max, 8192)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

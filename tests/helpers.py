@@ -87,3 +87,30 @@ def rel_l2(a, b):
     b = np.asarray(b, np.float64).ravel()
     d = np.linalg.norm(b)
     return np.linalg.norm(a - b) / (d if d > 0 else 1.0)
+
+
+def ce_scale(inv_n, n_dev, n_max):
+    """the gradient scale softmax_ce applies (kernels.h CeArgs): inv_n itself (as the fp32 value the kernel receives), or
+    1 / n over the rows it processes, n = min(n_max, *n_dev), when inv_n <= 0"""
+    if inv_n > 0:
+        return float(np.float32(inv_n))
+    return 1.0 / max(min(n_max, n_dev), 1)
+
+
+def softmax_ce_reference(x, labels, scale):
+    """float64 restatement of model.py:170-181 on the given logit values, row by row (torch tensors, any device).
+    x: (n, V) logits -- pass the values the kernel reads (an fp16 panel widened exactly); labels: (n,) ints.
+    -> loss = logsumexp(x) - x[label], pred = FIRST argmax, errt = (pred != label), grad = (softmax(x) - onehot(label)) * scale."""
+    import torch
+    x = x.to(torch.float64)
+    labels = labels.to(device=x.device, dtype=torch.long)
+    m = x.max(-1, keepdim=True).values
+    e = torch.exp(x - m)
+    s = e.sum(-1, keepdim=True)
+    loss = (m + torch.log(s))[:, 0] - x.gather(1, labels[:, None])[:, 0]
+    col = torch.arange(x.shape[1], device=x.device).expand_as(x)
+    pred = torch.where(x == m, col, torch.full_like(col, x.shape[1])).min(-1).values      # the first maximum, whatever argmax does on ties
+    errt = (pred != labels).to(torch.float64)
+    grad = e / s
+    grad[torch.arange(x.shape[0], device=x.device), labels] -= 1.0
+    return loss, pred, errt, grad * scale

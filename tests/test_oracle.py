@@ -114,3 +114,32 @@ def test_golden_fixtures(name):
         _, grads = vt.loss_and_grads(P, cfg, ids, ids, 20000, keep, eps)
         for k, g in grads.items():
             assert abs(float(gold['gnorm/' + k]) - np.linalg.norm(g)) <= 1e-9 * max(1.0, np.linalg.norm(g)), k
+
+
+def test_softmax_ce_reference_is_the_oracles_cross_entropy():
+    """tests/helpers.softmax_ce_reference (what the softmax_ce kernels are checked against) computes the oracle's own operation:
+    on the train forward of a small case, loss / pred / errt equal vae_numpy.forward's per-token values and the gradient at
+    scale 1 / N equals autograd of vae_torch's mean cross-entropy with respect to the logits; on rows with a duplicated maximum
+    pred is the first index, as numpy's argmax (the oracle's) returns it."""
+    from helpers import ce_scale, softmax_ce_reference
+    cfg, P, ids, keep, eps = make_case('mid')
+    o = vn.forward(P, cfg, ids, ids, 'train', 20000, keep, eps)
+    x, lab = torch.as_tensor(o['logits']), torch.as_tensor(o['labels'])
+    n = x.shape[0]
+    loss, pred, errt, grad = softmax_ce_reference(x, lab, ce_scale(0.0, n, n))
+    assert np.allclose(loss.numpy(), o['loss_gen_samp'], rtol=1e-12, atol=1e-12)
+    assert np.array_equal(pred.numpy(), o['pred'])
+    assert np.array_equal(errt.numpy(), o['errt_samp'])
+    ot = vt.forward(vt.to_torch(P), cfg, ids, ids, 'train', 20000, keep, eps)
+    ot['logits'].retain_grad()
+    ot['loss_gen'].backward()
+    assert torch.allclose(ot['logits'].detach(), x, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(grad, ot['logits'].grad, rtol=1e-10, atol=1e-15)
+    assert abs(ce_scale(1e-3, n, n) - float(np.float32(1e-3))) == 0.0 and ce_scale(-1.0, 0, 5) == 1.0 and ce_scale(0.0, 9, 5) == 0.2
+    # ties: the first maximum
+    rng = np.random.default_rng(0)
+    t = rng.standard_normal((6, 40))
+    for r, (i, j) in enumerate([(0, 1), (3, 39), (17, 18), (0, 39), (5, 6), (38, 39)]):
+        t[r, i] = t[r, j] = t[r].max() + 1.0
+    _, pt, _, _ = softmax_ce_reference(torch.as_tensor(t), torch.zeros(6, dtype=torch.long), 1.0)
+    assert np.array_equal(pt.numpy(), t.argmax(-1)) and list(pt.numpy()) == [0, 3, 17, 0, 5, 38]
