@@ -17,7 +17,21 @@
 // Arithmetic: fp32 dot products with lane-split K and a butterfly reduction; same gate equations and activation
 // approximations as gru.hip.  The summation order differs from the MFMA path of avae_decode_step, so logits agree to
 // rounding, token ids exactly unless two logits tie to the last bit.
+//
+// Sampled decoding (avae_decode_sample; contract in include/argsim_vae.h) is the same kernel, kMode 1 and 2: the GRU and
+// `out` phases are the greedy ones, the synchronisation is untouched (same barriers per token, no new fence).
+//   * every logit kept (kMode 1): after the butterfly sum lane j < 8 of the wave takes logit vb + j, adds the Gumbel noise
+//     of (row, step, id) and keeps a candidate (score, id, l / T) and a running (max, sum exp) of l / T; the final phase
+//     merges the workgroups' partials as the greedy one merges its maxima, and gets the log-probability from the pairs.
+//   * top-k (kMode 2): the logits phase only stores the logits to a (b, V) scratch, write-through like every hand-off;
+//     the workgroup that owns the row reads them with sc1 loads (8 per thread at V = 8192, in registers), finds the k-th
+//     largest by a radix select over order-preserving keys (4 passes of 8 bits, 256-bin LDS histogram), then takes
+//     the first maximum of the noisy scores and the log-sum-exp over the kept set.
+//   * a row is finished at step t > 0 iff the id it is fed is eos (a finished row is fed eos from then on), so the id
+//     log itself is the finished flag: the row's owner reads one id and publishes eos with logp 0.
+// The greedy instantiation's device code is the parent's instruction for instruction (one kernel-argument offset moved).
 #include "kernels.h"
+#include "sample_dev.h"
 
 namespace avae {
 
@@ -87,7 +101,12 @@ __device__ __forceinline__ bool grid_barrier(unsigned* ctr, unsigned& target, in
 constexpr int kRows = 1;            // batch rows per wave and pass (2 was measured slower: register spills at 16 waves per CU)
 constexpr int kDecThreads = 1024, kDecWaves = kDecThreads / 64;     // sixteen rows of the batch in flight per workgroup
 
-__global__ __launch_bounds__(kDecThreads) void decode_greedy_kernel(DecodeArgs a)
+constexpr int kSelMax = 8;          // sampled decoding with top-k: logits per thread of the row's owner (V <= 8192)
+constexpr int kSelWords = 512;      // its LDS behind the weights: 258 words of the radix select, 16 x 5 of the wave results
+
+// kMode 0: greedy (model.py:204-219).  1: sampled, every logit kept.  2: sampled, top-k (see the header: sampled decoding)
+template <int kMode>
+__global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -121,6 +140,8 @@ __global__ __launch_bounds__(kDecThreads) void decode_greedy_kernel(DecodeArgs a
         for (int i = tid; i < (v1 - v0) * D; i += kDecThreads) El[i] = a.E[(size_t)v0 * D + i];
     __syncthreads();
 
+    [[maybe_unused]] unsigned* sel = reinterpret_cast<unsigned*>(El + (a.cache_e ? (size_t)vp * D : 0));      // kMode 2: kSelWords
+    [[maybe_unused]] const uint64_t skey = kMode != 0 ? sample_key(a.sp.seed) : 0;
     unsigned target = 0;
     int cur = 0, kept = a.steps;
     bool ok = true;
@@ -217,11 +238,13 @@ __global__ __launch_bounds__(kDecThreads) void decode_greedy_kernel(DecodeArgs a
         // ---- tied logits (model.py:166) over this workgroup's vocabulary rows, partial argmax (first maximum)
         for (int bb0 = wave; bb0 < b; bb0 += kDecWaves * kRows) {
             float best[kRows]; int besti[kRows];
+            float bx[kRows], lm[kRows], ls[kRows];              // sampled: lanes 0..7 each keep the candidate and the (max, sum exp) of the ids = lane mod 8
             float4 ov[kRows][2];                                  // this lane's slice of the `out` rows (D <= 512: two pieces)
 #pragma unroll
             for (int r = 0; r < kRows; ++r) {
                 const int bb = min(bb0 + r * kDecWaves, b - 1);
                 best[r] = -INFINITY; besti[r] = 0x7fffffff;
+                bx[r] = 0.f; lm[r] = -INFINITY; ls[r] = 0.f;
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const int k = lane * 4 + 256 * i;
@@ -248,23 +271,52 @@ __global__ __launch_bounds__(kDecThreads) void decode_greedy_kernel(DecodeArgs a
                     }
                 }
 #pragma unroll
-                for (int r = 0; r < kRows; ++r)
+                for (int r = 0; r < kRows; ++r) {
+                    float mine = 0.f;                              // sampled: lane j < 8 takes logit vb + j
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         if (vb + j >= v1) break;
                         const float v = wave_sum(p[r][j]) * a.isd;
-                        if (v > best[r]) { best[r] = v; besti[r] = vb + j; }      // ascending v: the first maximum stays
+                        if constexpr (kMode == 0) { if (v > best[r]) { best[r] = v; besti[r] = vb + j; } }      // ascending v: the first maximum stays
+                        else if (lane == j) mine = v;
                     }
+                    if constexpr (kMode != 0) {
+                        const int bb = bb0 + r * kDecWaves, v = vb + lane;
+                        if (lane < 8 && v < v1 && bb < b) {
+                            if constexpr (kMode == 2) st4_sc1(a.logits + (size_t)bb * V + v, mine);
+                            else {
+                                const float xs = mine * a.sp.inv_t;
+                                const float sc = a.sp.noise ? xs + gumbel(skey, sample_base(bb, t), v) : mine;
+                                if (sc > best[r]) { best[r] = sc; besti[r] = v; bx[r] = xs; }
+                                lse_add(lm[r], ls[r], xs);
+                            }
+                        }
+                    }
+                }
             }
 #pragma unroll
             for (int r = 0; r < kRows; ++r) {
                 const int bb = bb0 + r * kDecWaves;
-                if (lane == 0 && bb < b) { st4_sc1(a.part_val + (size_t)w * b + bb, best[r]); st4i_sc1(a.part_idx + (size_t)w * b + bb, besti[r]); }
+                if constexpr (kMode == 1) {
+#pragma unroll
+                    for (int o = 4; o > 0; o >>= 1) {            // lanes 8.. hold the neutral element
+                        const float ob = __shfl_xor(best[r], o, 64), ox = __shfl_xor(bx[r], o, 64), om = __shfl_xor(lm[r], o, 64), os = __shfl_xor(ls[r], o, 64);
+                        const int oi = __shfl_xor(besti[r], o, 64);
+                        if (cand_better(ob, oi, best[r], besti[r])) { best[r] = ob; besti[r] = oi; bx[r] = ox; }
+                        lse_merge(lm[r], ls[r], om, os);
+                    }
+                    if (lane == 0 && bb < b) {
+                        st4_sc1(a.part_x + (size_t)w * b + bb, bx[r]); st4_sc1(a.part_m + (size_t)w * b + bb, lm[r]); st4_sc1(a.part_s + (size_t)w * b + bb, ls[r]);
+                    }
+                }
+                if constexpr (kMode != 2)
+                    if (lane == 0 && bb < b) { st4_sc1(a.part_val + (size_t)w * b + bb, best[r]); st4i_sc1(a.part_idx + (size_t)w * b + bb, besti[r]); }
             }
         }
         ok = grid_barrier(a.bar, target, G, a.err);
         if (!ok) break;
         // ---- final argmax of row bb by workgroup bb mod G (vocabulary blocks ascend with the workgroup index)
+        if constexpr (kMode == 0) {
         if (wave == 0)
             for (int bb = w; bb < b; bb += G) {
                 float best = -INFINITY; int besti = 0x7fffffff;
@@ -280,6 +332,81 @@ __global__ __launch_bounds__(kDecThreads) void decode_greedy_kernel(DecodeArgs a
                 }
                 if (lane == 0) st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, besti);
             }
+        } else if constexpr (kMode == 1) {
+        // sampled: the same merge over (score, id), with the candidate's l inv_t and the (max, sum exp) pairs for its logp
+        if (wave == 0)
+            for (int bb = w; bb < b; bb += G) {
+                float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
+                for (int g = lane; g < G; g += 64) {
+                    const float v = ld4_sc1(a.part_val + (size_t)g * b + bb);
+                    const int vi = ld4i_sc1(a.part_idx + (size_t)g * b + bb);
+                    if (cand_better(v, vi, best, besti)) { best = v; besti = vi; bx = ld4_sc1(a.part_x + (size_t)g * b + bb); }
+                    lse_merge(m, s, ld4_sc1(a.part_m + (size_t)g * b + bb), ld4_sc1(a.part_s + (size_t)g * b + bb));
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+                    const int oi = __shfl_xor(besti, o, 64);
+                    if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
+                    lse_merge(m, s, om, os);
+                }
+                if (lane == 0) {
+                    const bool fin = t > 0 && ld4i_sc1(lead + bb) == a.eos;       // a row fed eos has finished: eos again, logp 0
+                    st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, fin ? a.eos : (besti == 0x7fffffff ? 0 : besti));
+                    if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, fin ? 0.f : lse_logp(bx, m, s));
+                }
+            }
+        } else {
+        // sampled with top-k: the owner of row bb reads the row's logits (kSelMax per thread, in registers), finds the k-th
+        // largest by the radix select, then first maximum and log-sum-exp over the kept set
+        for (int bb = w; bb < b; bb += G) {
+            if (t > 0 && ld4i_sc1(lead + bb) == a.eos) {                      // (uniform over the workgroup)
+                if (tid == 0) { st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, a.eos); if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, 0.f); }
+                continue;
+            }
+            const float* lr = a.logits + (size_t)bb * V;
+            float lv[kSelMax]; unsigned key[kSelMax];
+#pragma unroll
+            for (int i = 0; i < kSelMax; ++i) { const int c = tid + i * kDecThreads; lv[i] = c < V ? ld4_sc1(lr + c) : 0.f; }
+#pragma unroll
+            for (int i = 0; i < kSelMax; ++i) key[i] = order_key(lv[i]);
+            const unsigned thr = kth_largest_key([&](auto f) {
+#pragma unroll
+                for (int i = 0; i < kSelMax; ++i) if (tid + i * kDecThreads < V) f(key[i]);
+            }, (unsigned)a.sp.top_k, sel);
+            float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
+            const uint64_t base = sample_base(bb, t);
+#pragma unroll
+            for (int i = 0; i < kSelMax; ++i) {
+                const int c = tid + i * kDecThreads;
+                if (c >= V || lv[i] != lv[i] || key[i] < thr) continue;
+                const float xs = lv[i] * a.sp.inv_t;
+                const float sc = a.sp.noise ? xs + gumbel(skey, base, c) : lv[i];
+                if (sc > best) { best = sc; besti = c; bx = xs; }
+                lse_add(m, s, xs);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+                const int oi = __shfl_xor(besti, o, 64);
+                if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
+                lse_merge(m, s, om, os);
+            }
+            float* wf = reinterpret_cast<float*>(sel + 260);
+            if (lane == 0) { wf[wave * 5] = best; wf[wave * 5 + 1] = bx; wf[wave * 5 + 2] = m; wf[wave * 5 + 3] = s; wf[wave * 5 + 4] = __int_as_float(besti); }
+            __syncthreads();
+            if (tid == 0) {
+                for (int o = 1; o < kDecWaves; ++o) {
+                    const int oi = __float_as_int(wf[o * 5 + 4]);
+                    if (cand_better(wf[o * 5], oi, best, besti)) { best = wf[o * 5]; besti = oi; bx = wf[o * 5 + 1]; }
+                    lse_merge(m, s, wf[o * 5 + 2], wf[o * 5 + 3]);
+                }
+                st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, besti == 0x7fffffff ? 0 : besti);
+                if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, lse_logp(bx, m, s));
+            }
+            __syncthreads();
+        }
+        }
         ok = grid_barrier(a.bar, target, G, a.err);
         if (!ok) break;
         cur ^= 1;
@@ -292,6 +419,8 @@ __global__ __launch_bounds__(kDecThreads) void decode_greedy_kernel(DecodeArgs a
     for (size_t i = (size_t)w * kDecThreads + tid; i < (size_t)b * a.steps; i += (size_t)G * kDecThreads) {
         const int bb = (int)(i / a.steps), s = (int)(i % a.steps);
         a.out_ids[i] = s < kept ? ld4i_sc1(a.ids_tm + (size_t)(s + 1) * b + bb) : a.eos;
+        if constexpr (kMode != 0)            // the step that ended the loop (s == kept) holds the closing eos of the longest rows
+            if (a.logp_out) a.logp_out[i] = s <= kept ? ld4_sc1(a.logp_tm + (size_t)s * b + bb) : 0.f;
     }
     if (w == 0 && tid == 0) *a.kept = kept;
 }
@@ -303,7 +432,8 @@ int decode_workgroups()
     return cus;
 }
 
-hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out)
+template <int kMode>
+static hipError_t decode_launch(hipStream_t st, DecodeArgs a, int* grid_out)
 {
     int dev = 0, cus = 0, lds_max = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -316,23 +446,34 @@ hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out)
     if (nu > 2 || a.L > 8 || (a.D & 3) || a.D > 512) return hipErrorInvalidValue;
     size_t floats = (size_t)a.L * nu * 6 * a.D + (size_t)nu * a.D;
     const size_t with_e = floats + (size_t)vp * a.D;
-    a.cache_e = with_e * 4 + 64 <= (size_t)lds_max - 1024 ? 1 : 0;
+    const size_t extra = kMode == 2 ? kSelWords * 4 : 0;
+    a.cache_e = with_e * 4 + 64 + extra <= (size_t)lds_max - 1024 ? 1 : 0;
     if (a.cache_e) floats = with_e;
-    const int lds_bytes = (int)(floats * 4 + 64);
+    const int lds_bytes = (int)(floats * 4 + 64 + extra);
     if ((size_t)lds_bytes > (size_t)lds_max) return hipErrorInvalidValue;
     static int attr_set = 0;
     if (attr_set < lds_bytes) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_greedy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel<kMode>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
         if (e != hipSuccess) return e;
         attr_set = lds_bytes;
     }
     int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_greedy_kernel, kDecThreads, (size_t)lds_bytes);
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, decode_kernel<kMode>, kDecThreads, (size_t)lds_bytes);
     if (e != hipSuccess) return e;
     if (per_cu < 1) return hipErrorCooperativeLaunchTooLarge;     // the grid barrier needs every workgroup resident
     if (grid_out) *grid_out = G;
-    hipLaunchKernelGGL(decode_greedy_kernel, dim3(G), dim3(kDecThreads), lds_bytes, st, a);
+    hipLaunchKernelGGL(decode_kernel<kMode>, dim3(G), dim3(kDecThreads), lds_bytes, st, a);
     return hipGetLastError();
+}
+
+hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out) { return decode_launch<0>(st, a, grid_out); }
+
+hipError_t decode_sample(hipStream_t st, DecodeArgs a, int* grid_out)
+{
+    if (a.V > (1 << 20) || a.steps > (1 << 20) || a.sp.top_k < 0) return hipErrorInvalidValue;
+    if (a.sp.top_k == 0 || a.sp.top_k >= a.V) { a.sp.top_k = 0; return decode_launch<1>(st, a, grid_out); }
+    if (a.V > kSelMax * kDecThreads || !a.logits) return hipErrorInvalidValue;
+    return decode_launch<2>(st, a, grid_out);
 }
 
 }  // namespace avae

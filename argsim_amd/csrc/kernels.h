@@ -237,6 +237,13 @@ int softmax_ce_form(const CeArgs& a);
 hipError_t softmax_ce(hipStream_t st, const CeArgs& a);
 // pred[i] = argmax_j logits[i, j]  (first max), rows < n
 hipError_t argmax_rows(hipStream_t st, const float* logits, int32_t* pred, int n, int V);
+// sampled decoding (contract: include/argsim_vae.h, avae_decode_sample), as the kernels take it: inv_t = 1 / temperature (1 at
+// temperature 0), top_k = 0 keeps every logit, noise = 0 is the plain first maximum (temperature 0 or top_k 1)
+struct SampleParams { float inv_t; int top_k; int noise; uint64_t seed; };
+// one token per row of logits (n, V) at step t (row index = batch row): pred (n), logp (n, optional); lead (n, optional): the ids fed
+// at this step, a row fed eos at t > 0 is finished (token eos, logp 0)
+hipError_t sample_rows(hipStream_t st, const float* logits, int n, int V, int t, const SampleParams& sp, const int32_t* lead, int eos,
+                       int32_t* pred, float* logp);
 
 // out[n] (+)= sum_m X[m, n]
 hipError_t colsum(hipStream_t st, const float* X, int M, int N, int ldx, float* out, const int32_t* m_dev);
@@ -262,10 +269,18 @@ struct DecodeArgs {
     unsigned* bar;                                  // grid-barrier counter, zero on entry
     int* err;                                       // error word (spin time-out)
     int b, steps, D, V, L, eos, cache_e; float isd;
+    // decode_sample only
+    SampleParams sp;
+    float *part_x, *part_m, *part_s;                // (G, b) per workgroup: l inv_t of its candidate, running (max, sum exp) of l inv_t
+    float* logits;                                  // (b, V), top_k > 0: the step's logits for the row's owner
+    float* logp_tm;                                 // (steps, b) time-major log-probabilities, or null
+    float* logp_out;                                // (b, steps) result, 0 beyond a row's eos, or null
 };
 // returns hipErrorInvalidValue where the geometry does not fit (D / CUs > 2 units per workgroup, LDS), the caller
 // then falls back to one launch sequence per token; *grid_out = workgroups launched
 hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out);
+// the sampled loop in the same persistent form (a.sp; finished rows emit eos).  Also refuses top_k > 0 with V > 8192
+hipError_t decode_sample(hipStream_t st, DecodeArgs a, int* grid_out);
 int decode_workgroups();                            // CU count of the current device (size of part_val / part_idx rows)
 
 // natural <-> G16 row permutation of a (3D, cols) matrix (cols = 1 for biases)

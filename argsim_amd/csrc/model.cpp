@@ -1700,7 +1700,8 @@ int avae_decode_init(avae_handle h, const float* z, int32_t b, float* state_out)
     return 0;
 }
 
-static int decode_step_ws(avae_handle h, Ws& w, const int32_t* lead, const float* state_in, int b, int32_t* pred_out, float* state_out)
+// one decoder step up to the tied logits (b, V) in w.logits
+static int decode_logits_ws(avae_handle h, Ws& w, const int32_t* lead, const float* state_in, int b, float* state_out)
 {
     const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
     AV_CHECK(embed_gather(h->stream, h->P + h->oE, lead, w.emb_tgt, b, D, V));
@@ -1709,7 +1710,12 @@ static int decode_step_ws(avae_handle h, Ws& w, const int32_t* lead, const float
         AV_CHECK(hipMemcpyAsync(state_out + (size_t)i * b * D, w.d_hd[i], (size_t)b * D * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     AV_TRY(gemm(h, false, true, w.d_hd[L - 1], D, h->P + h->oKout, D, w.ho, D, b, D, D, 1.f, h->P + h->oBout));
     AV_TRY(gemm(h, false, false, w.ho, D, h->P + h->oE, D, w.logits, V, b, V, D, 1.f / sqrtf((float)D)));
-    AV_CHECK(argmax_rows(h->stream, w.logits, pred_out, b, V));
+    return 0;
+}
+static int decode_step_ws(avae_handle h, Ws& w, const int32_t* lead, const float* state_in, int b, int32_t* pred_out, float* state_out)
+{
+    AV_TRY(decode_logits_ws(h, w, lead, state_in, b, state_out));
+    AV_CHECK(argmax_rows(h->stream, w.logits, pred_out, b, h->cfg.dim_tgt));
     return 0;
 }
 
@@ -1725,8 +1731,9 @@ int avae_decode_step(avae_handle h, const int32_t* lead, const float* state_in, 
 }
 
 // one launch sequence per token with a host check every 16 tokens: the fallback where the persistent kernel's geometry
-// does not fit (decode.hip) and the reference form for tests (option "persistent" = 0)
-static int decode_greedy_stepwise(avae_handle h, const float* z, int32_t b, int32_t steps, int32_t* out_ids, int32_t* n_steps)
+// does not fit (decode.hip) and the reference form for tests (option "persistent" = 0).  sp: null = the greedy loop of
+// model.py:204-219; else sampled decoding (sample_rows per token: a row that has emitted eos stays eos, logp_out optional)
+static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps)
 {
     const int D = h->cfg.dim_emb, L = h->cfg.rnn_layers;
     Ws w;
@@ -1734,7 +1741,7 @@ static int decode_greedy_stepwise(avae_handle h, const float* z, int32_t b, int3
     const size_t sn = (size_t)L * b * D;
     float* state[2]; int32_t* ids_tm = nullptr;
     {
-        size_t need = 2 * sn * sizeof(float) + (size_t)(steps + 1) * b * sizeof(int32_t);
+        size_t need = 2 * sn * sizeof(float) + (size_t)(steps + 1) * b * sizeof(int32_t) + (sp ? (size_t)steps * b * sizeof(float) : 0);
         if (h->scratch_n < (int64_t)need) {
             AV_CHECK(hipStreamSynchronize(h->stream));
             if (h->scratch) AV_CHECK(hipFree(h->scratch));
@@ -1745,6 +1752,7 @@ static int decode_greedy_stepwise(avae_handle h, const float* z, int32_t b, int3
         state[0] = h->scratch; state[1] = h->scratch + sn;
         ids_tm = reinterpret_cast<int32_t*>(h->scratch + 2 * sn);
     }
+    float* const logp_tm = sp ? reinterpret_cast<float*>(ids_tm + (size_t)(steps + 1) * b) : nullptr;
     AV_TRY(avae_decode_init(h, z, b, state[0]));
     std::vector<int32_t> host((size_t)(steps + 1) * b);
     for (int i = 0; i < b; ++i) host[i] = h->cfg.bos;
@@ -1754,7 +1762,12 @@ static int decode_greedy_stepwise(avae_handle h, const float* z, int32_t b, int3
     while (done < steps) {
         int n = std::min(chunk, steps - done);
         for (int s = 0; s < n; ++s) {
-            AV_TRY(decode_step_ws(h, w, ids_tm + (size_t)(done + s) * b, state[cur], b, ids_tm + (size_t)(done + s + 1) * b, state[cur ^ 1]));
+            const int t = done + s;
+            if (!sp) AV_TRY(decode_step_ws(h, w, ids_tm + (size_t)t * b, state[cur], b, ids_tm + (size_t)(t + 1) * b, state[cur ^ 1]));
+            else {
+                AV_TRY(decode_logits_ws(h, w, ids_tm + (size_t)t * b, state[cur], b, state[cur ^ 1]));
+                AV_CHECK(sample_rows(h->stream, w.logits, b, h->cfg.dim_tgt, t, *sp, ids_tm + (size_t)t * b, h->cfg.eos, ids_tm + (size_t)(t + 1) * b, logp_tm + (size_t)t * b));
+            }
             cur ^= 1;
         }
         AV_CHECK(hipMemcpyAsync(host.data() + (size_t)(done + 1) * b, ids_tm + (size_t)(done + 1) * b, (size_t)n * b * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
@@ -1773,12 +1786,23 @@ static int decode_greedy_stepwise(avae_handle h, const float* z, int32_t b, int3
     std::vector<int32_t> outv((size_t)b * steps, h->cfg.eos);
     for (int s = 0; s < kept; ++s) for (int i = 0; i < b; ++i) outv[(size_t)i * steps + s] = host[(size_t)(s + 1) * b + i];
     AV_CHECK(hipMemcpyAsync(out_ids, outv.data(), outv.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    std::vector<float> lpv;
+    if (sp && logp_out) {        // the same transpose; position `kept` holds the closing eos of the longest rows, 0 beyond
+        const int nl = std::min(kept + 1, steps);
+        std::vector<float> lp((size_t)nl * b);
+        AV_CHECK(hipMemcpyAsync(lp.data(), logp_tm, lp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        AV_CHECK(hipStreamSynchronize(h->stream));
+        lpv.assign((size_t)b * steps, 0.f);
+        for (int s = 0; s < nl; ++s) for (int i = 0; i < b; ++i) lpv[(size_t)i * steps + s] = lp[(size_t)s * b + i];
+        AV_CHECK(hipMemcpyAsync(logp_out, lpv.data(), lpv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
     AV_CHECK(hipStreamSynchronize(h->stream));
     if (n_steps) *n_steps = kept;
     return check_gru_err(h);
 }
 
-int avae_decode_greedy(avae_handle h, const float* z, int32_t b, int32_t steps, int32_t* out_ids, int32_t* n_steps)
+// the greedy (sp null) or sampled loop: one persistent launch where it serves, else the launch-per-token loop
+static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps)
 {
     if (!h) return 1;
     AV_TRY(check_bound(h));
@@ -1787,13 +1811,15 @@ int avae_decode_greedy(avae_handle h, const float* z, int32_t b, int32_t steps, 
     // measured at D = 512, V = 8192, steps = 512 (scripts/decode_bench.py, profiles/r03_decode_bench.txt): the persistent launch
     // takes 42 / 74 / 145 us per token at b = 1 / 16 / 64, the launch-per-token loop 116-130 us at any b <= 128 (its
     // GEMMs are far from full): one launch up to 32 rows, the per-token loop above
-    if (!h->persistent || b > 32) return decode_greedy_stepwise(h, z, b, steps, out_ids, n_steps);
+    if (!h->persistent || b > 32) return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps);
     // the whole loop in ONE persistent launch (decode.hip); state, partial maxima and the id log live in the scratch buffer
     const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
     const int G = decode_workgroups();
     if (G < 1) return fail(h, "no HIP device");
     const size_t sn = (size_t)L * b * D;
-    const size_t nf = 2 * sn + (size_t)b * D + (size_t)G * b;                                 // floats: state x2, o, part_val
+    const bool topk = sp && sp->top_k > 0;
+    const size_t nfs = sp ? 3 * (size_t)G * b + (topk ? (size_t)b * V : 0) + (logp_out ? (size_t)steps * b : 0) : 0;     // sampled: part_x/m/s, logits, logp_tm
+    const size_t nf = 2 * sn + (size_t)b * D + (size_t)G * b + nfs;                           // floats: state x2, o, part_val
     const size_t ni = (size_t)G * b + (size_t)(steps + 1) * b + 16;                            // ints: part_idx, ids_tm, kept, barrier
     const size_t need = (nf + ni) * 4;
     if (h->scratch_n < (int64_t)need) {
@@ -1809,6 +1835,13 @@ int avae_decode_greedy(avae_handle h, const float* z, int32_t b, int32_t steps, 
     a.Kout = h->P + h->oKout; a.bout = h->P + h->oBout;
     a.state[0] = h->scratch; a.state[1] = h->scratch + sn;
     a.o = h->scratch + 2 * sn; a.part_val = a.o + (size_t)b * D;
+    if (sp) {
+        a.sp = *sp;
+        a.part_x = a.part_val + (size_t)G * b; a.part_m = a.part_x + (size_t)G * b; a.part_s = a.part_m + (size_t)G * b;
+        float* f = a.part_s + (size_t)G * b;
+        if (topk) { a.logits = f; f += (size_t)b * V; }
+        if (logp_out) { a.logp_tm = f; a.logp_out = logp_out; }
+    }
     int32_t* ip = reinterpret_cast<int32_t*>(h->scratch + nf);
     a.part_idx = ip; a.ids_tm = ip + (size_t)G * b;
     a.kept = a.ids_tm + (size_t)(steps + 1) * b; a.bar = reinterpret_cast<unsigned*>(a.kept + 8);
@@ -1819,17 +1852,58 @@ int avae_decode_greedy(avae_handle h, const float* z, int32_t b, int32_t steps, 
     AV_CHECK(hipMemcpyAsync(a.ids_tm, bos.data(), b * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     AV_CHECK(hipMemsetAsync(a.kept, 0, 16 * sizeof(int32_t), h->stream));
     int grid = 0;
-    hipError_t e = decode_greedy(h->stream, a, &grid);
+    hipError_t e = sp ? decode_sample(h->stream, a, &grid) : decode_greedy(h->stream, a, &grid);
     if (e == hipErrorInvalidValue) {                       // geometry outside the persistent kernel: same results, more launches
         AV_CHECK(hipStreamSynchronize(h->stream));           // (bos.data() is still being read)
-        return decode_greedy_stepwise(h, z, b, steps, out_ids, n_steps);
+        return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps);
     }
-    if (e == hipErrorCooperativeLaunchTooLarge) return fail(h, "greedy decode kernel: one workgroup per CU does not fit this device");
+    if (e == hipErrorCooperativeLaunchTooLarge) return fail(h, "persistent decode kernel: one workgroup per CU does not fit this device");
     AV_CHECK(e);
     int kept = 0;
     AV_CHECK(hipMemcpyAsync(&kept, a.kept, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     AV_TRY(check_gru_err(h));                               // synchronises
     if (n_steps) *n_steps = kept;
+    return 0;
+}
+
+int avae_decode_greedy(avae_handle h, const float* z, int32_t b, int32_t steps, int32_t* out_ids, int32_t* n_steps)
+{
+    return decode_loop(h, z, b, steps, nullptr, out_ids, nullptr, n_steps);
+}
+
+// avae_sample_config -> what the kernels take; false with the message set
+static bool sample_params(avae_handle h, const avae_sample_config* sc, int V, SampleParams* sp)
+{
+    if (!sc) { fail(h, "sample config is null"); return false; }
+    if (!(sc->temperature >= 0.f) || std::isinf(sc->temperature)) { fail(h, "sample: temperature must be a finite number >= 0"); return false; }
+    if (sc->top_k < 0) { fail(h, "sample: top_k must be >= 0"); return false; }
+    if (V > (1 << 20)) { fail(h, "sample: the noise index holds 2^20 vocabulary ids"); return false; }
+    const bool greedy = sc->temperature == 0.f;
+    sp->inv_t = greedy ? 1.f : 1.f / sc->temperature;
+    sp->top_k = greedy || sc->top_k >= V ? 0 : sc->top_k;         // temperature 0: logp is over all of V
+    sp->noise = !greedy && sc->top_k != 1;
+    sp->seed = sc->seed;
+    return true;
+}
+
+int avae_decode_sample(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_config* sc,
+                       int32_t* out_ids, float* logp_out, int32_t* n_steps)
+{
+    if (!h) return 1;
+    SampleParams sp{};
+    if (!sample_params(h, sc, h->cfg.dim_tgt, &sp)) return 1;
+    if (steps > (1 << 20)) return fail(h, "sample: the noise index holds 2^20 steps");
+    return decode_loop(h, z, b, steps, &sp, out_ids, logp_out, n_steps);
+}
+
+// test hook: sample_rows (ops.hip, the launch-per-token sampler) on caller buffers at step t0, row index = batch row
+int avae_debug_sample_rows(avae_handle h, const float* logits, int n, int V, int t0, const avae_sample_config* sc, int32_t* pred, float* logp)
+{
+    if (!h) return 1;
+    SampleParams sp{};
+    if (!sample_params(h, sc, V, &sp)) return 1;
+    if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
+    AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, nullptr, h->cfg.eos, pred, logp));
     return 0;
 }
 

@@ -3,19 +3,14 @@
 // column sums, TF-style Adam, layout permutation.  Each cites the reference lines it replaces.
 #include <algorithm>
 #include "kernels.h"
+#include "sample_dev.h"
 
 namespace avae {
 
 // ---------------------------------------------------------------- counter RNG
 // stateless: value = f(seed, stream, index).  (Not TF's Philox stream: the reference's draws
 // are unreproducible anyway; parity tests inject keep_mask / eps.)
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
+// (mix64 itself: sample_dev.h, shared with the samplers)
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t stream, uint64_t idx)
 {
     uint64_t r = mix64(mix64(seed ^ (stream * 0xD6E8FEB86659FD93ULL)) + idx);
@@ -1071,6 +1066,68 @@ hipError_t argmax_rows(hipStream_t st, const float* logits, int32_t* pred, int n
 {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(argmax_rows_kernel, dim3(min(n, 4096)), dim3(256), 0, st, logits, pred, n, V);
+    return hipGetLastError();
+}
+
+// one sampled token per row of materialised logits (the launch-per-token form of avae_decode_sample, contract in
+// include/argsim_vae.h): kept set = logits >= the k-th largest (radix select, ties kept), token = first maximum of
+// l inv_t + Gumbel noise over it (no noise: of l), logp = log-softmax of l inv_t over it.  One workgroup per row; the
+// row is re-read per pass (32 KB at V = 8192: cache hits).  A NaN logit is treated as absent; a row with no number
+// above -inf gives token 0 and logp NaN.  lead (optional): the ids fed at this step -- with t > 0 a row fed eos is
+// finished: token eos, logp 0.
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ logits, int n, int V, int t, SampleParams sp,
+                                                          const int32_t* __restrict__ lead, int eos,
+                                                          int32_t* __restrict__ pred, float* __restrict__ logp)
+{
+    __shared__ unsigned s_sel[258];
+    __shared__ float s_f[4][4]; __shared__ int s_i[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t key = sample_key(sp.seed);
+    for (int row = blockIdx.x; row < n; row += gridDim.x) {
+        if (lead && t > 0 && lead[row] == eos) {                  // (uniform over the workgroup)
+            if (tid == 0) { pred[row] = eos; if (logp) logp[row] = 0.f; }
+            continue;
+        }
+        const float* x = logits + (size_t)row * V;
+        unsigned thr = 0;                                         // keep everything (NaN: see below)
+        if (sp.top_k > 0 && sp.top_k < V)
+            thr = kth_largest_key([&](auto f) { for (int c = tid; c < V; c += 256) f(order_key(x[c])); }, (unsigned)sp.top_k, s_sel);
+        const uint64_t base = sample_base(row, t);
+        float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
+        for (int c = tid; c < V; c += 256) {
+            const float l = x[c];
+            if (l != l || order_key(l) < thr) continue;
+            const float xs = l * sp.inv_t;
+            const float sc = sp.noise ? xs + gumbel(key, base, c) : l;
+            if (sc > best) { best = sc; besti = c; bx = xs; }      // ascending c: the first maximum stays
+            lse_add(m, s, xs);
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
+            lse_merge(m, s, om, os);
+        }
+        __syncthreads();
+        if (lane == 0) { s_f[wave][0] = best; s_f[wave][1] = bx; s_f[wave][2] = m; s_f[wave][3] = s; s_i[wave] = besti; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w) {
+                if (cand_better(s_f[w][0], s_i[w], best, besti)) { best = s_f[w][0]; besti = s_i[w]; bx = s_f[w][1]; }
+                lse_merge(m, s, s_f[w][2], s_f[w][3]);
+            }
+            const bool none = besti == 0x7fffffff;
+            pred[row] = none ? 0 : besti;
+            if (logp) logp[row] = none ? __int_as_float(0x7fc00000) : lse_logp(bx, m, s);
+        }
+    }
+}
+hipError_t sample_rows(hipStream_t st, const float* logits, int n, int V, int t, const SampleParams& sp, const int32_t* lead, int eos,
+                       int32_t* pred, float* logp)
+{
+    if (n <= 0) return hipSuccess;
+    if (V < 1 || V > (1 << 20) || t < 0 || t >= (1 << 20) || sp.top_k < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(min(n, 4096)), dim3(256), 0, st, logits, n, V, t, sp, lead, eos, pred, logp);
     return hipGetLastError();
 }
 

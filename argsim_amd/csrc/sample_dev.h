@@ -1,0 +1,97 @@
+// sample_dev.h -- device helpers shared by the two samplers (decode.hip: the persistent launch; ops.hip: sample_rows):
+// the counter RNG's mixer, the Gumbel noise of stream 3, order-preserving keys with a workgroup radix select of the
+// k-th largest, and the running (max, sum exp) pair of a log-sum-exp.  The contract is in include/argsim_vae.h
+// (avae_decode_sample); both samplers and the float64 reference of tests/sampling_ref.py implement exactly it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace avae {
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ULL;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    return x ^ (x >> 31);
+}
+
+// stream 3 of the generator (1: word dropout, 2: epsilon).  key = sample_key(seed) once per call / thread;
+// index = ((row << 20) + step) << 20 + v: a row's draws depend on neither the batch size nor the step cap.
+__device__ __forceinline__ uint64_t sample_key(uint64_t seed) { return mix64(seed ^ (3ULL * 0xD6E8FEB86659FD93ULL)); }
+__device__ __forceinline__ uint64_t sample_base(int row, int step) { return (((uint64_t)(unsigned)row << 20) + (uint64_t)(unsigned)step) << 20; }
+// g = -log(-log u), u = (23 random bits + 0.5) 2^-23: exact in fp32 and strictly inside (0, 1), so g is finite (the
+// 24-bit form of uniform01 rounds to 1.0 for its top values: k + 0.5 is no fp32 number above 2^23)
+__device__ __forceinline__ float gumbel(uint64_t key, uint64_t base, int v)
+{
+    const uint64_t x = mix64(key + base + (uint64_t)(unsigned)v);
+    const float u = ((float)(unsigned)(x >> 41) + 0.5f) * (1.0f / 8388608.0f);
+    return -logf(-logf(u));
+}
+
+// fp32 -> uint key with the same order (larger float, larger key; -0 and +0 share one key, as they compare equal); a NaN
+// gets key 0, below -inf: it is never kept before a number and never selected
+__device__ __forceinline__ unsigned order_key(float x)
+{
+    if (x != x) return 0u;
+    if (x == 0.f) x = 0.f;
+    const unsigned u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// the k-th largest key (1 <= k <= number of keys) over the whole workgroup by a radix select, 4 passes of 8 bits from
+// the top: a 256-bin histogram in LDS of the keys that match the prefix found so far, then the bin in which the count
+// from the top reaches k.  each(f) calls f(key) for every key of THIS thread; sh: 258 words of LDS.  Every thread of
+// the workgroup must call it (barriers inside); all return the same key.
+template <class Each>
+__device__ __forceinline__ unsigned kth_largest_key(Each each, unsigned k, unsigned* sh)
+{
+    const int tid = threadIdx.x, nth = blockDim.x;
+    unsigned prefix = 0, mask = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int i = tid; i < 256; i += nth) sh[i] = 0;
+        __syncthreads();
+        each([&](unsigned key) { if ((key & mask) == prefix) atomicAdd(&sh[(key >> shift) & 255u], 1u); });
+        __syncthreads();
+        if (tid < 64) {                         // lane i owns bins 4 i .. 4 i + 3; suffix sums run from the top bin down
+            const unsigned c0 = sh[4 * tid], c1 = sh[4 * tid + 1], c2 = sh[4 * tid + 2], c3 = sh[4 * tid + 3];
+            unsigned suf = c0 + c1 + c2 + c3;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned v = __shfl_down(suf, o, 64); if (tid + o < 64) suf += v; }
+            unsigned above = suf - (c0 + c1 + c2 + c3);       // keys in bins above this lane's
+            if (above < k && k <= suf) {                       // exactly one lane: the count crosses k inside its bins
+                int bin = 4 * tid + 3;
+                if (above + c3 < k) { above += c3; bin = 4 * tid + 2;
+                    if (above + c2 < k) { above += c2; bin = 4 * tid + 1;
+                        if (above + c1 < k) { above += c1; bin = 4 * tid; } } }
+                sh[256] = (unsigned)bin; sh[257] = k - above;
+            }
+        }
+        __syncthreads();
+        prefix |= sh[256] << shift; mask |= 255u << shift; k = sh[257];
+    }
+    return prefix;
+}
+
+// running log-sum-exp as (m, s): sum = s exp(m).  Equal values add 1 without an exponential, so a +inf logit gives
+// (inf, count) and not NaN; a NaN x is skipped by the caller.
+__device__ __forceinline__ void lse_add(float& m, float& s, float x)
+{
+    if (x == m) s += 1.f;
+    else if (x > m) { s = s * expf(m - x) + 1.f; m = x; }       // m = -inf at the start: s = 0 * 0 + 1
+    else s += expf(x - m);
+}
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2)
+{
+    if (s2 == 0.f) return;
+    if (s == 0.f) { m = m2; s = s2; return; }
+    if (m2 == m) s += s2;
+    else if (m2 > m) { s = s * expf(m - m2) + s2; m = m2; }
+    else s += s2 * expf(m2 - m);
+}
+// log-softmax value of x under (m, s)
+__device__ __forceinline__ float lse_logp(float x, float m, float s) { return (x == m ? 0.f : x - m) - logf(s); }
+
+// candidate (score, id) merge: larger score, then smaller id (the first maximum)
+__device__ __forceinline__ bool cand_better(float sc, int id, float best, int besti) { return sc > best || (sc == best && id < besti); }
+
+}  // namespace avae

@@ -36,6 +36,10 @@ class AvaeConfig(C.Structure):
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int64, C.c_int64)
 
+class AvaeSampleConfig(C.Structure):
+    _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -64,6 +68,7 @@ SIGNATURES = {
     'avae_decode_init': (C.c_int, [_P, _P, C.c_int32, _P]),
     'avae_decode_step': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     'avae_decode_greedy': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    'avae_decode_sample': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSampleConfig), _P, _P, C.POINTER(C.c_int32)]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),
@@ -72,6 +77,7 @@ SIGNATURES = {
     'avae_debug_gemm_tn16': (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float]),
     'avae_debug_softmax_ce': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.POINTER(C.c_int)]),
     'avae_debug_argmax_rows': (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    'avae_debug_sample_rows': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AvaeSampleConfig), _P, _P]),
     'avae_timing_collect': (C.c_int, [_P, C.POINTER(C.c_double)]),
     'avae_debug_timing': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),
     'avae_debug_train_ce': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),

@@ -10,6 +10,7 @@ The reference's feed -> fetch pairs map to methods:
     (errt_samp, loss_gen_samp, loss_kld_samp)          -> VAE.eval(src, tgt)
     model.z.eval({model.src: x})  / encode(sess,vae,x) -> VAE.encode(x) / encode(vae, x)
     decode(sess, vae, z, steps)                        -> VAE.decode(z, steps) / decode(vae, z, steps)
+    (new) sampled decoding                             -> VAE.sample(z, ...) / VAE.generate(n, ...) / sample(vae, z, ...)
 """
 import ctypes as C
 
@@ -321,6 +322,49 @@ class VAE:
         return out[:, :n.value].cpu().numpy()
 
 
+    def sample(self, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
+        """sampled decoding (include/argsim_vae.h, avae_decode_sample): array i32 (b, t<=steps) drawn from softmax(logits / temperature)
+        over the top_k most likely pieces (0: all), reproducible from seed; a row is eos from its first eos on.  temperature 0 or
+        top_k 1 is the argmax.  With return_logp also f32 (b, min(t + 1, steps)): the log-probability of every token, the closing eos
+        included (column t for the longest rows), 0 behind it -- a row's sum is the log-probability of its sentence."""
+        steps, top_k, seed = _check_sample_args(steps, temperature, top_k, seed)
+        z = torch.as_tensor(np.ascontiguousarray(z, dtype=np.float32)).to(self.device)
+        if z.dim() != 2 or z.shape[1] != self.cfg['dim_rep'] or z.shape[0] < 1:
+            raise ValueError("z must be (b, dim_rep) with b >= 1, got %s" % (tuple(z.shape),))
+        b = z.shape[0]
+        out = torch.empty((b, steps), dtype=torch.int32, device=self.device)
+        logp = torch.empty((b, steps), dtype=torch.float32, device=self.device) if return_logp else None
+        n = C.c_int32()
+        sc = _lib.AvaeSampleConfig(float(temperature), top_k, seed)
+        self._stream()
+        self._ck(self._l.avae_decode_sample(self._h, C.c_void_p(z.data_ptr()), b, steps, C.byref(sc), C.c_void_p(out.data_ptr()),
+                                            C.c_void_p(logp.data_ptr()) if return_logp else None, C.byref(n)))
+        ids = out[:, :n.value].cpu().numpy()
+        return (ids, logp[:, :min(n.value + 1, steps)].cpu().numpy()) if return_logp else ids
+
+    def generate(self, n, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
+        """n sentences from the prior: z ~ N(0, I) drawn on the host with np.random.default_rng(seed), then sample() with the same seed"""
+        if int(n) != n or n < 1:
+            raise ValueError("n must be an integer >= 1, got %r" % (n,))
+        _check_sample_args(steps, temperature, top_k, seed)
+        z = np.random.default_rng(seed).standard_normal((int(n), self.cfg['dim_rep'])).astype(np.float32)
+        return self.sample(z, steps, temperature, top_k, seed, return_logp)
+
+
+def _check_sample_args(steps, temperature, top_k, seed):
+    """the argument rules of avae_decode_sample, checked before anything touches the device -> (steps, top_k, seed) as ints"""
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= steps <= 1 << 20:
+        raise ValueError("steps must be an integer in [1, 2^20], got %r" % (steps,))
+    t = float(temperature)
+    if not (t >= 0.0) or t == float('inf'):
+        raise ValueError("temperature must be a finite number >= 0, got %r" % (temperature,))
+    if isinstance(top_k, bool) or int(top_k) != top_k or not 0 <= top_k < 1 << 31:
+        raise ValueError("top_k must be an integer >= 0, got %r" % (top_k,))
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be an integer in [0, 2^64), got %r" % (seed,))
+    return int(steps), int(top_k), int(seed)
+
+
 def vAe(mode, src=None, tgt=None, **cfg):
     """reference-shaped constructor (src/model.py:48): returns the VAE object in place of the Record.
     ``src``/``tgt`` pipeline tensors have no counterpart: batches are passed to the methods."""
@@ -335,3 +379,8 @@ def encode(vae, src):
 def decode(vae, z, steps=256):
     """src/model.py:204-219 without the session argument"""
     return vae.decode(z, steps)
+
+
+def sample(vae, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
+    """sampled counterpart of decode(): VAE.sample"""
+    return vae.sample(z, steps, temperature, top_k, seed, return_logp)

@@ -142,6 +142,33 @@ int  avae_decode_step(avae_handle h, const int32_t* lead, const float* state_in,
 int  avae_decode_greedy(avae_handle h, const float* z, int32_t b, int32_t steps,
                         int32_t* out_ids, int32_t* n_steps);
 
+
+/* ---- sampled decoding ------------------------------------------------------------------ */
+/* Draw sentences from the decoder: temperature and top-k, on the device, reproducible from a seed.
+ * For batch row r, step t (0-based) and vocabulary id v, with l[v] the tied logits of src/model.py:166:
+ *   noise   u = ((x >> 41) + 0.5) 2^-23,  x = mix64(mix64(seed ^ (3 * 0xD6E8FEB86659FD93)) + idx),
+ *           idx = ((r 2^20) + t) 2^20 + v  (stream 3 of the library's counter generator; mix64 is splitmix64's
+ *           finaliser);  g = -log(-log u) in fp32 (logf).  u is exact in fp32 and strictly inside (0, 1).  idx holds
+ *           neither b nor steps: a row's draws do not depend on the rows after it or on the step cap.
+ *           dim_tgt > 2^20 or steps > 2^20 is refused.
+ *   top-k   0 < top_k < V keeps {v : l[v] >= the top_k-th largest l}, ties at the threshold all kept;
+ *           top_k = 0 or >= V keeps everything.
+ *   token   the first maximum over the kept set of l[v] / temperature + g[v] (Gumbel-max: a draw from
+ *           softmax(l / temperature) over the kept set).  temperature == 0 or top_k == 1: no noise, the first
+ *           maximum of l.  A negative or non-finite temperature or a negative top_k is an error.
+ *   logp    the log-softmax of l / temperature over the kept set at the token; at temperature 0 the log-softmax
+ *           of l over all of V.
+ *   rows    a row that has emitted eos is finished: every later token is eos with logp 0.  (The greedy loop keeps
+ *           feeding such rows, as the reference does.)  The loop ends after the first step at which every row is
+ *           finished, or at `steps`.
+ * out_ids (b, steps) int32 device, eos-padded; logp_out optional (b, steps) float device: [r, j] belongs to
+ * out_ids[r, j] up to and including the row's first eos (column *n_steps is the closing eos of the longest rows when
+ * *n_steps < steps), 0 after it; *n_steps (host) = length of the longest row without its eos, as avae_decode_greedy.
+ * One persistent launch up to 32 rows (top_k > 0: dim_tgt <= 8192), else one launch sequence per token.             */
+typedef struct avae_sample_config { float temperature; int32_t top_k; uint64_t seed; } avae_sample_config;
+int  avae_decode_sample(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_config* sc,
+                        int32_t* out_ids, float* logp_out, int32_t* n_steps);
+
 #ifdef __cplusplus
 }
 #endif

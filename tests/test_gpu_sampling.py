@@ -1,0 +1,306 @@
+"""sampled decoding on the device (avae_decode_sample, avae_debug_sample_rows) against the float64 reference of tests/sampling_ref.py.
+
+The reference REPLAYS the device's tokens, so every position is judged on the device's own history.  Parameters: make_case('tiny'),
+make_case('mid') and the production geometry (V 8192, D 512, L 3), each with decode/out/kernel and decode/out/bias scaled so that the
+first step's max |logit| is 8 (random initialisation gives |logit| < 1: an almost flat distribution whose top-k boundary alone is
+closer than 1e-3 on 9 % of positions).
+
+TOL.  Not chosen in advance: it is 4 x the largest |device logp - reference logp| at the device's own tokens over every case of
+ALL below (two competing scores each carry the error; logp sees one token plus a normaliser).  Measured on MI355X: 6.995e-06
+(production geometry, b = 32 and 40, per-token path, T 0.7), so MAX_DLOGP = 7.0e-6 and TOL = 2.8e-5; the figure is printed again by
+test_tol_is_four_times_the_measured_logp_error, which fails if a run measures more than TOL / 4 or if TOL > 1e-3.  With this TOL the
+most undecidable case has 2 of 640 emitted positions (0.3 %; production, b = 32, T 0.7, top_k 40: a top-k boundary gap of 7.9e-6)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import sampling_ref as sr
+from helpers import make_case
+from oracle import vae_numpy as vn
+
+pytestmark = pytest.mark.gpu
+
+MAX_DLOGP = 7.0e-6          # measured: 6.995e-06 (production geometry, b = 32 and 40, per-token path, T 0.7)
+TOL = 4 * MAX_DLOGP
+KEYS = ('dim_tgt', 'dim_emb', 'dim_rep', 'rnn_layers', 'accelerate', 'learn_rate', 'bos', 'eos')
+CONFIGS = [(1.0, 0), (0.7, 0), (1.3, 0), (1.0, 8), (0.7, 40)]
+# (geometry, rows, persistent): tiny and mid at their own batch, production b = 1 / 5 / 32 on both paths and b = 40 (always per token)
+GEOMS = [('tiny', 4, 1), ('tiny', 4, 0), ('mid', 8, 1), ('mid', 8, 0),
+         ('prod', 1, 1), ('prod', 5, 1), ('prod', 32, 1), ('prod', 1, 0), ('prod', 5, 0), ('prod', 32, 0), ('prod', 40, 0)]
+STEPS = {'tiny': 40, 'mid': 40, 'prod': 20}
+_MODELS, _RUNS = {}, {}
+
+
+def _first_logits(P, cfg, z):
+    D, L = cfg['dim_emb'], cfg['rnn_layers']
+    E = P['embed/embedding']
+    h0 = np.asarray(z, np.float64) @ P['latent/ex/kernel'] + P['latent/ex/bias']
+    hd, _ = vn.decoder_rnn(P, cfg, E[np.full((1, len(z)), cfg['bos'], np.int32)], np.stack([h0] * L))
+    hd = hd.reshape(-1, D) @ P['decode/out/kernel'] + P['decode/out/bias']
+    return hd @ ((D ** -0.5) * E.T)
+
+
+def _model(name, eos_lean=0.0):
+    """(VAE, cfg, P, z (40, R)) of a geometry, parameters scaled to max |logit| = 8 at the first step; eos_lean adds that much of the
+    unit eos embedding to the out bias (rows end early)"""
+    key = (name, eos_lean)
+    if key not in _MODELS:
+        from argsim_amd.model import VAE
+        if name == 'prod':
+            cfg = vn.make_cfg(dim_tgt=8192, dim_emb=512, dim_rep=128, rnn_layers=3)
+            P = {k: v.astype(np.float32).astype(np.float64) for k, v in vn.init_params(cfg, 4, bias_scale=0.1).items()}
+        else:
+            cfg, P = make_case(name)[:2]
+        z = np.random.default_rng(11).standard_normal((40, cfg['dim_rep'])).astype(np.float32)
+        f = 8.0 / float(np.abs(_first_logits(P, cfg, z)).max())
+        for k in ('decode/out/kernel', 'decode/out/bias'):
+            P[k] = (P[k] * f).astype(np.float32).astype(np.float64)
+        if eos_lean:
+            e = P['embed/embedding'][cfg['eos']]
+            P['decode/out/bias'] = (P['decode/out/bias'] + eos_lean * np.sqrt(cfg['dim_emb']) * e / (e @ e)).astype(np.float32).astype(np.float64)
+        m = VAE('infer', init=False, **{k: cfg[k] for k in KEYS})
+        m.set_params(P)
+        _MODELS[key] = (m, cfg, P, z)
+    return _MODELS[key]
+
+
+def _run(name, b, persistent, T, k, seed=1):
+    """device run + replay of one case -> dict (cached: the tolerance test and the token test share the runs)"""
+    key = (name, b, persistent, T, k, seed)
+    if key not in _RUNS:
+        m, cfg, P, z = _model(name)
+        m.set_option('persistent', persistent)
+        ids, logp = m.sample(z[:b], steps=STEPS[name], temperature=T, top_k=k, seed=seed, return_logp=True)
+        m.set_option('persistent', 1)
+        ref = sr.sample(P, cfg, z[:b], STEPS[name], T, k, seed, replay=ids)
+        assert logp.shape == ref['live'].shape and ref['n_steps'] == ids.shape[1], (logp.shape, ref['live'].shape, ref['n_steps'], ids.shape)
+        same_set = ref['live'] & (ref['gap'] > 1e-3)        # (the ceiling of TOL: the measurement must not depend on TOL)
+        dl = float(np.abs(logp - ref['logp_dev'])[same_set].max())
+        _RUNS[key] = dict(ids=ids, logp=logp, ref=ref, dlogp=dl, cfg=cfg)
+    return _RUNS[key]
+
+
+ALL = [(g, T, k) for g in GEOMS for (T, k) in CONFIGS if not (g[0] == 'tiny' and k == 40)]       # tiny: V = 32 < 40 keeps everything
+
+
+def test_tol_is_four_times_the_measured_logp_error():
+    """max |device logp - reference logp| at the device's own tokens over all cases (positions whose top-k boundary is further than
+    1e-3 from a tie: elsewhere the two kept sets may differ by a whole term).  TOL = 4 x MAX_DLOGP must cover it and be <= 1e-3."""
+    worst = {}
+    for g, T, k in ALL:
+        r = _run(*g, T, k)
+        worst[(g, T, k)] = r['dlogp']
+    top = sorted(worst.items(), key=lambda kv: -kv[1])[:5]
+    mx = top[0][1]
+    print("max |dlogp| over %d cases: %.3e (TOL / 4 = %.3e); worst cases: %s" % (len(worst), mx, TOL / 4, top))
+    assert TOL <= 1e-3
+    assert mx <= TOL / 4, top
+
+
+@pytest.mark.parametrize("g,T,k", ALL, ids=lambda v: str(v).replace(' ', ''))
+def test_device_tokens_and_logp_equal_the_float64_reference(g, T, k):
+    """decidable position (top-2 score margin > TOL and, with top-k, boundary gap > TOL): the device token IS the reference's.
+    Elsewhere it scores within TOL of the reference's best and its logit is within TOL T of the kept set.  At most 2 % of the emitted
+    positions may be undecidable.  logp within TOL where the kept sets must agree (gap > TOL); finished rows: eos, logp 0."""
+    r = _run(*g, T, k)
+    ref, ids, logp, eos = r['ref'], r['ids'], r['logp'], r['cfg']['eos']
+    live = ref['live']
+    dec = live & (ref['margin'] > TOL) & (ref['gap'] > TOL)
+    und = live & ~dec
+    print("%s T %.1f k %d: %d emitted, %d undecidable, min margin %.2e, min gap %.2e, max dlogp %.2e" %
+          (g, T, k, live.sum(), und.sum(), ref['margin'][live].min(), ref['gap'][live].min(), r['dlogp']))
+    assert live.sum() >= ids.shape[0]
+    assert np.array_equal(ref['dev'][dec], ref['token'][dec]), np.argwhere(dec & (ref['dev'] != ref['token']))[:5]
+    assert (ref['deficit'][und] <= TOL).all() and (ref['below'][und] <= TOL * T).all()
+    assert und.sum() <= 0.02 * live.sum(), (und.sum(), live.sum())
+    chk = live & (ref['gap'] > TOL)
+    assert np.abs(logp - ref['logp_dev'])[chk].max() <= TOL
+    assert (logp[~live] == 0.0).all() and (ref['dev'][~live] == eos).all()
+    padded = np.full(live.shape, eos, np.int32)
+    padded[:, :ids.shape[1]] = ids
+    assert (padded[~live] == eos).all()
+
+
+def _upto_first_eos(a, eos, steps):
+    """rows of (b, n) padded with eos to steps + 1 columns, and every row's length including its first eos"""
+    p = np.full((a.shape[0], steps + 1), eos, np.int32)
+    p[:, :a.shape[1]] = a
+    return p, (p == eos).argmax(1) + 1
+
+
+@pytest.mark.parametrize("name,b", [('mid', 8), ('prod', 5), ('prod', 32), ('prod', 40)])
+@pytest.mark.parametrize("persistent", [1, 0])
+def test_temperature_0_and_top_k_1_are_the_greedy_ids(name, b, persistent):
+    """bit-equal to avae_decode_greedy on every row up to and including its first eos, on both paths (the greedy loop goes on
+    feeding a finished row, the sampled one does not: beyond a row's eos they differ on purpose)"""
+    for lean in (0.0, 6.0):
+        m, cfg, P, z = _model(name, lean)
+        m.set_option('persistent', persistent)
+        want, nw = _upto_first_eos(m.decode(z[:b], steps=24), cfg['eos'], 24)
+        for kw in (dict(temperature=0.0), dict(temperature=0.0, top_k=5), dict(temperature=0.7, top_k=1)):
+            ids, logp = m.sample(z[:b], steps=24, seed=3, return_logp=True, **kw)
+            got, ng = _upto_first_eos(ids, cfg['eos'], 24)
+            assert np.array_equal(ng, nw), (lean, kw)
+            for r in range(b):
+                assert np.array_equal(got[r, :ng[r]], want[r, :ng[r]]), (lean, kw, r)
+            if 'top_k' in kw and kw['top_k'] == 1 and kw['temperature'] > 0:
+                assert (logp == 0.0).all()           # one kept logit
+            else:
+                assert (logp <= 0.0).all() and (logp[:, 0] < 0.0).all()
+        m.set_option('persistent', 1)
+
+
+@pytest.mark.parametrize("persistent", [1, 0])
+def test_same_seed_same_bits_and_rows_and_step_caps_are_independent(persistent):
+    m, cfg, P, z = _model('prod')
+    m.set_option('persistent', persistent)
+    kw = dict(temperature=1.0, top_k=40)
+    a, la = m.sample(z[:32], steps=40, seed=7, return_logp=True, **kw)
+    b_, lb = m.sample(z[:32], steps=40, seed=7, return_logp=True, **kw)
+    assert np.array_equal(a, b_) and np.array_equal(la.view(np.int32), lb.view(np.int32))
+    c = m.sample(z[:32], steps=40, seed=8, **kw)
+    assert c.shape != a.shape or not np.array_equal(a, c)
+    # steps = 20 is a prefix of steps = 40
+    s20, l20 = m.sample(z[:32], steps=20, seed=7, return_logp=True, **kw)
+    assert np.array_equal(s20, a[:, :20]) and np.array_equal(l20.view(np.int32), la[:, :20].view(np.int32))
+    # row r of 32 = row r of the batch cut to r + 1 rows
+    for r in (0, 4, 16, 31):
+        one, l1 = m.sample(z[:r + 1], steps=40, seed=7, return_logp=True, **kw)
+        n = min(one.shape[1], a.shape[1])
+        if persistent:           # one wave per row in an order that does not depend on b: the same bits
+            assert np.array_equal(one[r, :n], a[r, :n]) and np.array_equal(l1[r, :n].view(np.int32), la[r, :n].view(np.int32)), r
+            assert (one[r, n:] == cfg['eos']).all() and (a[r, n:] == cfg['eos']).all()
+        else:                    # the GEMM tiling may change with b: equal on decidable positions up to the first difference
+            ref = sr.sample(P, cfg, z[:r + 1], 40, seed=7, T=1.0, top_k=40, replay=one)
+            for t in range(n):
+                if one[r, t] != a[r, t]:
+                    assert not (ref['margin'][r, t] > TOL and ref['gap'][r, t] > TOL), (r, t)
+                    break
+    m.set_option('persistent', 1)
+
+
+@pytest.mark.parametrize("persistent", [1, 0])
+def test_finished_rows_stay_eos_with_logp_0(persistent):
+    # eos wins at once in every row: nothing is kept (the bias of test_persistent_greedy_decode_equals_the_per_token_loop)
+    from argsim_amd.model import VAE
+    m = VAE('infer', seed=2, dim_tgt=8192, dim_emb=512, dim_rep=128, rnn_layers=3)
+    z = np.random.default_rng(5).standard_normal((5, 128)).astype(np.float32)
+    E = m.get_tensor('embed/embedding')
+    m.set_tensor('decode/out/bias', m.get_tensor('decode/out/bias') + 200.0 * E[1] / np.linalg.norm(E[1]))
+    m.set_option('persistent', persistent)
+    for k in (0, 40):
+        ids, logp = m.sample(z, steps=40, temperature=1.0, top_k=k, seed=1, return_logp=True)
+        assert ids.shape == (5, 0) and logp.shape == (5, 1) and (np.abs(logp) < 1e-6).all()
+    m.close()
+    # a mixed batch: rows end at different steps
+    m, cfg, P, z = _model('mid', 3.0)
+    m.set_option('persistent', persistent)
+    ids, logp = m.sample(z[:8], steps=40, temperature=1.0, top_k=0, seed=2, return_logp=True)
+    m.set_option('persistent', 1)
+    eos = cfg['eos']
+    p, n = _upto_first_eos(ids, eos, 40)
+    assert len(set(n.tolist())) > 1, n                      # really mixed
+    assert ids.shape[1] == min(n.max() - 1, 40)             # n_steps = the longest row without its eos
+    for r in range(8):
+        assert (p[r, n[r] - 1:] == eos).all()
+        assert (logp[r, :min(n[r], logp.shape[1])] < 0.0).all() and (logp[r, n[r]:] == 0.0).all()
+
+
+def _rows(m, x, t0, T, k, seed, want_logp=True):
+    import torch
+    xd = torch.as_tensor(x, dtype=torch.float32).to(m.device).contiguous()
+    n, V = xd.shape
+    pred = torch.full((n,), -7, dtype=torch.int32, device=m.device)
+    logp = torch.full((n,), 7.0, dtype=torch.float32, device=m.device)
+    sc = m._l.avae_debug_sample_rows.argtypes[5]._type_(float(T), int(k), int(seed))
+    rc = m._l.avae_debug_sample_rows(m._h, C.c_void_p(xd.data_ptr()), n, V, t0, C.byref(sc), C.c_void_p(pred.data_ptr()),
+                                     C.c_void_p(logp.data_ptr()) if want_logp else None)
+    torch.cuda.synchronize()
+    return rc, pred.cpu().numpy(), logp.cpu().numpy()
+
+
+@pytest.mark.parametrize("V", [4, 31, 256, 8192, 8196])
+def test_row_kernel_alone(V):
+    """sample_rows on caller logits: every top_k edge, ties at the k-th logit (all kept), at two temperatures; 6 rows at step 9"""
+    m = _model('tiny')[0]
+    rng = np.random.default_rng(V)
+    x = (3.0 * rng.standard_normal((6, V))).astype(np.float32)
+    x[1] = np.round(x[1])                                   # many ties, at the threshold too
+    x[2, :] = x[2, 0]                                       # all equal
+    x[3, :2] = (0.0, -0.0)                                  # the two zeros compare equal: one key
+    x[3, 2:] = -np.abs(x[3, 2:]) - 0.5
+    und = tot = 0
+    for k in sorted({0, 1, 2, V - 1, V, V + 5}):
+        for T in (1.0, 0.6, 0.0):
+            rc, pred, logp = _rows(m, x, 9, T, k, seed=21)
+            assert rc == 0
+            for r in range(6):
+                p = sr.position(x[r].astype(np.float64), T, k, 21, r, 9)
+                tot += 1
+                assert p['kept'][pred[r]] or T == 0.0, (k, T, r)     # the input is exact: the kept set is too
+                if p['margin'] > TOL:
+                    assert pred[r] == p['token'], (k, T, r)
+                else:
+                    und += 1
+                    assert p['scores'][p['token']] - p['scores'][pred[r]] <= TOL, (k, T, r)
+                assert abs(logp[r] - p['logp'][pred[r]]) <= TOL, (k, T, r, logp[r], p['logp'][pred[r]])
+    # without noise a tie is decided by the first maximum, exactly
+    rc, pred, _ = _rows(m, x, 9, 0.0, 0, seed=1)
+    assert np.array_equal(pred, x.argmax(1))
+    rc, pred, _ = _rows(m, x, 9, 1.0, 1, seed=1, want_logp=False)
+    assert np.array_equal(pred, x.argmax(1))
+    print("V %d: %d of %d positions undecidable" % (V, und, tot))
+
+
+def test_row_kernel_infinities_and_nan():
+    """a +inf logit is chosen with logp 0; a NaN logit is treated as absent (never chosen before a number, not in the normaliser);
+    a row of NaN only gives token 0 and logp NaN (there is no number to choose)"""
+    m = _model('tiny')[0]
+    V = 300
+    rng = np.random.default_rng(0)
+    x = rng.standard_normal((4, V)).astype(np.float32)
+    x[0, 77] = np.inf
+    x[1, ::3] = np.nan
+    x[2, :] = np.nan
+    x[3, :] = np.nan
+    x[3, 299] = -2.0
+    for k in (0, 5, 250):
+        for T in (1.0, 0.0):
+            rc, pred, logp = _rows(m, x, 0, T, k, seed=4)
+            assert rc == 0
+            assert pred[0] == 77 and logp[0] == 0.0
+            clean = np.where(np.isnan(x[1]), -np.inf, x[1]).astype(np.float64)
+            p = sr.position(clean, T, k, 4, 1, 0)
+            assert not np.isnan(x[1, pred[1]])
+            assert pred[1] == p['token'] or p['margin'] <= TOL
+            assert abs(logp[1] - p['logp'][pred[1]]) <= TOL
+            assert pred[2] == 0 and np.isnan(logp[2])
+            assert pred[3] == 299 and logp[3] == 0.0
+
+
+def test_bad_arguments_are_errors_with_a_message_and_launch_nothing():
+    import torch
+    m, cfg, P, z = _model('mid')
+    zd = torch.as_tensor(z[:4]).to(m.device)
+    out = torch.full((4, 8), -5, dtype=torch.int32, device=m.device)
+    n = C.c_int32(-9)
+    mk = m._l.avae_decode_sample.argtypes[4]._type_
+    for T, k, steps in ((-1.0, 0, 8), (float('nan'), 0, 8), (float('inf'), 0, 8), (1.0, -2, 8), (1.0, 0, 0), (1.0, 0, -3)):
+        sc = mk(T, k, 0)
+        rc = m._l.avae_decode_sample(m._h, C.c_void_p(zd.data_ptr()), 4, steps, C.byref(sc), C.c_void_p(out.data_ptr()), None, C.byref(n))
+        assert rc != 0 and len(m._l.avae_last_error(m._h)) > 0, (T, k, steps)
+        torch.cuda.synchronize()
+        assert bool((out == -5).all()) and n.value == -9
+    assert m._l.avae_decode_sample(m._h, C.c_void_p(zd.data_ptr()), 4, 8, None, C.c_void_p(out.data_ptr()), None, C.byref(n)) != 0
+    rc, pred, logp = _rows(m, np.zeros((2, 8), np.float32), 0, -0.5, 0, 0)
+    assert rc != 0 and (pred == -7).all()
+    rc, pred, logp = _rows(m, np.zeros((2, 8), np.float32), 0, 1.0, -1, 0)
+    assert rc != 0 and (pred == -7).all()
+    with pytest.raises(ValueError):
+        m.sample(z[:4], temperature=-1.0)
+    # and the public calls work on the same handle afterwards
+    ids = m.generate(3, steps=12, temperature=0.9, top_k=8, seed=5)
+    assert ids.shape[0] == 3 and ids.shape[1] <= 12 and np.array_equal(ids, m.generate(3, steps=12, temperature=0.9, top_k=8, seed=5))
+    from argsim_amd import model
+    assert np.array_equal(model.sample(m, z[:3], steps=12, seed=5), m.sample(z[:3], steps=12, seed=5))
