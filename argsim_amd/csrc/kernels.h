@@ -254,6 +254,35 @@ struct AdamArgs { float* p; const float* g; float* m; float* v; int64_t n; float
                   const int* skip_if; };   // device word: non-zero -> the update is a no-op (GRU time-out flag)
 hipError_t adam_tf(hipStream_t st, const AdamArgs& a);
 
+// ---------------------------------------------------------------- importance-weighted likelihood (score.hip)
+// The k draws of B rows go through the decoder in batches: the rows r are cut into blocks of rc, and a block's draws lie behind
+// each other (draw-major), so the pair (kk, r) of the block at r0 (rcb = min(rc, B - r0) rows) is row r0 * k + kk * rcb + (r - r0)
+// of z and any run of whole draws of one block is one contiguous decoder batch whose row j carries the ids of row r0 + j % rcb.
+struct ScoreDraw {
+    const float* mu; const float* lv;   // (B, R)
+    const float* eps_in;                // optional (k, B, R): overrides stream 4 of the counter generator
+    float* eps_out;                     // optional (k, B, R)
+    float* z;                           // (k * B, R) in decoder-batch order (above)
+    float* lat;                         // (k, B): 1/2 sum_j (z^2 - eps^2 - lv)
+    int* err;                           // device word, set to 1 where an eps is not finite
+    int k, B, R, rc; uint64_t seed;
+};
+hipError_t score_draw(hipStream_t st, const ScoreDraw& a);
+// dst (n, S) row j = src (rc, S) row j % rc
+hipError_t tile_ids(hipStream_t st, int32_t* dst, const int32_t* src, int n, int rc, int S);
+// a decoder batch of n rows whose row j carries the ids of row j % rc: ids0 (T, rc) <- lead (T, n) of the first rc rows, tokrow (T, n) <- t * rc + j % rc
+hipError_t lead_rows(hipStream_t st, const int32_t* lead, int T, int n, int rc, int32_t* ids0, int32_t* tokrow);
+struct ScoreRows {
+    const float* loss;                  // per-token cross-entropy, compacted (prep_ids order)
+    const int32_t* rank;                // (T, n): compact row of (t, j) or -1
+    int T, n, rc, k0, r0, B;            // batch row j = draw k0 + j / rc of row r0 + j % rc
+    float* logpx;                       // (k, B) <- -sum_t loss
+    int32_t* ntok;                      // optional (B) <- positions summed (written by the rows of draw 0)
+};
+hipError_t score_rows(hipStream_t st, const ScoreRows& a);
+// logw (k, B, optional) = logpx - lat; bound (B) = logsumexp_k logw - log k, the maximum subtracted
+hipError_t score_bound(hipStream_t st, const float* logpx, const float* lat, int k, int B, float* logw, float* bound);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

@@ -55,6 +55,7 @@ struct avae_ctx {
     int gru_ablate = 0, gru_force_slow = 0, gru_stagger = 0, gru_item = 2;
     int skinny = 1;       // a few rows (latent block, one-step top layer; backward: remainder rows, small products): one 32x32 tile per workgroup,
                           // K split over its waves (gemm_f32.hip); 0: the tiled forms
+    int score_plan[4] = {0, 0, 0, 0};      // last avae_score / avae_score_z: decoder batch size N, rows rc and draws kc per batch, batches whose draws shared one first-layer projection through a row index
     const int* expect_ptr[3] = {nullptr, nullptr, nullptr}; int expect_val[3] = {0, 0, 0};      // (dyn_expected)
     int rows_form = 0;    // one-shot: the next gemm() call's rows are the batch rows -- skinny form whatever the batch size (see gemm)
     int compact = 2;      // encoder activations stored over the REAL rows only (row_map / GruArgs::rowmap): padded rows of a ragged batch cost nothing in the
@@ -313,11 +314,9 @@ void layout(avae_ctx* h, Bump& b, Ws& w, int B, int Ss, int St, bool train)
     }
 }
 
-int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train)
+// the one arena every call lays its buffers out in: grown (never shrunk) to `need` bytes
+int reserve_ws(avae_ctx* h, size_t need)
 {
-    Bump probe{nullptr};
-    layout(h, probe, w, B, Ss, St, train);
-    size_t need = probe.off + 4096;
     if (need > h->ws_cap) {
         AV_CHECK(hipStreamSynchronize(h->stream));
         if (h->ws) AV_CHECK(hipFree(h->ws));
@@ -328,6 +327,14 @@ int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train)
         AV_CHECK(hipMalloc(reinterpret_cast<void**>(&h->ws), cap));
         h->ws_cap = cap;
     }
+    return 0;
+}
+
+int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train)
+{
+    Bump probe{nullptr};
+    layout(h, probe, w, B, Ss, St, train);
+    AV_TRY(reserve_ws(h, probe.off + 4096));
     Bump real{h->ws};
     layout(h, real, w, B, Ss, St, train);
     return 0;
@@ -658,7 +665,8 @@ static void gru_common(avae_ctx* h, const Ws& w, GruArgs& a, int njobs, int S, i
 }
 // Row orders of this call (one launch, after prep_ids has the lengths): for every GRU launch shape of the step whose team
 // kernels can skip padding, the batch rows sorted by length and dealt over the workgroups.  with_dec: the decoder runs too.
-int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec)
+// with_enc = false: a call that runs the decoder alone (score_rows_dev).
+int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec, bool with_enc = true)
 {
     if (!h->skip_pad || !h->persistent || w.Bx % 16) return 0;
     if (w.Bx != B && !h->compact) return 0;                   // (phantom rows need the compact layout)
@@ -672,8 +680,8 @@ int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec)
         ord[n] = RowOrder{lens, add, p.T, p.cpj, w.ord_perm[k], w.ord_slens[k]};
         which[n++] = k; w.ord_T[k] = p.T; w.ord_cpj[k] = p.cpj;
     };
-    want(0, 2, Ss, 6 * D, 2 * D, w.lens_src, 0);          // (every layer but a one-step top layer carries both directions)
-    if (top_one_step(h)) want(1, 1, Ss, 6 * D, 2 * D, w.lens_src, 0);
+    if (with_enc) want(0, 2, Ss, 6 * D, 2 * D, w.lens_src, 0);          // (every layer but a one-step top layer carries both directions)
+    if (with_enc && top_one_step(h)) want(1, 1, Ss, 6 * D, 2 * D, w.lens_src, 0);
     if (with_dec) want(2, 1, T, 3 * D, D, w.lens_tgt, 1);
     if (!n) return 0;
     const bool hint = which[0] == 0 && h->compact == 2;        // (order 0 sorts the source rows: its step sum = the real source positions)
@@ -742,6 +750,22 @@ int build_compact(avae_ctx* h, Ws& w, int B, int Ss, int T, bool train)
     // the decoder stack the same way (training / evaluation calls: T > 1): a row's steps end one behind its last non-eos target id
     if (T < 2 || !use_table(h, T * B, B) || h->compact == 3) return 0;      // (3: the encoder alone, for measurements)
     if ((phantom && !w.ord_ok[2]) || !team(1, T, 3 * D, D, nullptr)) return 0;
+    AV_CHECK(row_map(h->stream, w.lens_tgt, 1, T, B, w.map_tgt, w.nact_tgt, w.ntgt));
+    w.compact_d = true;
+    return 0;
+}
+// The decoder half of build_compact for a call that runs the decoder alone (score_rows_dev): the same conditions, with the fill of the
+// TARGET rows unknown to the host -- the layout is taken where the batch needs it to reach the team kernels (phantom rows) and left alone
+// elsewhere (static row counts).
+int build_compact_dec(avae_ctx* h, Ws& w, int B, int T)
+{
+    w.compact = false; w.compact_d = false;
+    h->expect_ptr[0] = h->expect_ptr[1] = h->expect_ptr[2] = nullptr;
+    if (!h->compact || h->compact == 3 || !h->persistent || T < 2 || !use_table(h, T * B, B)) return 0;
+    if (w.Bx == B || !w.ord_ok[2]) return 0;
+    GruArgs q{};
+    gru_common(h, w, q, 1, T, B, 3 * h->cfg.dim_emb, h->cfg.dim_emb, nullptr, w.Bx);
+    if (!gru_plan(q, true, true).full()) return 0;
     AV_CHECK(row_map(h->stream, w.lens_tgt, 1, T, B, w.map_tgt, w.nact_tgt, w.ntgt));
     w.compact_d = true;
     return 0;
@@ -835,7 +859,10 @@ int run_latent(avae_ctx* h, Ws& w, int B, bool train, uint64_t seed, const float
 }
 
 // decoder GRU stack over T steps from per-layer initial states (state stride: layer * B * D; 0 = shared h0)
-int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int64_t state_stride, bool save, const int32_t* ids0 = nullptr, bool compact = false)
+// share_rows (T, B) with share_n: the first layer's input projection is taken over the share_n rows of w.emb_tgt only and read through
+// share_rows by the team kernels (rows of the batch that carry the same ids: score_rows_dev; the caller has checked the kernel form)
+int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int64_t state_stride, bool save, const int32_t* ids0 = nullptr, bool compact = false,
+                    const int32_t* share_rows = nullptr, int share_n = 0)
 {
     // compact layout (build_compact): the arrays between the GEMMs and the GRU launches hold the real rows only
     const int32_t* const cdyn = compact ? w.ntgt : nullptr;
@@ -852,6 +879,8 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
             AV_CHECK(id_groups_build(h->stream, ids0, rt, V, w.grp_tgt, save));
             AV_CHECK(rows_gather(h->stream, w.emb_tgt, h->P + h->oE, id_groups_uid(w.grp_tgt, rt, V), cnt, std::min(V, rt), D));
             AV_TRY(gemm(h, false, false, w.emb_tgt, D, h->P + p.W, D, w.ew, 3 * D, std::min(V, rt), 3 * D, D, 1.f, h->P + p.bW, 0, 0, cnt, 1));
+        } else if (i == 0 && share_rows) {
+            AV_TRY(gemm(h, false, false, x, D, h->P + p.W, D, w.d_gi[0], 3 * D, share_n, 3 * D, D, 1.f, h->P + p.bW));
         } else if (i > 0 && w.act_d[i - 1]) {
             AV_TRY(gemm_bf16_pre(h, w.d_hd16[i - 1], D, false, h->P + p.W, D, false, w.d_gi[i], 3 * D, rt, 3 * D, D, 1.f, 0, 1, cdyn, cdyn ? 1 : 0, h->P + p.bW));
         } else {
@@ -866,6 +895,7 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
         if (indirect) AV_CHECK(rank_rows(h->stream, w.tokrow_tgt, ids0, id_groups_rank(w.grp_tgt, rt, h->cfg.dim_tgt), rt, h->cfg.dim_tgt));
         else if (table0) AV_CHECK(rows_gather_ranked(h->stream, w.d_gi[0], w.ew, ids0, id_groups_rank(w.grp_tgt, rt, h->cfg.dim_tgt), rt, 3 * D, h->cfg.dim_tgt));
         j.gi = indirect ? w.ew : w.d_gi[i]; j.gi_rows = indirect ? w.tokrow_tgt : nullptr;
+        if (i == 0 && share_rows) j.gi_rows = share_rows;
         j.R = h->P + p.R; j.bR = h->P + p.bR;
         j.h0 = state_in + state_stride * i;
         j.hs = w.d_hd[i];
@@ -888,10 +918,12 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
     return 0;
 }
 
+int run_logits_ce(avae_ctx* h, Ws& w, int rt, bool train, float inv_n);
+
 int forward(avae_ctx* h, Ws& w, const int32_t* src, const int32_t* tgt, int B, int Ss, int St, bool train,
             uint64_t seed, const uint8_t* keep_mask, const float* eps, float inv_n)
 {
-    const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, R = h->cfg.dim_rep, L = h->cfg.rnn_layers;
+    const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, R = h->cfg.dim_rep;
     const int T = St + 1, rt = T * B;
     Sched sc = schedule(h);
     PrepArgs p{};
@@ -911,6 +943,17 @@ int forward(avae_ctx* h, Ws& w, const int32_t* src, const int32_t* tgt, int B, i
         AV_CHECK(embed_gather(h->stream, h->P + h->oE, w.lead, w.emb_tgt, rt, D, V));
         AV_TRY(run_decoder_rnn(h, w, B, T, w.h0, 0, train));
     }
+    AV_TRY(run_logits_ce(h, w, rt, train, inv_n));
+    float beta = h->cfg.kl_beta;
+    AV_CHECK(finalize_losses(h->stream, h->losses, w.loss_samp, w.ntok, rt, w.kld, B * R, h->cfg.free_bits, 1.f / ((float)B * R), sc.anneal * beta));
+    return 0;
+}
+
+// the kept positions of the top decoder layer -> out affine -> tied logits -> per-token softmax cross-entropy (w.loss_samp, w.errt_samp,
+// w.pred in the compact order of prep_ids; model.py:161-180)
+int run_logits_ce(avae_ctx* h, Ws& w, int rt, bool train, float inv_n)
+{
+    const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
     AV_CHECK(rows_gather(h->stream, w.hc, w.d_hd[L - 1], w.cidx, w.ntok, rt, D, w.compact_d ? w.map_tgt : nullptr));
     AV_TRY(gemm(h, false, true, w.hc, D, h->P + h->oKout, D, w.ho, D, rt, D, D, 1.f, h->P + h->oBout, 0, 0, w.ntok, 1));
     CeArgs c{};
@@ -930,8 +973,6 @@ int forward(avae_ctx* h, Ws& w, const int32_t* src, const int32_t* tgt, int B, i
     AV_TRY(gemm(h, false, false, w.ho, D, h->P + h->oE, D, w.logits, V, rt, V, D, 1.f / sqrtf((float)D), nullptr, 0, 0, w.ntok, 1));
     c.loss_samp = w.loss_samp; c.errt_samp = w.errt_samp; c.pred = w.pred; c.loss_acc = nullptr;      // (the scalar is summed from loss_samp in a fixed order: finalize_losses)
     AV_CHECK(softmax_ce(h->stream, c));
-    float beta = h->cfg.kl_beta;
-    AV_CHECK(finalize_losses(h->stream, h->losses, w.loss_samp, w.ntok, rt, w.kld, B * R, h->cfg.free_bits, 1.f / ((float)B * R), sc.anneal * beta));
     return 0;
 }
 
@@ -1282,6 +1323,130 @@ int check_gru_err(avae_ctx* h)
     return 0;
 }
 
+// -------------------------------------------------------------------------------- importance-weighted likelihood
+// (contract: include/argsim_vae.h, avae_score / avae_score_z; kernels: score.hip)
+constexpr int kScoreErrWord = 110;      // spare word of the error block: an eps that is not finite (score_draw)
+
+// Decoder batch size of the score path.  The k draws of B rows are k * B decoder rows; they run in batches of at most N rows, N the
+// largest count whose logits panel (N x (S_tgt + 1) x V floats) stays within what avae_eval sizes for the same batch (B rows) or 2^27
+// floats (the panel of the headline batch, 256 x 65 x 8192, is 1.02 x that), whichever is larger, and at most 256 rows, the headline
+// batch the GRU team kernels are tuned at.  A batch is rc rows under kc draws each (their first-layer projection is shared, run_decoder_rnn):
+// all k draws of N / k rows, or N draws of one row where k > N.
+struct ScorePlan { int N, rc, kc; };
+ScorePlan score_plan(const avae_ctx* h, int B, int k, int St)
+{
+    const size_t per_row = (size_t)(St + 1) * h->cfg.dim_tgt;
+    const size_t budget = std::max((size_t)B * per_row, (size_t)1 << 27);
+    size_t n = std::min<size_t>({(size_t)k * B, (size_t)256, budget / per_row});
+    ScorePlan p; p.N = (int)std::max<size_t>(n, 1);
+    if (k <= p.N) { p.kc = k; p.rc = std::min(B, p.N / k); }
+    else { p.kc = p.N; p.rc = 1; }
+    return p;
+}
+// buffers of a score call that outlive its decoder batches: behind the largest layout of the call, in the same arena
+struct ScoreWs { float *z, *lat, *logpx; int32_t *ntok, *tgt_rep, *ids0, *tokrow; };
+void score_layout(Bump& b, ScoreWs& s, int B, int k, int R, int N, int St)
+{
+    const size_t kb = (size_t)k * B, T = St + 1;
+    s.z = b.take<float>(kb * R); s.lat = b.take<float>(kb); s.logpx = b.take<float>(kb); s.ntok = b.take<int32_t>(B);
+    s.tgt_rep = b.take<int32_t>((size_t)N * St); s.ids0 = b.take<int32_t>((size_t)N * T); s.tokrow = b.take<int32_t>((size_t)N * T);
+}
+// one arena for the encoder pass over (B, Ss) (Ss = 0: none), every decoder batch of the plan and the buffers above
+int score_ws(avae_ctx* h, const ScorePlan& sp, int B, int k, int Ss, int St, ScoreWs& s)
+{
+    Ws w; size_t top = 0; std::vector<int> seen;
+    if (Ss > 0) { Bump b{nullptr}; layout(h, b, w, B, Ss, 1, false); top = b.off; }
+    for (int r0 = 0; r0 < B; r0 += sp.rc)
+        for (int k0 = 0; k0 < k; k0 += sp.kc) {
+            const int n = std::min(sp.rc, B - r0) * std::min(sp.kc, k - k0);
+            if (std::find(seen.begin(), seen.end(), n) != seen.end()) continue;
+            seen.push_back(n);
+            Bump b{nullptr}; layout(h, b, w, n, 1, St, false); top = std::max(top, b.off);
+        }
+    Bump probe{nullptr}; probe.off = top;
+    score_layout(probe, s, B, k, h->cfg.dim_rep, sp.N, St);
+    AV_TRY(reserve_ws(h, probe.off + 4096));
+    Bump real{h->ws}; real.off = top;
+    score_layout(real, s, B, k, h->cfg.dim_rep, sp.N, St);
+    return 0;
+}
+
+// encoder + latent affines over src (b, t): w.mu, w.lv
+int encode_ws(avae_ctx* h, Ws& w, const int32_t* src, int b, int t)
+{
+    PrepArgs p{};
+    p.src = src; p.tgt = src; p.B = b; p.Ss = t; p.St = 1; p.eos = h->cfg.eos; p.bos = h->cfg.bos;
+    p.src_tm = w.src_tm; p.lens_src = w.lens_src; p.lens_tgt = w.lens_tgt; p.lead = w.lead; p.gold = w.gold;
+    p.rank = w.rank; p.cidx = w.cidx; p.ntok = w.ntok; p.chunk_counts = w.ntok + 4;
+    // tgt is unused by the encoder; feed the first column of src as a 1-wide dummy target
+    AV_CHECK(prep_ids(h->stream, p));
+    AV_TRY(build_row_orders(h, w, b, t, 2, false));
+    AV_TRY(build_compact(h, w, b, t, 0, false));
+    AV_TRY(run_encoder(h, w, b, t, false));
+    AV_TRY(run_latent(h, w, b, false, 0, nullptr));
+    return 0;
+}
+
+// Teacher-forced log p(tgt row | z row) for the k draws of B rows, s.z in decoder-batch order (kernels.h ScoreDraw): s.logpx (k, B),
+// s.ntok (B).  Per decoder batch: the ids of its rows replicated over its draws on the device, prep (lead = [bos] + tgt, no word dropout,
+// mask, compaction), initial state from z, the decoder stack with ONE first-layer projection for the draws of a row (the per-id table
+// where the batch is table-fed, else the projection of the block's own rows read through a row index), logits, per-token CE, row sums.
+int score_rows_dev(avae_ctx* h, const ScorePlan& sp, const ScoreWs& s, const int32_t* tgt, int B, int k, int St)
+{
+    const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, R = h->cfg.dim_rep;
+    const int T = St + 1;
+    h->score_plan[0] = sp.N; h->score_plan[1] = sp.rc; h->score_plan[2] = sp.kc; h->score_plan[3] = 0;
+    for (int r0 = 0; r0 < B; r0 += sp.rc)
+        for (int k0 = 0; k0 < k; k0 += sp.kc) {
+            const int rc = std::min(sp.rc, B - r0), kc = std::min(sp.kc, k - k0), n = rc * kc, rt = T * n;
+            const float* z = s.z + ((size_t)r0 * k + (size_t)k0 * rc) * R;
+            Ws w;
+            Bump real{h->ws};
+            layout(h, real, w, n, 1, St, false);
+            const int32_t* ids = tgt + (size_t)r0 * St;
+            if (kc > 1) { AV_CHECK(tile_ids(h->stream, s.tgt_rep, ids, n, rc, St)); ids = s.tgt_rep; }
+            PrepArgs p{};
+            p.src = ids; p.tgt = ids; p.B = n; p.Ss = 1; p.St = St; p.eos = h->cfg.eos; p.bos = h->cfg.bos;      // (no source here: its first column stands in)
+            p.src_tm = w.src_tm; p.lens_src = w.lens_src; p.lens_tgt = w.lens_tgt; p.lead = w.lead; p.gold = w.gold;
+            p.rank = w.rank; p.cidx = w.cidx; p.ntok = w.ntok; p.chunk_counts = w.ntok + 4;
+            AV_CHECK(prep_ids(h->stream, p));
+            AV_TRY(build_row_orders(h, w, n, 1, T, true, false));
+            AV_TRY(build_compact_dec(h, w, n, T));
+            h->rows_form = 1;
+            AV_TRY(gemm(h, false, true, z, R, h->P + h->oWex, D, w.h0, D, n, D, R, 1.f, h->P + h->oBex));
+            if (use_table(h, rt, n)) AV_TRY(run_decoder_rnn(h, w, n, T, w.h0, 0, false, w.lead, w.compact_d));
+            else {
+                GruArgs q{};
+                gru_common(h, w, q, 1, T, n, 3 * D, D, nullptr, 0);
+                if (kc > 1 && gru_plan(q, true, h->persistent != 0).form == GruForm::team) {
+                    AV_CHECK(lead_rows(h->stream, w.lead, T, n, rc, s.ids0, s.tokrow));
+                    AV_CHECK(embed_gather(h->stream, h->P + h->oE, s.ids0, w.emb_tgt, T * rc, D, V));
+                    AV_TRY(run_decoder_rnn(h, w, n, T, w.h0, 0, false, nullptr, false, s.tokrow, T * rc));
+                    ++h->score_plan[3];
+                } else {
+                    AV_CHECK(embed_gather(h->stream, h->P + h->oE, w.lead, w.emb_tgt, rt, D, V));
+                    AV_TRY(run_decoder_rnn(h, w, n, T, w.h0, 0, false));
+                }
+            }
+            AV_TRY(run_logits_ce(h, w, rt, false, 0.f));
+            const ScoreRows sr{w.loss_samp, w.rank, T, n, rc, k0, r0, B, s.logpx, s.ntok};
+            AV_CHECK(score_rows(h->stream, sr));
+        }
+    return 0;
+}
+
+// the GRU time-out word and the eps word in one synchronisation
+int check_score_err(avae_ctx* h)
+{
+    int e = 0;
+    AV_CHECK(hipMemcpyAsync(&e, h->errw + kScoreErrWord, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    const int gru = check_gru_err(h);
+    if (e) (void)hipMemsetAsync(h->errw + kScoreErrWord, 0, sizeof(int), h->stream);      // (whatever the GRU check said: the flag must not outlive its call)
+    if (gru) return gru;
+    if (e) return fail(h, "score: eps holds a value that is not finite");
+    return 0;
+}
+
 }  // namespace
 
 // ================================================================================= C ABI
@@ -1475,6 +1640,14 @@ int avae_timing_collect(avae_handle h, double* out)
 // rows of the launch geometry the GRU team kernels take for a batch of B rows (gru_team_batch: B itself, the next row count with a
 // geometry -- the slots beyond B hold phantom rows --, or 0).  Host arithmetic only: callable without a GPU.
 int avae_debug_team_batch(int32_t B) { return B > 0 ? gru_team_batch(B) : 0; }
+// test hook: the decoder batches of the last avae_score / avae_score_z (score_plan): out = N, rc, kc, batches that ran the shared
+// first-layer projection of the non-table path (lead_rows + GruJob::gi_rows)
+int avae_debug_score_plan(avae_handle h, int32_t out[4])
+{
+    if (!h || !out) return 1;
+    for (int i = 0; i < 4; ++i) out[i] = h->score_plan[i];
+    return 0;
+}
 // ids present in the last forward's two id sources (encoder input, decoder input) where those layers were table-fed
 // (use_table), else -1: out[0] = src, out[1] = tgt.  Synchronises.
 int avae_debug_present_ids(avae_handle h, int32_t out[2])
@@ -1671,16 +1844,7 @@ int avae_encode(avae_handle h, const int32_t* src, int32_t b, int32_t t, float* 
     AV_CHECK(hipSetDevice(h->device));
     Ws w;
     AV_TRY(get_ws(h, w, b, t, 1, false));
-    PrepArgs p{};
-    p.src = src; p.tgt = src; p.B = b; p.Ss = t; p.St = 1; p.eos = h->cfg.eos; p.bos = h->cfg.bos;
-    p.src_tm = w.src_tm; p.lens_src = w.lens_src; p.lens_tgt = w.lens_tgt; p.lead = w.lead; p.gold = w.gold;
-    p.rank = w.rank; p.cidx = w.cidx; p.ntok = w.ntok; p.chunk_counts = w.ntok + 4;
-    // tgt is unused by the encoder; feed the first column of src as a 1-wide dummy target
-    AV_CHECK(prep_ids(h->stream, p));
-    AV_TRY(build_row_orders(h, w, b, t, 2, false));
-    AV_TRY(build_compact(h, w, b, t, 0, false));
-    AV_TRY(run_encoder(h, w, b, t, false));
-    AV_TRY(run_latent(h, w, b, false, 0, nullptr));
+    AV_TRY(encode_ws(h, w, src, b, t));
     const size_t n = (size_t)b * h->cfg.dim_rep * sizeof(float);
     if (z_out) AV_CHECK(hipMemcpyAsync(z_out, w.mu, n, hipMemcpyDeviceToDevice, h->stream));
     if (lv_out) AV_CHECK(hipMemcpyAsync(lv_out, w.lv, n, hipMemcpyDeviceToDevice, h->stream));
@@ -1905,6 +2069,56 @@ int avae_debug_sample_rows(avae_handle h, const float* logits, int n, int V, int
     if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
     AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, nullptr, h->cfg.eos, pred, logp));
     return 0;
+}
+
+int avae_score_z(avae_handle h, const float* z, const int32_t* tgt, int32_t b, int32_t St, float* logpx, int32_t* ntok)
+{
+    if (!h) return 1;
+    AV_TRY(check_bound(h));
+    if (b < 1 || St < 1) return fail(h, "score: empty batch");
+    if (!z || !tgt || !logpx) return fail(h, "score: z, tgt and logpx must be given");
+    AV_CHECK(hipSetDevice(h->device));
+    const int R = h->cfg.dim_rep;
+    const ScorePlan sp = score_plan(h, b, 1, St);
+    ScoreWs s;
+    AV_TRY(score_ws(h, sp, b, 1, 0, St, s));
+    AV_CHECK(hipMemcpyAsync(s.z, z, (size_t)b * R * sizeof(float), hipMemcpyDeviceToDevice, h->stream));      // (k = 1: the batch order is the row order)
+    AV_TRY(score_rows_dev(h, sp, s, tgt, b, 1, St));
+    AV_CHECK(hipMemcpyAsync(logpx, s.logpx, (size_t)b * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (ntok) AV_CHECK(hipMemcpyAsync(ntok, s.ntok, (size_t)b * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    return check_gru_err(h);
+}
+
+int avae_score(avae_handle h, const int32_t* src, const int32_t* tgt, int32_t B, int32_t Ss, int32_t St, const avae_score_config* sc,
+               const float* eps, float* eps_out, float* logpx, float* logw, float* bound, int32_t* ntok)
+{
+    if (!h) return 1;
+    AV_TRY(check_bound(h));
+    if (!sc) return fail(h, "score config is null");
+    if (sc->k < 1) return fail(h, "score: k must be >= 1");
+    if (B < 1 || Ss < 1 || St < 1) return fail(h, "score: empty batch");
+    if (!bound) return fail(h, "score: bound must be given");
+    if (!src || !tgt) return fail(h, "score: src and tgt must be given");
+    const int R = h->cfg.dim_rep, k = sc->k;
+    if (k > (1 << 20) || R > (1 << 20)) return fail(h, "score: the draw index holds 2^20 draws and 2^20 latent dimensions");
+    if ((size_t)k * B > ((size_t)1 << 30) / R) return fail(h, "score: k x B x dim_rep exceeds 2^30 elements");
+    AV_CHECK(hipSetDevice(h->device));
+    const ScorePlan sp = score_plan(h, B, k, St);
+    ScoreWs s;
+    AV_TRY(score_ws(h, sp, B, k, Ss, St, s));
+    {   // the encoder once, then every draw
+        Ws w;
+        Bump real{h->ws};
+        layout(h, real, w, B, Ss, 1, false);
+        AV_TRY(encode_ws(h, w, src, B, Ss));
+        const ScoreDraw d{w.mu, w.lv, eps, eps_out, s.z, s.lat, h->errw + kScoreErrWord, k, B, R, sp.rc, sc->seed};
+        AV_CHECK(score_draw(h->stream, d));
+    }
+    AV_TRY(score_rows_dev(h, sp, s, tgt, B, k, St));
+    AV_CHECK(score_bound(h->stream, s.logpx, s.lat, k, B, logw, bound));
+    if (logpx) AV_CHECK(hipMemcpyAsync(logpx, s.logpx, (size_t)k * B * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    if (ntok) AV_CHECK(hipMemcpyAsync(ntok, s.ntok, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
+    return check_score_err(h);
 }
 
 }  // extern "C"

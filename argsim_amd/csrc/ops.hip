@@ -10,17 +10,7 @@ namespace avae {
 // ---------------------------------------------------------------- counter RNG
 // stateless: value = f(seed, stream, index).  (Not TF's Philox stream: the reference's draws
 // are unreproducible anyway; parity tests inject keep_mask / eps.)
-// (mix64 itself: sample_dev.h, shared with the samplers)
-__device__ __forceinline__ float uniform01(uint64_t seed, uint64_t stream, uint64_t idx)
-{
-    uint64_t r = mix64(mix64(seed ^ (stream * 0xD6E8FEB86659FD93ULL)) + idx);
-    return (float)((r >> 40) + 0.5) * (1.0f / 16777216.0f);      // (0,1)
-}
-__device__ __forceinline__ float normal01(uint64_t seed, uint64_t stream, uint64_t idx)
-{
-    float u1 = uniform01(seed, stream, 2 * idx), u2 = uniform01(seed, stream, 2 * idx + 1);
-    return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
+// (mix64, uniform01, normal01 themselves: sample_dev.h, shared with the samplers and score.hip)
 
 // ---------------------------------------------------------------- prep_ids
 // src/model.py:82-95 + src/util_tf.py:40-57: transpose to time-major, lengths, decoder mask,

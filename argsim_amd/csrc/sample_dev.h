@@ -16,6 +16,19 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)
     return x ^ (x >> 31);
 }
 
+// the generator itself: value = f(seed, stream, index).  Streams: 1 word dropout, 2 epsilon (ops.hip), 3 Gumbel (below),
+// 4 the draws of the importance-weighted score (score.hip)
+__device__ __forceinline__ float uniform01(uint64_t seed, uint64_t stream, uint64_t idx)
+{
+    uint64_t r = mix64(mix64(seed ^ (stream * 0xD6E8FEB86659FD93ULL)) + idx);
+    return (float)((r >> 40) + 0.5) * (1.0f / 16777216.0f);      // (0,1)
+}
+__device__ __forceinline__ float normal01(uint64_t seed, uint64_t stream, uint64_t idx)
+{
+    float u1 = uniform01(seed, stream, 2 * idx), u2 = uniform01(seed, stream, 2 * idx + 1);
+    return sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+
 // stream 3 of the generator (1: word dropout, 2: epsilon).  key = sample_key(seed) once per call / thread;
 // index = ((row << 20) + step) << 20 + v: a row's draws depend on neither the batch size nor the step cap.
 __device__ __forceinline__ uint64_t sample_key(uint64_t seed) { return mix64(seed ^ (3ULL * 0xD6E8FEB86659FD93ULL)); }

@@ -40,6 +40,10 @@ class AvaeSampleConfig(C.Structure):
     _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64)]
 
 
+class AvaeScoreConfig(C.Structure):
+    _fields_ = [('k', C.c_int32), ('seed', C.c_uint64)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -69,6 +73,8 @@ SIGNATURES = {
     'avae_decode_step': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     'avae_decode_greedy': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'avae_decode_sample': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSampleConfig), _P, _P, C.POINTER(C.c_int32)]),
+    'avae_score': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AvaeScoreConfig), _P, _P, _P, _P, _P, _P]),
+    'avae_score_z': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),
@@ -83,6 +89,7 @@ SIGNATURES = {
     'avae_debug_train_ce': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),
     'avae_debug_stamps': (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     'avae_debug_present_ids': (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    'avae_debug_score_plan': (C.c_int, [_P, C.POINTER(C.c_int32)]),
     'avae_debug_team_batch': (C.c_int, [C.c_int32]),
     'avae_bucket_count': (C.c_int, [_P]),
     'avae_bucket_info': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -11,6 +11,8 @@ The reference's feed -> fetch pairs map to methods:
     model.z.eval({model.src: x})  / encode(sess,vae,x) -> VAE.encode(x) / encode(vae, x)
     decode(sess, vae, z, steps)                        -> VAE.decode(z, steps) / decode(vae, z, steps)
     (new) sampled decoding                             -> VAE.sample(z, ...) / VAE.generate(n, ...) / sample(vae, z, ...)
+    (new) importance-weighted log p(x), k draws        -> VAE.score(src, tgt, k, ...) / score(vae, src, k, seed)
+    (new) teacher-forced log p(tgt | z)                -> VAE.score_z(z, tgt)
 """
 import ctypes as C
 
@@ -351,6 +353,65 @@ class VAE:
         return self.sample(z, steps, temperature, top_k, seed, return_logp)
 
 
+    # ------------------------------------------------------------------ likelihood
+    def score(self, src, tgt=None, k=1, seed=0, eps=None, return_parts=False):
+        """k-sample importance-weighted bound on log p(tgt row) with the proposal q(z | src row) (include/argsim_vae.h, avae_score):
+        f32 (B,), nats per sentence; tgt=None scores src itself.  The encoder runs once, the k draws go through the decoder as rows.
+        eps (k, B, R) overrides the generator (stream 4, reproducible from seed).  With return_parts a dict: bound (B,), logw (k, B),
+        logpx (k, B) = log p(tgt | z_k), ntok (B,) positions scored per row (its length + 1), eps (k, B, R) the draws used;
+        logw.mean(0) is the k-sample ELBO estimate, exp(-bound.sum() / ntok.sum()) the per-token perplexity."""
+        k, seed = _check_score_args(k, seed)
+        src = self._ids(self.trim(src))
+        tgt = src if tgt is None else self._ids(self.trim(tgt))
+        B, R = src.shape[0], self.cfg['dim_rep']
+        if src.dim() != 2 or tgt.dim() != 2 or tgt.shape[0] != B or B < 1:
+            raise ValueError("src and tgt must be (B, S) with the same B >= 1, got %s and %s" % (tuple(src.shape), tuple(tgt.shape)))
+        ep = None
+        if eps is not None:
+            ep = torch.as_tensor(np.ascontiguousarray(eps, dtype=np.float32)).to(self.device).contiguous()
+            if tuple(ep.shape) != (k, B, R):
+                raise ValueError("eps must be (k, B, dim_rep) = %s, got %s" % ((k, B, R), tuple(ep.shape)))
+        f32 = dict(dtype=torch.float32, device=self.device)
+        bound = torch.empty(B, **f32)
+        logw = logpx = eps_out = ntok = None
+        if return_parts:
+            logw, logpx, eps_out = torch.empty((k, B), **f32), torch.empty((k, B), **f32), torch.empty((k, B, R), **f32)
+            ntok = torch.empty(B, dtype=torch.int32, device=self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        sc = _lib.AvaeScoreConfig(k, seed)
+        self._stream()
+        self._ck(self._l.avae_score(self._h, ptr(src), ptr(tgt), B, src.shape[1], tgt.shape[1], C.byref(sc), ptr(ep), ptr(eps_out),
+                                    ptr(logpx), ptr(logw), ptr(bound), ptr(ntok)))
+        if not return_parts:
+            return bound.cpu().numpy()
+        return dict(bound=bound.cpu().numpy(), logw=logw.cpu().numpy(), logpx=logpx.cpu().numpy(), ntok=ntok.cpu().numpy(),
+                    eps=eps_out.cpu().numpy())
+
+    def score_z(self, z, tgt):
+        """teacher-forced log p(tgt row | z row) (avae_score_z), the inverse of sample(): (logpx f32 (b,), ntok i32 (b,)) -- the sum
+        of the log-probabilities of the row's tokens and its closing eos, and how many positions that is"""
+        z = torch.as_tensor(np.ascontiguousarray(z, dtype=np.float32)).to(self.device)
+        tgt = self._ids(self.trim(tgt))
+        if z.dim() != 2 or z.shape[1] != self.cfg['dim_rep'] or z.shape[0] < 1 or tgt.dim() != 2 or tgt.shape[0] != z.shape[0]:
+            raise ValueError("z must be (b, dim_rep) and tgt (b, S) with b >= 1, got %s and %s" % (tuple(z.shape), tuple(tgt.shape)))
+        b = z.shape[0]
+        logpx = torch.empty(b, dtype=torch.float32, device=self.device)
+        ntok = torch.empty(b, dtype=torch.int32, device=self.device)
+        self._stream()
+        self._ck(self._l.avae_score_z(self._h, C.c_void_p(z.data_ptr()), C.c_void_p(tgt.data_ptr()), b, tgt.shape[1],
+                                      C.c_void_p(logpx.data_ptr()), C.c_void_p(ntok.data_ptr())))
+        return logpx.cpu().numpy(), ntok.cpu().numpy()
+
+
+def _check_score_args(k, seed):
+    """the argument rules of avae_score, checked before anything touches the device -> (k, seed) as ints"""
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= 1 << 20:
+        raise ValueError("k must be an integer in [1, 2^20], got %r" % (k,))
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be an integer in [0, 2^64), got %r" % (seed,))
+    return int(k), int(seed)
+
+
 def _check_sample_args(steps, temperature, top_k, seed):
     """the argument rules of avae_decode_sample, checked before anything touches the device -> (steps, top_k, seed) as ints"""
     if isinstance(steps, bool) or int(steps) != steps or not 1 <= steps <= 1 << 20:
@@ -384,3 +445,8 @@ def decode(vae, z, steps=256):
 def sample(vae, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
     """sampled counterpart of decode(): VAE.sample"""
     return vae.sample(z, steps, temperature, top_k, seed, return_logp)
+
+
+def score(vae, src, k=1, seed=0):
+    """importance-weighted log p(src row) per sentence, k draws: VAE.score"""
+    return vae.score(src, None, k, seed)

@@ -40,8 +40,13 @@ def parse_args(argv=None):
     p.add_argument('--save-tf', action='store_true', help="also write every checkpoint as TF V2 checkpoint files "
                    "(<ckpt>/<trial><round>.index/.data-*), the format the reference's eval scripts restore; CudnnGRU "
                    "names are unverified against a real TensorFlow (ckpt.py)")
+    p.add_argument('--iw', default=0, type=int, help="validation also reports the K-sample importance-weighted NLL per sentence "
+                   "and its per-token perplexity (nll_iw, ppl_iw); 0 = off")
     p.add_argument('--profile-run', action='store_true', help=argparse.SUPPRESS)    # the child that --profile traces
-    return p.parse_args(argv)
+    A = p.parse_args(argv)
+    if not 0 <= A.iw <= 1 << 20:
+        p.error("--iw must be in [0, 2^20] (0 = off), got %d" % A.iw)
+    return A
 
 
 def batch(size, path, vocab, seed, kudo, max_len, rank=0, world=1):
@@ -123,6 +128,28 @@ def summ(model, valid, batch_valid, rank=0, world=1, group=None):
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     e, g, n, k, m = (float(x) for x in t)
     return e / n, g / n, k / m
+
+
+def summ_iw(model, valid, batch_valid, k, seed, rank=0, world=1, group=None):
+    """(nll_iw, ppl_iw) over ALL validation sentences: the mean per sentence of minus the k-sample importance-weighted bound on
+    log p(x) (VAE.score) and the per-token perplexity exp(-sum bound / sum ntok).  Sharded and summed exactly as ``summ``: the chunks
+    of ``partition`` dealt round-robin over the ranks, the three sums (bound, positions, sentences) added in float64 on the
+    host-side group."""
+    import math
+    import numpy as np
+    from .util_np import partition
+    chunks = list(partition(len(valid), batch_valid, discard=False))[rank::world]
+    parts = [model.score(valid[i:j], None, k, seed, return_parts=True) for i, j in chunks]
+    sums = [sum(float(p['bound'].sum(dtype=np.float64)) for p in parts), float(sum(int(p['ntok'].sum()) for p in parts)),
+            float(sum(p['bound'].size for p in parts))]
+    if world > 1:
+        import torch
+        import torch.distributed as dist
+        t = torch.tensor(sums, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        sums = [float(x) for x in t]
+    b, n, m = sums
+    return -b / m, math.exp(-b / n)
 
 
 def with_global_counts(gen, eos, group):
@@ -254,9 +281,13 @@ def main(argv=None):
             dt = time.perf_counter() - t0
             step = model.step
             errt, vgen, vkld = summ(model, valid, T.batch_valid, rank, world, valid_group)      # every rank: its share of the chunks
+            if A.iw > 0:       # every rank too; the draws are those of (seed, validation row within its chunk, draw)
+                nll_iw, ppl_iw = summ_iw(model, valid, T.batch_valid, A.iw, A.seed, rank, world, valid_group)
             if rank == 0:
                 rec = dict(step=step, step_errt=errt, step_loss_gen=vgen, step_loss_kld=vkld,
                            train_loss_gen=lg, train_loss_kld=lk, sentences_per_sec=A.valid_every * T.batch_train / dt)
+                if A.iw > 0:
+                    rec.update(nll_iw=nll_iw, ppl_iw=ppl_iw)
                 log.write(json.dumps(rec) + "\n")
                 log.flush()
                 print(rec)

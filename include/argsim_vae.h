@@ -169,6 +169,48 @@ typedef struct avae_sample_config { float temperature; int32_t top_k; uint64_t s
 int  avae_decode_sample(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_config* sc,
                         int32_t* out_ids, float* logp_out, int32_t* n_steps);
 
+/* ---- importance-weighted sentence likelihood --------------------------------------------- */
+/* A K-sample importance-weighted bound on log p(tgt row) with the proposal q(z | src row), and its decoder half alone:
+ * the teacher-forced log p(tgt row | z row) of sentences the caller supplies (the inverse of avae_decode_sample).
+ * For batch row r, draw k (0-based) and latent dimension j:
+ *   mu, lv  the valid-mode encoder of src, as avae_encode returns them.
+ *   eps     eps[k, r, j] of the caller's array if given, else normal01(seed, 4, idx), idx = ((r 2^20) + k) 2^20 + j: stream 4
+ *           of the library's counter generator (1 word dropout, 2 epsilon, 3 Gumbel), Box-Muller in fp32 on
+ *           u1 = uniform01(2 idx), u2 = uniform01(2 idx + 1): sqrt(-2 log u1) cos(2 pi u2), uniform01(i) = ((x >> 40) + 0.5) 2^-24,
+ *           x = mix64(mix64(seed ^ (4 * 0xD6E8FEB86659FD93)) + i).  idx holds neither B nor K: a row's draws do not depend on
+ *           the rows around it, and the first K' draws of a K-sample call are the draws of a K'-sample call.
+ *           k > 2^20 or dim_rep > 2^20 is refused.
+ *   z       z[k, r] = mu[r] + exp(0.5 lv[r]) eps[k, r] in fp32, as the training forward draws it.
+ *   logpx   logpx[k, r] = - sum of the per-token cross-entropy over the positions of row r that the decoder mask keeps
+ *           (src/model.py:90-91: position 0 and every position whose preceding target id is not eos), the decoder fed
+ *           lead = [bos] + tgt WITHOUT word dropout from the initial state of z[k, r]: log p(tgt row | z[k, r]).
+ *   ntok    ntok[r] = how many positions that is (>= 1).
+ *   logw    logw[k, r] = logpx[k, r] - 1/2 sum_j (z_j^2 - eps_j^2 - lv_j) = log p(x | z) + log p(z) - log q(z | x); the log 2 pi
+ *           terms cancel and are never computed.
+ *   bound   bound[r] = logsumexp_k logw[k, r] - log K, the maximum over k subtracted before the exponentials (at dim_emb 512
+ *           logw is around -600 and its own exponential is 0 in fp32).  mean_k logw is the K-sample ELBO estimate; the
+ *           caller can form it from logw.
+ * Errors (text through avae_last_error): k < 1, B < 1, S_src < 1, S_tgt < 1, a null sc, a null bound, a null src or tgt, an eps that
+ * is not finite (the caller's array is checked on the device while it is read), k > 2^20, dim_rep > 2^20, k B dim_rep > 2^30
+ * elements.  avae_score_z refuses b < 1, S_tgt < 1 and a null z, tgt or logpx; it does NOT check z: a z that is not finite gives a
+ * logpx that is not finite.
+ * Every array is device memory.  The encoder runs once; the K x B (k, r) pairs go through the decoder as rows, in batches
+ * of at most 256 rows whose logits fit the workspace, the draws of a row sharing one first-layer input
+ * projection.  No float atomics anywhere on the path: the same arguments give the same bits.  Both entries are enqueued on
+ * the handle's stream and end with the GRU time-out check, which synchronises it, as avae_encode does.                   */
+typedef struct avae_score_config { int32_t k; uint64_t seed; } avae_score_config;
+int  avae_score(avae_handle h, const int32_t* src, const int32_t* tgt, int32_t B, int32_t S_src, int32_t S_tgt,
+                const avae_score_config* sc,
+                const float* eps,      /* optional (k,B,R) device: overrides the generator              */
+                float* eps_out,        /* optional (k,B,R) device: the draws used                       */
+                float* logpx,          /* optional (k,B)                                                */
+                float* logw,           /* optional (k,B)                                                */
+                float* bound,          /* (B)                                                           */
+                int32_t* ntok);        /* optional (B) device: positions scored per row                 */
+/* teacher-forced log p(tgt row | z row): the decoder half alone, z (b, dim_rep) supplied by the caller */
+int  avae_score_z(avae_handle h, const float* z, const int32_t* tgt, int32_t b, int32_t S_tgt,
+                  float* logpx /* (b) */, int32_t* ntok /* optional (b) */);
+
 #ifdef __cplusplus
 }
 #endif
