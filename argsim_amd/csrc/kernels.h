@@ -283,6 +283,35 @@ hipError_t score_rows(hipStream_t st, const ScoreRows& a);
 // logw (k, B, optional) = logpx - lat; bound (B) = logsumexp_k logw - log k, the maximum subtracted
 hipError_t score_bound(hipStream_t st, const float* logpx, const float* lat, int k, int B, float* logw, float* bound);
 
+// ---------------------------------------------------------------- beam search (beam.hip)
+// One token of the search over n sentences of W hypotheses (contract: include/argsim_vae.h, avae_decode_beam); hypothesis (r, w)
+// is row r * W + w of every per-row array.  Win = rows a sentence has going INTO the step (1 at the first token, then W).
+// beam_rows: per row of logits (rows, V) its W best candidates cum + logp, best first: cand_sc / cand_tok (rows, W), cand_cnt (rows);
+// a finished row (fin, optional) offers (cum, eos) alone; cum null: zeros.  W == 1 ranks by the logit itself (the first maximum).
+hipError_t beam_rows(hipStream_t st, const float* logits, int rows, int V, int W, const float* cum, const int32_t* fin, int eos,
+                     float* cand_sc, int32_t* cand_tok, int32_t* cand_cnt);
+struct BeamStep {
+    int n, Win, W, eos;
+    const float* cand_sc; const int32_t* cand_tok; const int32_t* cand_cnt;       // (n * Win, W) from beam_rows
+    const int32_t* fin_in; const int32_t* len_in;                                 // (n * Win) or null (nothing finished, length 0)
+    int32_t* lat_parent; int32_t* lat_token; float* lat_cum;                      // (n * W): the step's lattice entry
+    float* cum_out; int32_t* fin_out; int32_t* len_out;                           // (n * W)
+    int32_t* live;                                                                // [1] += slots not finished after the step
+};
+hipError_t beam_select(hipStream_t st, const BeamStep& a);
+// state_out (L, n * W, D): row r * W + j of layer l <- row r * Win + parent[r * W + j] of hd[l] (n * Win, D)
+hipError_t beam_gather(hipStream_t st, const float* const* hd, int L, int n, int Win, int W, int D, const int32_t* parent, float* state_out);
+struct BeamEnd {
+    int n, W, n_run, steps, eos;
+    const int32_t* lat_parent; const int32_t* lat_token; const float* lat_cum;    // (n_run, n * W)
+    const float* cum; const int32_t* len;                                         // (n * W) after the last step
+    const float* lenpow;                                                          // [len] = len^alpha as fp32, or null: score = cum
+    int32_t* out_ids;                                                             // (n, W, steps), ranked best first, eos beyond n_run
+    float* score_out; float* cum_out; int32_t* len_out;                           // (n, W) ranked, optional
+    int32_t* o_parent; int32_t* o_token; float* o_cum; size_t out_step;           // optional caller lattice, row stride out_step per step
+};
+hipError_t beam_backtrack(hipStream_t st, const BeamEnd& a);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

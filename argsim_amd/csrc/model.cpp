@@ -1870,7 +1870,7 @@ static int decode_logits_ws(avae_handle h, Ws& w, const int32_t* lead, const flo
     const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
     AV_CHECK(embed_gather(h->stream, h->P + h->oE, lead, w.emb_tgt, b, D, V));
     AV_TRY(run_decoder_rnn(h, w, b, 1, state_in, (int64_t)b * D, false));
-    for (int i = 0; i < L; ++i)
+    for (int i = 0; i < L && state_out; ++i)      // (null: the caller takes the new state out of w.d_hd itself -- the beam search gathers it by parent)
         AV_CHECK(hipMemcpyAsync(state_out + (size_t)i * b * D, w.d_hd[i], (size_t)b * D * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     AV_TRY(gemm(h, false, true, w.d_hd[L - 1], D, h->P + h->oKout, D, w.ho, D, b, D, D, 1.f, h->P + h->oBout));
     AV_TRY(gemm(h, false, false, w.ho, D, h->P + h->oE, D, w.logits, V, b, V, D, 1.f / sqrtf((float)D)));
@@ -2068,6 +2068,155 @@ int avae_debug_sample_rows(avae_handle h, const float* logits, int n, int V, int
     if (!sample_params(h, sc, V, &sp)) return 1;
     if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
     AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, nullptr, h->cfg.eos, pred, logp));
+    return 0;
+}
+
+// ---------------------------------------------------------------- beam search (contract: include/argsim_vae.h, avae_decode_beam; kernels: beam.hip)
+// h->scratch is ONE buffer shared by get / set_tensor staging, the greedy and sampled loops, the beam search and its debug hook: every
+// user lays it out afresh per call and all work is ordered on the handle's stream, so no call sees another's data.  (decode_stepwise
+// and decode_loop keep their own inline copies of this growth step.)
+static int grow_scratch(avae_handle h, size_t need, const char* what)
+{
+    if (h->scratch_n >= (int64_t)need) return 0;
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    if (h->scratch) AV_CHECK(hipFree(h->scratch));
+    h->scratch = nullptr; h->scratch_n = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&h->scratch), need) != hipSuccess) {
+        (void)hipGetLastError();
+        h->scratch = nullptr;
+        char b_[256]; snprintf(b_, sizeof b_, "%s: %.0f MB of scratch could not be allocated on the device", what, (double)need / 1048576.0);
+        return fail(h, b_);
+    }
+    h->scratch_n = (int64_t)need;
+    return 0;
+}
+
+int avae_decode_beam(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_beam_config* bc, int32_t* out_ids, float* score,
+                     float* cum, int32_t* len, int32_t* lat_parent, int32_t* lat_token, float* lat_cum, int32_t* n_steps)
+{
+    if (!h) return 1;
+    AV_TRY(check_bound(h));
+    if (!bc) return fail(h, "beam config is null");
+    if (!z || !out_ids) return fail(h, "beam: z and out_ids must be given");
+    if (b < 1 || steps < 1) return fail(h, "beam: empty batch");
+    const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers, R = h->cfg.dim_rep, eos = h->cfg.eos, W = bc->width;
+    if (W < 1 || W > 32) return fail(h, "beam: width must be in [1, 32]");
+    if (W > V) return fail(h, "beam: width exceeds dim_tgt");
+    if (!(bc->length_alpha >= 0.f) || std::isinf(bc->length_alpha)) return fail(h, "beam: length_alpha must be a finite number >= 0");
+    if (steps > (1 << 20)) return fail(h, "beam: at most 2^20 steps");
+    AV_CHECK(hipSetDevice(h->device));
+    // sentences go through the search in groups of at most floor(1024 / width): at most 1024 decoder rows per step and a bounded workspace
+    const int gs = 1024 / W, gmax = std::min<int>(b, gs), rmax = gmax * W;
+    { Ws probe; AV_TRY(get_ws(h, probe, rmax, 1, 1, false)); }      // the workspace grows HERE if it has to, never inside the loop
+    // scratch, sized once per call (4-byte words): state x2 | cum x2 | lat_cum | cand_sc | lenpow || fin x2 | len x2 | lat_parent | lat_token | cand_tok | cand_cnt | live | bos
+    const size_t sn = (size_t)L * rmax * D, lat = (size_t)steps * rmax;
+    const size_t nf = 2 * sn + 2 * (size_t)rmax + lat + (size_t)rmax * W + (size_t)steps + 1;
+    const size_t ni = 4 * (size_t)rmax + 2 * lat + (size_t)rmax * W + (size_t)rmax + (size_t)steps + (size_t)gmax;
+    // (the group lattice is 12 bytes x steps x rows: 6 MB at steps 512 x 1024 rows, 12 GB at the 2^20 steps the contract admits -- a size
+    // the device cannot serve is refused with a message that names it)
+    AV_TRY(grow_scratch(h, (nf + ni) * 4, "beam: the search lattice (12 bytes x steps x min(b x width, 1024 rows)) and state"));
+    float* state[2] = {h->scratch, h->scratch + sn};
+    float* cumb[2] = {state[1] + sn, state[1] + sn + rmax};
+    float* g_lat_cum = cumb[1] + rmax;
+    float* cand_sc = g_lat_cum + lat;
+    float* lenpow = cand_sc + (size_t)rmax * W;
+    int32_t* ip = reinterpret_cast<int32_t*>(h->scratch + nf);
+    int32_t* finb[2] = {ip, ip + rmax};
+    int32_t* lenb[2] = {ip + 2 * (size_t)rmax, ip + 3 * (size_t)rmax};
+    int32_t* g_lat_parent = ip + 4 * (size_t)rmax;
+    int32_t* g_lat_token = g_lat_parent + lat;
+    int32_t* cand_tok = g_lat_token + lat;
+    int32_t* cand_cnt = cand_tok + (size_t)rmax * W;
+    int32_t* live = cand_cnt + rmax;
+    int32_t* lead0 = live + steps;
+    const bool norm = bc->length_alpha != 0.f;
+    std::vector<float> lp;
+    if (norm) {      // len^alpha in double on the host, rounded to fp32; the kernel divides in fp32
+        lp.resize((size_t)steps + 1);
+        for (int i = 0; i <= steps; ++i) lp[i] = (float)std::pow((double)std::max(i, 1), (double)bc->length_alpha);
+        AV_CHECK(hipMemcpyAsync(lenpow, lp.data(), lp.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    std::vector<int32_t> bos((size_t)gmax, h->cfg.bos);
+    AV_CHECK(hipMemcpyAsync(lead0, bos.data(), bos.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    AV_CHECK(hipStreamSynchronize(h->stream));      // the two host vectors are read: an early return below leaves no copy pending on them
+    int n_max = 0;
+    const int chunk = 16;
+    for (int r0 = 0; r0 < b; r0 += gs) {
+        const int n = std::min(gs, b - r0), rows = n * W;
+        Ws w0, w1;                 // the decoder's buffers for the n rows of the first token and the n * W rows of every later one
+        AV_TRY(get_ws(h, w0, n, 1, 1, false));
+        AV_TRY(get_ws(h, w1, rows, 1, 1, false));
+        AV_CHECK(hipMemsetAsync(live, 0, (size_t)steps * sizeof(int32_t), h->stream));
+        AV_TRY(avae_decode_init(h, z + (size_t)r0 * R, n, state[0]));
+        int done = 0, n_run = 0, cur = 0;
+        while (done < steps && !n_run) {
+            const int m = std::min(chunk, steps - done);
+            for (int s = 0; s < m; ++s) {
+                const int t = done + s, Win = t ? W : 1, rin = n * Win;
+                Ws& w = t ? w1 : w0;
+                const int32_t* lead = t ? g_lat_token + (size_t)(t - 1) * rows : lead0;
+                AV_TRY(decode_logits_ws(h, w, lead, state[cur], rin, nullptr));
+                AV_CHECK(beam_rows(h->stream, w.logits, rin, V, W, t ? cumb[cur] : nullptr, t ? finb[cur] : nullptr, eos, cand_sc, cand_tok, cand_cnt));
+                BeamStep a{};
+                a.n = n; a.Win = Win; a.W = W; a.eos = eos;
+                a.cand_sc = cand_sc; a.cand_tok = cand_tok; a.cand_cnt = cand_cnt;
+                a.fin_in = t ? finb[cur] : nullptr; a.len_in = t ? lenb[cur] : nullptr;
+                a.lat_parent = g_lat_parent + (size_t)t * rows; a.lat_token = g_lat_token + (size_t)t * rows; a.lat_cum = g_lat_cum + (size_t)t * rows;
+                a.cum_out = cumb[cur ^ 1]; a.fin_out = finb[cur ^ 1]; a.len_out = lenb[cur ^ 1];
+                a.live = live + t;
+                AV_CHECK(beam_select(h->stream, a));
+                AV_CHECK(beam_gather(h->stream, w.d_hd.data(), L, n, Win, W, D, a.lat_parent, state[cur ^ 1]));
+                cur ^= 1;
+            }
+            int32_t alive[chunk];
+            AV_CHECK(hipMemcpyAsync(alive, live + done, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            AV_CHECK(hipStreamSynchronize(h->stream));
+            for (int s = 0; s < m && !n_run; ++s) if (alive[s] == 0) n_run = done + s + 1;
+            done += m;
+        }
+        if (!n_run) n_run = done;
+        // (the steps a chunk ran beyond n_run moved nothing: every slot was finished, the beam stays in its order)
+        BeamEnd e{};
+        e.n = n; e.W = W; e.n_run = n_run; e.steps = steps; e.eos = eos;
+        e.lat_parent = g_lat_parent; e.lat_token = g_lat_token; e.lat_cum = g_lat_cum;
+        e.cum = cumb[cur]; e.len = lenb[cur]; e.lenpow = norm ? lenpow : nullptr;
+        const size_t o = (size_t)r0 * W;
+        e.out_ids = out_ids + o * steps;
+        e.score_out = score ? score + o : nullptr; e.cum_out = cum ? cum + o : nullptr; e.len_out = len ? len + o : nullptr;
+        e.o_parent = lat_parent ? lat_parent + o : nullptr; e.o_token = lat_token ? lat_token + o : nullptr; e.o_cum = lat_cum ? lat_cum + o : nullptr;
+        e.out_step = (size_t)b * W;
+        AV_CHECK(beam_backtrack(h->stream, e));
+        n_max = std::max(n_max, n_run);
+    }
+    AV_TRY(check_gru_err(h));       // synchronises
+    if (n_steps) *n_steps = n_max;
+    return 0;
+}
+
+// test hook: one selection step of the beam search (beam_rows + beam_select, beam.hip) on caller buffers: logits (n * width, V), cum and
+// fin (n * width) -> parent, token, cum_out, fin_out (n * width)
+int avae_debug_beam_select(avae_handle h, const float* logits, int n, int width, int V, const float* cum, const int32_t* fin,
+                           int32_t* parent, int32_t* token, float* cum_out, int32_t* fin_out)
+{
+    if (!h) return 1;
+    if (!logits || !cum || !fin || !parent || !token || !cum_out || !fin_out) return fail(h, "beam select: every array must be given");
+    if (n < 1 || n > (1 << 20) || V < 1 || width < 1 || width > 32 || width > V) return fail(h, "beam select: bad shape or width");
+    AV_CHECK(hipSetDevice(h->device));
+    const size_t rows = (size_t)n * width;
+    AV_TRY(grow_scratch(h, (2 * rows * width + 3 * rows + 1) * 4, "beam select"));
+    float* cand_sc = h->scratch;
+    float* lat_cum = cand_sc + rows * width;
+    int32_t* cand_tok = reinterpret_cast<int32_t*>(lat_cum + rows);
+    int32_t* cand_cnt = cand_tok + rows * width;
+    int32_t* len_out = cand_cnt + rows;      // (the lengths and the live count are not returned)
+    AV_CHECK(beam_rows(h->stream, logits, (int)rows, V, width, cum, fin, h->cfg.eos, cand_sc, cand_tok, cand_cnt));
+    BeamStep a{};
+    a.n = n; a.Win = width; a.W = width; a.eos = h->cfg.eos;
+    a.cand_sc = cand_sc; a.cand_tok = cand_tok; a.cand_cnt = cand_cnt; a.fin_in = fin; a.len_in = nullptr;
+    a.lat_parent = parent; a.lat_token = token; a.lat_cum = lat_cum; a.cum_out = cum_out; a.fin_out = fin_out; a.len_out = len_out;
+    a.live = len_out + rows;
+    AV_CHECK(hipMemsetAsync(a.live, 0, sizeof(int32_t), h->stream));
+    AV_CHECK(beam_select(h->stream, a));
     return 0;
 }
 

@@ -55,9 +55,11 @@ __device__ __forceinline__ unsigned order_key(float x)
 // the k-th largest key (1 <= k <= number of keys) over the whole workgroup by a radix select, 4 passes of 8 bits from
 // the top: a 256-bin histogram in LDS of the keys that match the prefix found so far, then the bin in which the count
 // from the top reaches k.  each(f) calls f(key) for every key of THIS thread; sh: 258 words of LDS.  Every thread of
-// the workgroup must call it (barriers inside); all return the same key.
+// the workgroup must call it (barriers inside); all return the same key.  need / ties (optional, both or neither): how many keys
+// EQUAL to the result are among the k largest, and how many keys equal it (beam.hip breaks that tie by token); with them the call
+// ends in a barrier, so that sh is free again at once.
 template <class Each>
-__device__ __forceinline__ unsigned kth_largest_key(Each each, unsigned k, unsigned* sh)
+__device__ __forceinline__ unsigned kth_largest_key(Each each, unsigned k, unsigned* sh, unsigned* need = nullptr, unsigned* ties = nullptr)
 {
     const int tid = threadIdx.x, nth = blockDim.x;
     unsigned prefix = 0, mask = 0;
@@ -82,6 +84,7 @@ __device__ __forceinline__ unsigned kth_largest_key(Each each, unsigned k, unsig
         __syncthreads();
         prefix |= sh[256] << shift; mask |= 255u << shift; k = sh[257];
     }
+    if (need) { *need = k; *ties = sh[prefix & 255u]; __syncthreads(); }      // (the last pass' histogram: keys that share the top 24 bits, by their low 8)
     return prefix;
 }
 

@@ -40,6 +40,10 @@ class AvaeSampleConfig(C.Structure):
     _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64)]
 
 
+class AvaeBeamConfig(C.Structure):
+    _fields_ = [('width', C.c_int32), ('length_alpha', C.c_float)]
+
+
 class AvaeScoreConfig(C.Structure):
     _fields_ = [('k', C.c_int32), ('seed', C.c_uint64)]
 
@@ -73,6 +77,7 @@ SIGNATURES = {
     'avae_decode_step': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     'avae_decode_greedy': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'avae_decode_sample': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSampleConfig), _P, _P, C.POINTER(C.c_int32)]),
+    'avae_decode_beam': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeBeamConfig), _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     'avae_score': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AvaeScoreConfig), _P, _P, _P, _P, _P, _P]),
     'avae_score_z': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)
@@ -84,6 +89,7 @@ SIGNATURES = {
     'avae_debug_softmax_ce': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.POINTER(C.c_int)]),
     'avae_debug_argmax_rows': (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     'avae_debug_sample_rows': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AvaeSampleConfig), _P, _P]),
+    'avae_debug_beam_select': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     'avae_timing_collect': (C.c_int, [_P, C.POINTER(C.c_double)]),
     'avae_debug_timing': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),
     'avae_debug_train_ce': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32)]),

@@ -344,6 +344,39 @@ class VAE:
         ids = out[:, :n.value].cpu().numpy()
         return (ids, logp[:, :min(n.value + 1, steps)].cpu().numpy()) if return_logp else ids
 
+    def beam(self, z, steps=256, width=4, length_alpha=0.0, return_all=False):
+        """beam-search decoding (include/argsim_vae.h, avae_decode_beam): the `width` best continuations per sentence, ranked by
+        cum / len ** length_alpha.  By default array i32 (b, t<=steps): the best hypothesis of every row, trimmed as decode() trims.
+        With return_all a dict: ids (b, width, n) best first, score, cum (b, width) f32, len (b, width) i32 (tokens including the
+        closing eos of a finished hypothesis), n (steps the search ran) and the search lattice lat_parent, lat_token i32, lat_cum f32
+        (n, b, width), time-major, in search-slot order."""
+        steps, width, length_alpha = _check_beam_args(steps, width, length_alpha)
+        if width > self.cfg['dim_tgt']:
+            raise ValueError("width must be at most dim_tgt = %d, got %d" % (self.cfg['dim_tgt'], width))
+        z = torch.as_tensor(np.ascontiguousarray(z, dtype=np.float32)).to(self.device)
+        if z.dim() != 2 or z.shape[1] != self.cfg['dim_rep'] or z.shape[0] < 1:
+            raise ValueError("z must be (b, dim_rep) with b >= 1, got %s" % (tuple(z.shape),))
+        b = z.shape[0]
+        i32, f32 = dict(dtype=torch.int32, device=self.device), dict(dtype=torch.float32, device=self.device)
+        out = torch.empty((b, width, steps), **i32)
+        score = cum = ln = lp = lt = lc = None
+        if return_all:
+            score, cum, ln = torch.empty((b, width), **f32), torch.empty((b, width), **f32), torch.empty((b, width), **i32)
+            lp, lt, lc = torch.empty((steps, b, width), **i32), torch.empty((steps, b, width), **i32), torch.empty((steps, b, width), **f32)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        n = C.c_int32()
+        bc = _lib.AvaeBeamConfig(width, length_alpha)
+        self._stream()
+        self._ck(self._l.avae_decode_beam(self._h, ptr(z), b, steps, C.byref(bc), ptr(out), ptr(score), ptr(cum), ptr(ln), ptr(lp), ptr(lt),
+                                          ptr(lc), C.byref(n)))
+        n = n.value
+        if not return_all:
+            best = out[:, 0, :n].cpu().numpy()
+            m = int((best != self.eos).sum(1).max()) if best.size else 0        # (an unfinished best row keeps all n tokens)
+            return best[:, :m]
+        return dict(ids=out[:, :, :n].cpu().numpy(), score=score.cpu().numpy(), cum=cum.cpu().numpy(), len=ln.cpu().numpy(), n=n,
+                    lat_parent=lp[:n].cpu().numpy(), lat_token=lt[:n].cpu().numpy(), lat_cum=lc[:n].cpu().numpy())
+
     def generate(self, n, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
         """n sentences from the prior: z ~ N(0, I) drawn on the host with np.random.default_rng(seed), then sample() with the same seed"""
         if int(n) != n or n < 1:
@@ -426,6 +459,18 @@ def _check_sample_args(steps, temperature, top_k, seed):
     return int(steps), int(top_k), int(seed)
 
 
+def _check_beam_args(steps, width, length_alpha):
+    """the argument rules of avae_decode_beam, checked before anything touches the device -> (steps, width, length_alpha)"""
+    if isinstance(steps, bool) or int(steps) != steps or not 1 <= steps <= 1 << 20:
+        raise ValueError("steps must be an integer in [1, 2^20], got %r" % (steps,))
+    if isinstance(width, bool) or int(width) != width or not 1 <= width <= 32:
+        raise ValueError("width must be an integer in [1, 32], got %r" % (width,))
+    a = float(length_alpha)
+    if not (a >= 0.0) or a == float('inf'):
+        raise ValueError("length_alpha must be a finite number >= 0, got %r" % (length_alpha,))
+    return int(steps), int(width), a
+
+
 def vAe(mode, src=None, tgt=None, **cfg):
     """reference-shaped constructor (src/model.py:48): returns the VAE object in place of the Record.
     ``src``/``tgt`` pipeline tensors have no counterpart: batches are passed to the methods."""
@@ -445,6 +490,11 @@ def decode(vae, z, steps=256):
 def sample(vae, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
     """sampled counterpart of decode(): VAE.sample"""
     return vae.sample(z, steps, temperature, top_k, seed, return_logp)
+
+
+def beam(vae, z, steps=256, width=4, length_alpha=0.0, return_all=False):
+    """beam-search counterpart of decode(): VAE.beam"""
+    return vae.beam(z, steps, width, length_alpha, return_all)
 
 
 def score(vae, src, k=1, seed=0):

@@ -169,6 +169,42 @@ typedef struct avae_sample_config { float temperature; int32_t top_k; uint64_t s
 int  avae_decode_sample(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_config* sc,
                         int32_t* out_ids, float* logp_out, int32_t* n_steps);
 
+/* ---- beam-search decoding --------------------------------------------------------------- */
+/* The third decoder beside avae_decode_greedy and avae_decode_sample: the `width` best continuations per sentence, on the device,
+ * on the launch-per-token path (the b x width hypotheses are the decoder's batch rows).  For sentence r, step t (0-based) and the
+ * hypothesis in slot w, with l[w, v] the tied logits of src/model.py:166:
+ *   logp    logp[w, v] = l[w, v] - logsumexp_v l[w, .] in fp32, the maximum subtracted first: (l - max) - log(sum exp(l - max)).
+ *           Reductions run in a fixed order (a thread's own terms in index order, a wave by shuffles, a workgroup through LDS);
+ *           no float atomics: the same arguments give the same bits.
+ *   start   one hypothesis per sentence, [bos] with cum = 0 and the state of avae_decode_init; the other width - 1 slots do not
+ *           exist at step 0 (the first step selects among the V candidates of that one row).
+ *   cands   a live hypothesis w offers the V candidates (w, v) with cum[w] + logp[w, v]; a finished one (its last token is eos)
+ *           offers exactly one, itself: token eos, cum unchanged (the sampler's rule: a finished row emits eos with logp 0).
+ *   select  the `width` candidates largest under the total order (score descending, parent slot ascending, token ascending)
+ *           become slots 0 .. width - 1 in that order; a NaN sorts below -inf, as in the sampler's radix keys.  width == 1 takes
+ *           the first maximum of l itself, as temperature == 0 does in the sampler: ids are bit-equal to avae_decode_greedy up to
+ *           the row's first eos, and eos after it.
+ *   end     the loop ends after the first step at which every slot of every sentence is finished, or at `steps`; *n_steps is the
+ *           number of steps run.  The lattice beyond it is (parent = slot, token = eos, cum unchanged).
+ *   output  per sentence the final beam is re-ranked by score = cum / len^length_alpha (len^length_alpha evaluated in double on the
+ *           host and rounded to fp32, the division in fp32; length_alpha == 0: score = cum), ties to the lower slot, and
+ *           backtracked on the device into out_ids.  len counts the closing eos of a finished hypothesis; otherwise it is *n_steps.
+ *   groups  sentences are independent and go through the search in groups of at most floor(1024 / width): at most 1024 decoder
+ *           rows per step.  A finished group stops; *n_steps is the maximum over the groups.
+ * Errors (text through avae_last_error): a null bc, z or out_ids; b < 1, steps < 1, width < 1, width > 32, width > dim_tgt; a
+ * length_alpha that is negative or not finite; steps > 2^20; a lattice the device has no memory for (the call keeps 12 bytes x steps x
+ * min(b x width, 1024) of it in its scratch: 6 MB at steps 512, refused with the size named where the allocation fails).  */
+typedef struct avae_beam_config { int32_t width; float length_alpha; } avae_beam_config;
+int  avae_decode_beam(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_beam_config* bc,
+                      int32_t* out_ids,    /* (b, width, steps) int32 device, eos-padded, best first         */
+                      float*   score,      /* (b, width) optional: final score (above)                       */
+                      float*   cum,        /* (b, width) optional: raw sum of token log-probabilities        */
+                      int32_t* len,        /* (b, width) optional: tokens incl. the closing eos if it has one */
+                      int32_t* lat_parent, /* (steps, b, width) optional: the search lattice, time-major     */
+                      int32_t* lat_token,  /* (steps, b, width) optional                                     */
+                      float*   lat_cum,    /* (steps, b, width) optional                                     */
+                      int32_t* n_steps);   /* host: steps the search ran                                     */
+
 /* ---- importance-weighted sentence likelihood --------------------------------------------- */
 /* A K-sample importance-weighted bound on log p(tgt row) with the proposal q(z | src row), and its decoder half alone:
  * the teacher-forced log p(tgt row | z row) of sentences the caller supplies (the inverse of avae_decode_sample).
