@@ -545,6 +545,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn256_kernel(GemmBf16Args g)
     }
 }
 
+static int big_tile_count(const GemmArgs& g) { return ((g.M + T2 - 1) / T2) * ((g.N + T2 - 1) / T2); }
+
 // C (M x N) = alpha * A^T B (+ C): A [K][lda], B [K][ldb] bf16 row-major as their producers wrote them.  K split over
 // ~2 rounds of one workgroup per CU with float atomics INTO C (which must hold the value to add onto: the zero-filled
 // gradient) when g.split_k > 1, as gemm_bf16_nt re-derives it; g.dyn / dyn_kind 2: device-side K.
@@ -553,9 +555,7 @@ hipError_t gemm_bf16_tn(hipStream_t st, const unsigned short* A, int lda, const 
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     if ((lda | ldb | g.M | g.N) & 7 || g.dyn_kind == 1 || g.bias) return hipErrorInvalidValue;
     GemmBf16Args a{A, B, g.C, nullptr, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, g.split_k, g.dyn, g.dyn_kind};
-    const int big_tiles = ((g.M + T2 - 1) / T2) * ((g.N + T2 - 1) / T2);
-    int s2 = g.split_k > 1 ? (512 + big_tiles / 2) / big_tiles : 1;
-    s2 = std::max(1, std::min(std::min(s2, 16), std::max(1, g.K / (4 * BKH))));
+    const int big_tiles = big_tile_count(g), s2 = gemm_bf16_slices(g.split_k, big_tiles, g.K, BKH);
     if (gemm_bf16_p8_tn_ok(g, lda, ldb)) return gemm_bf16_p8_tn(st, A, lda, B, ldb, g, s2);
     static bool attr_done = false;
     if (!attr_done) {
@@ -572,9 +572,14 @@ hipError_t gemm_bf16_tn(hipStream_t st, const unsigned short* A, int lda, const 
 
 bool gemm_bf16_c16_ok(const GemmArgs& g, int lda, int ldb)
 {
-    const int big_tiles = ((g.M + T2 - 1) / T2) * ((g.N + T2 - 1) / T2);
-    return ((lda | ldb) & 7) == 0 && g.N >= 192 && g.M >= 192 && big_tiles >= 200 && g.split_k <= 1 && !g.bias && !g.accumulate && (g.N & 7) == 0 && (g.ldc & 7) == 0 &&
+    return ((lda | ldb) & 7) == 0 && gemm_bf16_big_fills(g.M, g.N, big_tile_count(g), 1) && g.split_k <= 1 && !g.bias && !g.accumulate && (g.N & 7) == 0 && (g.ldc & 7) == 0 &&
            gemm_bf16_p8_ok(g, lda, ldb);
+}
+bool gemm_bf16_c16_takes(int M, int N, int K, const int* rows, int nt8)
+{
+    GemmArgs probe{nullptr, nullptr, nullptr, nullptr, M, N, K, K, K, N, 1.f, 0, 1, rows, rows ? 1 : 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    probe.nt8 = nt8;
+    return (K & 7) == 0 && gemm_bf16_c16_ok(probe, K, K);
 }
 
 // operands already converted: A [M][lda] bf16, B [N][ldb] bf16, lda/ldb multiples of 8
@@ -584,12 +589,9 @@ hipError_t gemm_bf16_nt(hipStream_t st, const unsigned short* A, int lda, const 
     if ((lda | ldb) & 7) return hipErrorInvalidValue;
     if (g.c16 && !gemm_bf16_c16_ok(g, lda, ldb)) return hipErrorInvalidValue;      // (only the phased kernel writes the 2-byte panel: the caller asks first)
     GemmBf16Args a{A, B, g.C, g.bias, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, g.split_k, g.dyn, g.dyn_kind};
-    // large tiles where they fill the chip, by themselves or through the K split (a caller's split was sized for 128x128
-    // tiles at three workgroups per CU; here one workgroup per CU, so it is re-derived: ~2 rounds of 256 workgroups)
-    const int big_tiles = ((g.M + T2 - 1) / T2) * ((g.N + T2 - 1) / T2);
-    int s2 = g.split_k > 1 ? (512 + big_tiles / 2) / big_tiles : 1;
-    s2 = std::max(1, std::min(std::min(s2, 16), std::max(1, g.K / (4 * BKH))));      // (more slices: the float atomics dominate)
-    if (g.N >= 192 && g.M >= 192 && big_tiles * s2 >= 200) {
+    // large tiles where they fill the chip, by themselves or through the K split (re-derived for them: gemm_bf16_slices)
+    const int big_tiles = big_tile_count(g), s2 = gemm_bf16_slices(g.split_k, big_tiles, g.K, BKH);
+    if (gemm_bf16_big_fills(g.M, g.N, big_tiles, s2)) {
         if (gemm_bf16_p8_ok(g, lda, ldb)) return gemm_bf16_p8(st, A, lda, B, ldb, g, s2);
         static bool attr_done = false;
         if (!attr_done) {

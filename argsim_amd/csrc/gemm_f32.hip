@@ -12,6 +12,7 @@
 // a k-contiguous operand row then feeds four consecutive steps from ONE ds_read_b128.
 #include "kernels.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace avae {
 
@@ -477,6 +478,16 @@ static void launch_skinny(hipStream_t st, bool b_nc, const GemmArgs& g)
     else      hipLaunchKernelGGL(gemm_f32_skinny_kernel<false>, grid, dim3(512), 0, st, g);
 }
 
+// (a_mc, b_nc) -> the kernel instantiation of those operand layouts: f(A, B) is called once, with A / B a std::true_type or std::false_type
+template <class F>
+static void with_layouts(bool a_mc, bool b_nc, F&& f)
+{
+    if (!a_mc && !b_nc)      f(std::false_type{}, std::false_type{});
+    else if (!a_mc && b_nc)  f(std::false_type{}, std::true_type{});
+    else if (a_mc && b_nc)   f(std::true_type{}, std::true_type{});
+    else                     f(std::true_type{}, std::false_type{});
+}
+
 template <int WM, int WN, int TM, int TN>
 static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g)
 {
@@ -503,10 +514,7 @@ static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs&
         const bool persist = (ps_env ? atoi(ps_env) != 0 : true) && allow_fast && aligned && !g.A2 && g.split_k <= 1 && g.dyn_kind != 2 && tiles > 1024;
         if (persist) {
             dim3 pg(768);
-            if (!a_mc && !b_nc)      hipLaunchKernelGGL((gemm_f32_persist_kernel<false, false, true>), pg, dim3(256), 0, st, g);
-            else if (!a_mc && b_nc)  hipLaunchKernelGGL((gemm_f32_persist_kernel<false, true, true>), pg, dim3(256), 0, st, g);
-            else if (a_mc && b_nc)   hipLaunchKernelGGL((gemm_f32_persist_kernel<true, true, true>), pg, dim3(256), 0, st, g);
-            else                     hipLaunchKernelGGL((gemm_f32_persist_kernel<true, false, true>), pg, dim3(256), 0, st, g);
+            with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_persist_kernel<decltype(A)::value, decltype(B)::value, true>), pg, dim3(256), 0, st, g); });
             return;
         }
     }
@@ -517,30 +525,18 @@ static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs&
         const bool use_db = db_env ? atoi(db_env) != 0 && !g.A2 : (!g.A2 && g.split_k <= 1 && eff_tiles > 768 && tiles <= 1024);
         if (use_db) {
             if (fast) {
-                if (!a_mc && !b_nc)      hipLaunchKernelGGL((gemm_f32_kernel<false, false, WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, g);
-                else if (!a_mc && b_nc)  hipLaunchKernelGGL((gemm_f32_kernel<false, true, WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, g);
-                else if (a_mc && b_nc)   hipLaunchKernelGGL((gemm_f32_kernel<true, true, WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, g);
-                else                     hipLaunchKernelGGL((gemm_f32_kernel<true, false, WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, g);
+                with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, g); });
             } else {
-                if (!a_mc && !b_nc)      hipLaunchKernelGGL((gemm_f32_kernel<false, false, WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, g);
-                else if (!a_mc && b_nc)  hipLaunchKernelGGL((gemm_f32_kernel<false, true, WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, g);
-                else if (a_mc && b_nc)   hipLaunchKernelGGL((gemm_f32_kernel<true, true, WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, g);
-                else                     hipLaunchKernelGGL((gemm_f32_kernel<true, false, WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, g);
+                with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, g); });
             }
             return;
         }
     }
     if (fast) {
-        if (!a_mc && !b_nc)      hipLaunchKernelGGL((gemm_f32_kernel<false, false, WM, WN, TM, TN, true>), grid, dim3(256), 0, st, g);
-        else if (!a_mc && b_nc)  hipLaunchKernelGGL((gemm_f32_kernel<false, true, WM, WN, TM, TN, true>), grid, dim3(256), 0, st, g);
-        else if (a_mc && b_nc)   hipLaunchKernelGGL((gemm_f32_kernel<true, true, WM, WN, TM, TN, true>), grid, dim3(256), 0, st, g);
-        else                     hipLaunchKernelGGL((gemm_f32_kernel<true, false, WM, WN, TM, TN, true>), grid, dim3(256), 0, st, g);
+        with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN, true>), grid, dim3(256), 0, st, g); });
         return;
     }
-    if (!a_mc && !b_nc)      hipLaunchKernelGGL((gemm_f32_kernel<false, false, WM, WN, TM, TN>), grid, dim3(256), 0, st, g);
-    else if (!a_mc && b_nc)  hipLaunchKernelGGL((gemm_f32_kernel<false, true, WM, WN, TM, TN>), grid, dim3(256), 0, st, g);
-    else if (a_mc && b_nc)   hipLaunchKernelGGL((gemm_f32_kernel<true, true, WM, WN, TM, TN>), grid, dim3(256), 0, st, g);
-    else                     hipLaunchKernelGGL((gemm_f32_kernel<true, false, WM, WN, TM, TN>), grid, dim3(256), 0, st, g);
+    with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN>), grid, dim3(256), 0, st, g); });
 }
 
 hipError_t gemm_f32(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g)

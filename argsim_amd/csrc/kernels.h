@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"
+
 namespace avae {
 
 // ---------------------------------------------------------------- GEMM (gemm_f32.hip)
@@ -54,6 +56,8 @@ bool gemm_bf16_p8_ok(const GemmArgs& g, int lda, int ldb);
 hipError_t gemm_bf16_p8(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g, int s2);
 // would gemm_bf16_nt run this problem on the phased kernel (the only one that writes GemmArgs::c16)?
 bool gemm_bf16_c16_ok(const GemmArgs& g, int lda, int ldb);
+// the same question from the shape alone: A (M, K), B (N, K) fp32 k-contiguous with K % 8 == 0, C (M, N), rows: the device-side row count or null
+bool gemm_bf16_c16_takes(int M, int N, int K, const int* rows, int nt8);
 // ... and of gemm_bf16_tn's contract (operands [k][x] row-major, K host- or device-side, any K)
 bool gemm_bf16_p8_tn_ok(const GemmArgs& g, int lda, int ldb);
 hipError_t gemm_bf16_p8_tn(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g, int s2);

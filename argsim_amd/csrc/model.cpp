@@ -57,7 +57,6 @@ struct avae_ctx {
                           // K split over its waves (gemm_f32.hip); 0: the tiled forms
     int score_plan[4] = {0, 0, 0, 0};      // last avae_score / avae_score_z: decoder batch size N, rows rc and draws kc per batch, batches whose draws shared one first-layer projection through a row index
     const int* expect_ptr[3] = {nullptr, nullptr, nullptr}; int expect_val[3] = {0, 0, 0};      // (dyn_expected)
-    int rows_form = 0;    // one-shot: the next gemm() call's rows are the batch rows -- skinny form whatever the batch size (see gemm)
     int compact = 2;      // encoder activations stored over the REAL rows only (row_map / GruArgs::rowmap): padded rows of a ragged batch cost nothing in the
                           // encoder's GEMMs.  0 off, 1 on, 2 auto: on where the share of real positions the previous calls reported is below 0.85 (fill_hint)
     int skip_pad = 1;     // team GRU kernels skip the steps behind a row block's longest row (rows sorted by length, ops.hip row_order); 0: every step of every row
@@ -98,7 +97,6 @@ struct avae_ctx {
     // bf16-operand GEMM mode (compute_dtype = 1): converted operand panels
     unsigned short *bfA = nullptr, *bfB = nullptr; size_t bfA_cap = 0, bfB_cap = 0;
     float* slab = nullptr; size_t slab_floats = 0;     // bf16 mode: the K slices' partial tiles of the weight-gradient GEMMs (gemm_bf16_p8.hip; 512 tiles of 256 x 256)
-    unsigned short* keep_a16 = nullptr;       // one-shot: the next bf16-mode GEMM converts its (k-contiguous) A operand HERE and leaves it for the backward (gemm_raw)
     unsigned short* bfP = nullptr; size_t bfP_cap = 0;     // bf16 mode: (softmax - onehot)/N as written by softmax_ce_kernel, (N,V) bf16
     // (dyn / dyn_max: a GEMM whose M or K is a device-side count -- its FLOPs are scaled by count / static bound at collection)
     struct Stamp { hipEvent_t a, b; int cls; double flops; const int* dyn; int dyn_max; };
@@ -360,94 +358,191 @@ static int dyn_expected(const avae_ctx* h, const int* dyn, int dyn_kind)
     for (int i = 0; i < 3; ++i) if (dyn == h->expect_ptr[i]) return h->expect_val[i];
     return 0;
 }
+// h->scratch is ONE buffer shared by get / set_tensor staging, the greedy and sampled loops, the beam search and its debug hook: every
+// user lays it out afresh per call and all work is ordered on the handle's stream, so no call sees another's data.
+int grow_scratch(avae_ctx* h, size_t need, const char* what)
+{
+    if (h->scratch_n >= (int64_t)need) return 0;
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    if (h->scratch) AV_CHECK(hipFree(h->scratch));
+    h->scratch = nullptr; h->scratch_n = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&h->scratch), need) != hipSuccess) {
+        (void)hipGetLastError();
+        h->scratch = nullptr;
+        char b_[256]; snprintf(b_, sizeof b_, "%s: %.0f MB of scratch could not be allocated on the device", what, (double)need / 1048576.0);
+        return fail(h, b_);
+    }
+    h->scratch_n = (int64_t)need;
+    return 0;
+}
+
 // second problem of a pair (same shape, layout, scalars): see GemmArgs in kernels.h
 struct Pair { const float* A; const float* B; float* C; const float* bias; };
 
-int gemm_raw(avae_ctx* h, bool a_mc, bool b_nc, const float* A, int lda, const float* Bm, int ldb, float* C, int ldc,
-             int M, int N, int K, float alpha, const float* bias, int accumulate, int split_k, const int* dyn, int dyn_kind,
-             int thin = 0, const Pair* pair = nullptr, unsigned short* c16 = nullptr)
+// One GEMM product as a value: C = alpha * op(A) op(B) (+bias) (+C), layouts as in GemmArgs (kernels.h).  Built by nt() / nn() / tn_grad()
+// and the setters below; gemm() takes its launches from gemm_plan() (gemm_plan.cpp), which sees the shape, the flags here and the options.
+struct GemmCall {
+    const float* A; int lda; bool a_mc;
+    const float* B; int ldb; bool b_nc;
+    float* C; int ldc;
+    int M, N, K;
+    float alpha = 1.f; const float* bias = nullptr; int accumulate = 0;
+    const int* dyn = nullptr; int dyn_kind = 0;      // device-side count: 1 the rows (M), 2 the depth (K)
+    const Pair* pair = nullptr;
+    bool wgrad = false;                 // weight gradient: C holds the zero-filled gradient (tn_grad)
+    bool allow_atomic = false;          // backward: the plan may split K with float atomics into the cleared output
+    bool rows_are_batch = false;        // forward: the rows are the batch rows -- the skinny form whatever the batch size (gemm_plan)
+    int thin = -1, split_k = 0;         // a caller's own tile form (GemmArgs::thin) / K split; -1 / 0: the plan's
+    // bf16 mode only
+    const unsigned short* A16 = nullptr; const unsigned short* B16 = nullptr;      // the operand as a producer wrote it in bf16, row-major with the same leading dimension (gemm_bf16_pre, gemm_tn16)
+    unsigned short* keep_a16 = nullptr; // the k-contiguous A operand is converted HERE and left for the backward's weight-gradient GEMM
+    unsigned short* c16 = nullptr;      // GemmArgs::c16: the result as an fp16 panel instead of C
+
+    GemmCall& scaled(float a) { alpha = a; return *this; }
+    GemmCall& biased(const float* b) { bias = b; return *this; }
+    GemmCall& plus() { accumulate = 1; return *this; }
+    GemmCall& rows(const int* d) { dyn = d; dyn_kind = d ? 1 : 0; return *this; }
+    GemmCall& depth(const int* d) { dyn = d; dyn_kind = d ? 2 : 0; return *this; }
+    GemmCall& with(const Pair* p) { pair = p; return *this; }
+    GemmCall& atomic() { allow_atomic = true; return *this; }
+    GemmCall& batch_rows() { rows_are_batch = true; return *this; }
+    GemmCall& form(int thin_, int split_k_ = 1) { thin = thin_; split_k = split_k_; return *this; }
+    GemmCall& a16(const unsigned short* p) { A16 = p; return *this; }
+    GemmCall& b16(const unsigned short* p) { B16 = p; return *this; }
+    GemmCall& keep(unsigned short* p) { keep_a16 = p; return *this; }
+};
+// C (M x N) = A B^T: A (M, K) and B (N, K), both k-contiguous
+GemmCall nt(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K) { return GemmCall{A, lda, false, B, ldb, false, C, ldc, M, N, K}; }
+// C (M x N) = A B: A (M, K), B (K, N)
+GemmCall nn(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K) { return GemmCall{A, lda, false, B, ldb, true, C, ldc, M, N, K}; }
+// dW (M x N) += A^T B over K rows: A (K, M), B (K, N); the gradients are zero-filled beforehand
+GemmCall tn_grad(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K)
 {
-    if (pair && h->cfg.compute_dtype != 0) {     // the other GEMM kernels take one problem per launch
-        AV_TRY(gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, split_k, dyn, dyn_kind, thin));
-        return gemm_raw(h, a_mc, b_nc, pair->A, lda, pair->B, ldb, pair->C, ldc, M, N, K, alpha, pair->bias, accumulate, split_k, dyn, dyn_kind, thin);
+    GemmCall c{A, lda, true, B, ldb, true, C, ldc, M, N, K};
+    c.wgrad = true;
+    return c;
+}
+
+GemmShape gemm_shape(const avae_ctx* h, const GemmCall& c)
+{
+    return GemmShape{c.a_mc, c.b_nc, c.M, c.N, c.K, c.ldc, c.accumulate, c.split_k, c.thin, c.dyn_kind, dyn_expected(h, c.dyn, c.dyn_kind),
+                     c.allow_atomic, c.rows_are_batch, c.pair != nullptr, c.wgrad, h->cfg.compute_dtype, h->skinny != 0, h->dyn_split != 0, h->dyn_thin != 0};
+}
+// the one launch of a product the bf16-operand paths below shape themselves (gemm_bf16_nt / gemm_bf16_tn re-derive the K split): a
+// weight gradient takes its split from the plan, anything else runs as it stands
+GemmLaunch bf16_launch(const avae_ctx* h, const GemmCall& c)
+{
+    if (!c.wgrad) return GemmLaunch{0, c.M, 0, 1, c.accumulate, kZeroNone, c.dyn_kind ? 1 : 0};
+    GemmShape s = gemm_shape(h, c);
+    s.compute_dtype = 1;
+    return gemm_plan(s).launch[0];
+}
+
+// one launch of a plan: rows [l.row0, l.row0 + l.rows) of the call on the GEMM kernels of the handle's compute_dtype
+int gemm_launch(avae_ctx* h, const GemmCall& c, const GemmLaunch& l)
+{
+    if (c.pair && h->cfg.compute_dtype != 0) {     // the other GEMM kernels take one problem per launch
+        GemmCall one = c, two = c;
+        one.pair = two.pair = nullptr; two.keep_a16 = nullptr;
+        two.A = c.pair->A; two.B = c.pair->B; two.C = c.pair->C; two.bias = c.pair->bias;
+        AV_TRY(gemm_launch(h, one, l));
+        return gemm_launch(h, two, l);
     }
-    GemmArgs g{A, Bm, C, bias, M, N, K, lda, ldb, ldc, alpha, accumulate, split_k, dyn, dyn_kind, dyn_expected(h, dyn, dyn_kind), thin,
+    const float* A = c.A + (size_t)l.row0 * c.lda; float* C = c.C + (size_t)l.row0 * c.ldc;      // (row0 > 0: k-contiguous A only, gemm_plan)
+    const int M = l.rows, N = c.N, K = c.K;
+    const int* dyn = l.dyn ? c.dyn : nullptr; const int dyn_kind = l.dyn ? c.dyn_kind : 0;
+    const Pair* pair = c.pair;
+    GemmArgs g{A, c.B, C, c.bias, M, N, K, c.lda, c.ldb, c.ldc, c.alpha, l.accumulate, l.split_k, dyn, dyn_kind, dyn_expected(h, dyn, dyn_kind), l.thin,
                pair ? pair->A : nullptr, pair ? pair->B : nullptr, pair ? pair->C : nullptr, pair ? pair->bias : nullptr};
     Timed t(h, 0, 2.0 * M * N * K * (pair ? 2 : 1), dyn, dyn_kind == 1 ? M : (dyn_kind == 2 ? K : 0));
     if (h->cfg.compute_dtype == 1 && h->bf16_direct) {
         // bf16 operands rounded on the way into LDS, straight from the fp32 operands in whatever layout: no conversion passes
-        AV_CHECK(gemm_bf16_direct(h->stream, a_mc, b_nc, g));
+        AV_CHECK(gemm_bf16_direct(h->stream, c.a_mc, c.b_nc, g));
         return 0;
     }
     if (h->cfg.compute_dtype == 1) {
         // bf16 operands: convert (transposing [k][x] operands) into k-contiguous panels, then one NT kernel
         const int Kp = (K + 7) & ~7;
         unsigned short* a16 = nullptr;
-        if (h->keep_a16 && !a_mc && Kp == K) { a16 = h->keep_a16; }      // a layer input: its bf16 copy [M][K] stays for the weight-gradient GEMM of the backward
-        h->keep_a16 = nullptr;
+        if (c.keep_a16 && !c.a_mc && Kp == K) a16 = c.keep_a16 + (size_t)l.row0 * K;      // a layer input: its bf16 copy [M][K] stays for the weight-gradient GEMM of the backward
         if (!a16) { AV_TRY(grow_bf16(h, &h->bfA, &h->bfA_cap, (size_t)M * Kp)); a16 = h->bfA; }
         AV_TRY(grow_bf16(h, &h->bfB, &h->bfB_cap, (size_t)N * Kp));
-        AV_CHECK(cvt_bf16(h->stream, A, lda, a_mc, a_mc ? K : M, a_mc ? M : K, a16, Kp));
-        AV_CHECK(cvt_bf16(h->stream, Bm, ldb, b_nc, b_nc ? K : N, b_nc ? N : K, h->bfB, Kp));
+        AV_CHECK(cvt_bf16(h->stream, A, c.lda, c.a_mc, c.a_mc ? K : M, c.a_mc ? M : K, a16, Kp));
+        AV_CHECK(cvt_bf16(h->stream, c.B, c.ldb, c.b_nc, c.b_nc ? K : N, c.b_nc ? N : K, h->bfB, Kp));
         g.nt8 = h->bf16_nt8;
-        g.c16 = c16;
+        g.c16 = c.c16;
         AV_CHECK(gemm_bf16_nt(h->stream, a16, Kp, h->bfB, Kp, g));
         return 0;
     }
-    if (c16) return fail(h, "the fp16 output panel exists in compute_dtype 1 only");
+    if (c.c16) return fail(h, "the fp16 output panel exists in compute_dtype 1 only");
     // compute_dtype 2: fp32 operands split into 3 x bf16 on the fly (6 partial products, fp32-accurate); thin
     // row panels (a few rows, little work) stay on the exact-fp32 kernel's 32x128 tiles
-    if (h->cfg.compute_dtype == 2 && !thin) AV_CHECK(gemm_f32s(h->stream, a_mc, b_nc, g));
-    else AV_CHECK(gemm_f32(h->stream, a_mc, b_nc, g));
+    if (h->cfg.compute_dtype == 2 && !l.thin) AV_CHECK(gemm_f32s(h->stream, c.a_mc, c.b_nc, g));
+    else AV_CHECK(gemm_f32(h->stream, c.a_mc, c.b_nc, g));
     return 0;
 }
 
-// bf16 mode, A already bf16 and row-major ((rows, lda16), written by the producer -- the softmax gradient): as the A panel
-// itself (a_mc = false: k-contiguous) or transposed once from the 2-byte source (a_mc = true); B converted as usual.
-int gemm_bf16_pre(avae_ctx* h, const unsigned short* A16, int lda16, bool a_mc, const float* Bm, int ldb, bool b_nc, float* C, int ldc,
-                  int M, int N, int K, float alpha, int accumulate, int split_k, const int* dyn, int dyn_kind, const float* bias = nullptr)
+// the product as gemm_plan() shapes it: per launch, clear what the plan asks for, then launch
+int gemm(avae_ctx* h, const GemmCall& c)
 {
-    GemmArgs g{nullptr, Bm, C, bias, M, N, K, lda16, ldb, ldc, alpha, accumulate, split_k, dyn, dyn_kind, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    Timed t(h, 0, 2.0 * M * N * K, dyn, dyn_kind == 1 ? M : (dyn_kind == 2 ? K : 0));
+    const GemmPlan p = gemm_plan(gemm_shape(h, c));
+    for (int i = 0; i < p.n; ++i) {
+        const GemmLaunch& l = p.launch[i];
+        float* C = c.C + (size_t)l.row0 * c.ldc;
+        if (l.zero == kZeroAll) AV_CHECK(zero_fill(h->stream, C, sizeof(float) * (size_t)l.rows * c.N));
+        if (l.zero == kZeroDynRows) AV_CHECK(zero_rows_dyn(h->stream, C, c.dyn, l.rows, c.N));
+        AV_TRY(gemm_launch(h, c, l));
+    }
+    return 0;
+}
+
+// bf16 mode, A already bf16 and row-major (c.A16: (rows, lda), written by the producer -- the softmax gradient, a layer's h): as the A
+// panel itself (a_mc = false: k-contiguous) or transposed once from the 2-byte source (a_mc = true); B converted as usual.
+int gemm_bf16_pre(avae_ctx* h, const GemmCall& c)
+{
+    const GemmLaunch l = bf16_launch(h, c);
+    const int M = c.M, N = c.N, K = c.K;
+    GemmArgs g{nullptr, c.B, c.C, c.bias, M, N, K, c.lda, c.ldb, c.ldc, c.alpha, l.accumulate, l.split_k, c.dyn, c.dyn_kind, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    Timed t(h, 0, 2.0 * M * N * K, c.dyn, c.dyn_kind == 1 ? M : (c.dyn_kind == 2 ? K : 0));
     const int Kp = (K + 7) & ~7;
-    const unsigned short* Ap = A16; int lda_p = lda16;
-    if (a_mc) {
+    const unsigned short* Ap = c.A16; int lda_p = c.lda;
+    if (c.a_mc) {
         AV_TRY(grow_bf16(h, &h->bfA, &h->bfA_cap, (size_t)M * Kp));
-        AV_CHECK(transpose_bf16(h->stream, A16, lda16, K, M, h->bfA, Kp));
+        AV_CHECK(transpose_bf16(h->stream, c.A16, c.lda, K, M, h->bfA, Kp));
         Ap = h->bfA; lda_p = Kp;
     }
     AV_TRY(grow_bf16(h, &h->bfB, &h->bfB_cap, (size_t)N * Kp));
-    AV_CHECK(cvt_bf16(h->stream, Bm, ldb, b_nc, b_nc ? K : N, b_nc ? N : K, h->bfB, Kp));
+    AV_CHECK(cvt_bf16(h->stream, c.B, c.ldb, c.b_nc, c.b_nc ? K : N, c.b_nc ? N : K, h->bfB, Kp));
     g.nt8 = h->bf16_nt8;
     AV_CHECK(gemm_bf16_nt(h->stream, Ap, lda_p, h->bfB, Kp, g));
     return 0;
 }
 
-int grad_split(int M, int N, int K);
 // bf16 mode, weight gradient C (M x N) += alpha * A^T B over K rows with BOTH operands row-major [k][x]: bf16 as a producer
-// wrote them (A16 / B16) or fp32 converted row by row (no transpose); the GEMM reads them through transposing LDS loads
-// (gemm_bf16_tn).  C holds the zero-filled gradient; dynk: device-side K.
-int gemm_tn16(avae_ctx* h, const unsigned short* A16, const float* A32, int lda, const unsigned short* B16, const float* B32, int ldb,
-              float* C, int ldc, int M, int N, int K, float alpha, const int* dynk)
+// wrote them (c.A16 / c.B16) or fp32 converted row by row (c.A / c.B, no transpose); the GEMM reads them through transposing LDS
+// loads (gemm_bf16_tn).  C holds the zero-filled gradient; c.dyn: device-side K.
+int gemm_tn16(avae_ctx* h, const GemmCall& c)
 {
-    const int s = grad_split(M, N, K);
-    GemmArgs g{nullptr, nullptr, C, nullptr, M, N, K, lda, ldb, ldc, alpha, s > 1 ? 0 : 1, s, dynk, dynk ? 2 : 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    Timed t(h, 0, 2.0 * M * N * K, dynk, dynk ? K : 0);
-    int la = lda, lb = ldb;
+    const GemmLaunch l = bf16_launch(h, c);
+    const int M = c.M, N = c.N, K = c.K;
+    GemmArgs g{nullptr, nullptr, c.C, nullptr, M, N, K, c.lda, c.ldb, c.ldc, c.alpha, l.accumulate, l.split_k, c.dyn, c.dyn_kind, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    Timed t(h, 0, 2.0 * M * N * K, c.dyn, c.dyn ? K : 0);
+    const unsigned short* A16 = c.A16; const unsigned short* B16 = c.B16;
+    int la = c.lda, lb = c.ldb;
     if (!A16) {
         la = (M + 7) & ~7;
         AV_TRY(grow_bf16(h, &h->bfA, &h->bfA_cap, (size_t)K * la));
-        AV_CHECK(cvt_bf16(h->stream, A32, lda, false, K, M, h->bfA, la));
+        AV_CHECK(cvt_bf16(h->stream, c.A, c.lda, false, K, M, h->bfA, la));
         A16 = h->bfA;
     }
     if (!B16) {
         lb = (N + 7) & ~7;
         AV_TRY(grow_bf16(h, &h->bfB, &h->bfB_cap, (size_t)K * lb));
-        AV_CHECK(cvt_bf16(h->stream, B32, ldb, false, K, N, h->bfB, lb));
+        AV_CHECK(cvt_bf16(h->stream, c.B, c.ldb, false, K, N, h->bfB, lb));
         B16 = h->bfB;
     }
     g.nt8 = h->bf16_nt8;
-    if (h->bf16_nt8 && s > 1) {
+    if (h->bf16_nt8 && l.split_k > 1) {
         if (!h->slab) {
             const size_t n = (size_t)512 << 16;
             AV_CHECK(hipMalloc(reinterpret_cast<void**>(&h->slab), n * sizeof(float)));
@@ -458,135 +553,7 @@ int gemm_tn16(avae_ctx* h, const unsigned short* A16, const float* A32, int lda,
     AV_CHECK(gemm_bf16_tn(h->stream, A16, la, B16, lb, g));
     return 0;
 }
-static bool tn16_ok(const avae_ctx* h, int M, int N) { return h->cfg.compute_dtype == 1 && h->bf16_tn && ((M | N) & 7) == 0 && (size_t)M * N >= (size_t)1 << 19; }
-
-// C = alpha * op(A) op(B) (+bias) with launch shaping for the 256-CU chip (k-contiguous A only):
-//  * thin outputs (M <= 512): 32x128 block tiles so that the few rows still spread over many CUs;
-//    where float atomics are acceptable (backward) a long K is split over ~768 workgroups instead;
-//  * a tile count just above a multiple of 256 (M = 65*256 rows -> 130 row tiles): the rows that make
-//    whole rounds of 256 tiles run as one launch and the thin remainder as 32x128 tiles, instead of a
-//    few CUs carrying an extra full tile while the rest idle.
-// Both forward forms are deterministic (no atomics): z and the per-token losses stay bit-reproducible.
-int gemm(avae_ctx* h, bool a_mc, bool b_nc, const float* A, int lda, const float* Bm, int ldb, float* C, int ldc,
-         int M, int N, int K, float alpha = 1.f, const float* bias = nullptr, int accumulate = 0, int split_k = 0,
-         const int* dyn = nullptr, int dyn_kind = 0, bool allow_atomic = false)
-{
-    const int mt = (M + 127) / 128, nt = (N + 127) / 128, tiles = mt * nt;
-    unsigned short* const keep = h->keep_a16;           // (bf16 mode: where the converted A operand is to stay, see gemm_raw)
-    if (split_k != 0 || a_mc || dyn_kind == 2)
-        return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, split_k ? split_k : 1, dyn, dyn_kind);
-    // The skinny form (gemm_f32.hip: one 32x32 tile per workgroup, K split over its waves) sums K in another order than the tiled
-    // kernels, so WHICH form a forward product takes must not depend on the batch: z and the per-token losses of a row are the
-    // same bits in a batch of 16 and of 1024 (test_large_batch_rows_are_independent).  Forward: only the call sites whose rows
-    // are the batch rows themselves ask for it (rows_form), for every batch size.  Backward (allow_atomic: the gradients carry
-    // float-atomic order anyway): a few rows over a moderate K take it instead of a zero fill + split-K atomics.
-    const bool rows_form = h->rows_form != 0; h->rows_form = 0;
-    if (rows_form && h->skinny && h->cfg.compute_dtype != 1 && !a_mc && split_k == 0 && dyn_kind == 0)
-        return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, 1, nullptr, 0, 3);
-    // Ragged batches (compact layout: the host knows roughly how many rows are real): a backward GEMM with a narrow output whose real rows
-    // make fewer 128x128 tiles than the chip has CUs (dho = dlogits E over 7.4 k of 16.6 k token rows: 232 tiles, ONE workgroup per CU,
-    // 105 TFLOP/s) splits K over ~768 workgroups instead (float atomics into the zero-filled output: the gradients carry that order anyway).
-    // The expectation only shapes the launch; rows beyond the device-side count are never touched either way.
-    if (allow_atomic && h->dyn_split && dyn_kind == 1 && !accumulate && ldc == N && h->cfg.compute_dtype == 0 && K >= 1536) {
-        const int expect = dyn_expected(h, dyn, dyn_kind);
-        if (expect > 0) {
-            const int eff_tiles = ((expect + 127) / 128) * nt;
-            const int sk = std::min(768 / std::max(eff_tiles, 1), K / 512);
-            if (eff_tiles <= 320 && sk >= 2) {
-                AV_CHECK(zero_rows_dyn(h->stream, C, dyn, M, N));
-                return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, 0, sk, dyn, dyn_kind);
-            }
-        }
-    }
-    const bool prefer_skinny = allow_atomic && h->skinny && M <= 512 && K <= 2048 && h->cfg.compute_dtype != 1;
-    const int thin_form = (allow_atomic && h->skinny) ? 3 : 1;
-    if (tiles <= 96) {
-        if (allow_atomic && !accumulate && ldc == N && K >= 512 && !prefer_skinny) {
-            int s = std::min(768 / tiles, K / 128);
-            if (s >= 2) {
-                AV_CHECK(zero_fill(h->stream, C, sizeof(float) * (size_t)M * N));
-                return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, 0, s, dyn, dyn_kind);
-            }
-        }
-        if (M <= 512)
-            return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, 1, dyn, dyn_kind, thin_form);      // (3: the skinny form where it applies, else 32x128 tiles)
-    }
-    // A GEMM whose row count is only known on the device (the ids present in the batch: about V / 2 of the static bound
-    // of V rows) with a narrow output: 128x128 tiles over the rows that exist are fewer than one round of the chip (dE of
-    // the table-fed layers: 112 tiles for 768 slots, 49 TFLOP/s).  64x64 tiles: four times the tiles, deterministic.
-    if (h->dyn_thin && dyn_kind == 1 && h->cfg.compute_dtype == 0 && nt <= 4 && tiles <= 512 && K >= 1024) {
-        // (backward -- dE of the present ids, K = 3D or 6D: the K range split over 2-4 slices as well, float atomics into the zeroed rows:
-        //  3 584 x 512 x 3 072: 113 -> 96 us; fewer present ids, a ragged batch: more)
-        const int sk = std::min(4, K / 768);
-        if (allow_atomic && h->dyn_split && !accumulate && ldc == N && sk >= 2) {
-            AV_CHECK(zero_rows_dyn(h->stream, C, dyn, M, N));
-            return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, 0, sk, dyn, dyn_kind, 2);
-        }
-        return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, 1, dyn, dyn_kind, 2);
-    }
-    // The forward projection of the present target ids (static bound V rows x 3D: 768 tiles of 128x128, about 40 % of them real): 32x128
-    // tiles fill the chip with the rows that exist (78 -> 54 us; the encoder's, 1536 static tiles, is faster on 128x128).  Any tile
-    // form keeps a row's K order: the bits of gi do not move.
-    if (h->dyn_thin && dyn_kind == 1 && h->cfg.compute_dtype == 0 && tiles <= 768 && nt > 4 && K <= 512 && !accumulate)
-        return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, 1, dyn, dyn_kind, 1);
-    if (tiles > 256 && tiles % 256 != 0) {
-        int main_mt = mt;
-        while (main_mt > 0 && (main_mt * nt) % 256 != 0) --main_mt;
-        const int tail_tiles = (mt - main_mt) * nt;
-        const double frac = (double)tiles / 256.0;
-        if (main_mt > 0 && tail_tiles < 200 && (std::ceil(frac) - frac) >= 0.3) {
-            const int main_rows = main_mt * 128, tail_rows = M - main_rows;
-            AV_TRY(gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, main_rows, N, K, alpha, bias, accumulate, 1, dyn, dyn_kind));
-            // rows beyond the device-side row count hold unread garbage either way: the tail keeps the static bound
-            const float* At = A + (size_t)main_rows * lda; float* Ct = C + (size_t)main_rows * ldc;
-            if (keep) h->keep_a16 = keep + (size_t)main_rows * K;
-            if (allow_atomic && !accumulate && ldc == N && K >= 1024 && !(h->skinny && K <= 2048 && h->cfg.compute_dtype != 1)) {
-                // backward only: a few rows x a long K (dho: 256 rows x K = 8192 took 0.2 ms on 32 thin tiles):
-                // K split over ~768 workgroups of full tiles with float atomics instead
-                const int s = std::min(768 / (((tail_rows + 127) / 128) * nt), K / 128);
-                if (s >= 2) {
-                    AV_CHECK(zero_fill(h->stream, Ct, sizeof(float) * (size_t)tail_rows * N));
-                    return gemm_raw(h, a_mc, b_nc, At, lda, Bm, ldb, Ct, ldc, tail_rows, N, K, alpha, bias, 0, s, nullptr, 0);
-                }
-            }
-            return gemm_raw(h, a_mc, b_nc, At, lda, Bm, ldb, Ct, ldc, tail_rows, N, K, alpha, bias, accumulate, 1, nullptr, 0, thin_form);
-        }
-    }
-    return gemm_raw(h, a_mc, b_nc, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, bias, accumulate, 1, dyn, dyn_kind);
-}
-// K-split so that a weight-gradient GEMM (few output tiles, very long K) fills the chip: aim at 768
-// co-resident workgroups (3 per CU), every slice at least 4 K-tiles deep
-int grad_split(int M, int N, int K)
-{
-    int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int s = 768 / tiles;
-    int kmax = K / 128; if (kmax < 1) kmax = 1;
-    if (s > kmax) s = kmax;
-    return s < 1 ? 1 : s;
-}
-// dW (M x N) += A^T B over K rows; A [k][m] lda, B [k][n] ldb.  grads are zero-filled beforehand.
-int gemm_tn_grad(avae_ctx* h, const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
-                 float alpha = 1.f, const int* dynk = nullptr, const Pair* pair = nullptr)
-{
-    if (h->cfg.compute_dtype != 0) {
-        const int s = grad_split(M, N, K);
-        return gemm_raw(h, true, true, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, nullptr, s > 1 ? 0 : 1, s, dynk, dynk ? 2 : 0, 0, pair);
-    }
-    // exact-fp32 kernel.  Few output tiles over a very long K: the K split's float atomics (~1.3 TB/s chip-wide, all
-    // workgroups at once at the end of one synchronous round) are the overhead, and they scale with tile bytes x
-    // slices.  64x64 tiles give four times the tiles, so a quarter of the slices fill the chip (decoder dW/dR pair,
-    // the two directions' dR: +6 %, gpurun_out/ab8.log); ~1536 workgroups = 6 per CU.  A pair shares them.
-    // A small output (decode/out/kernel, latent) uses 32x128 tiles.
-    const int np = pair ? 2 : 1;
-    const int t128 = ((M + 127) / 128) * ((N + 127) / 128);
-    int thin = 2, tiles = ((M + 63) / 64) * ((N + 63) / 64) * np, target = 1536;
-    if (t128 * np > 96) { thin = 0; tiles = t128 * np; target = 768; }      // enough full tiles: 128x128 (measured: 64x64 loses 3-8 % there)
-    if (t128 <= 16) { thin = 1; tiles = ((M + 31) / 32) * ((N + 127) / 128) * np; target = 768; }
-    int s = (target + tiles / 2) / tiles;
-    s = std::max(1, std::min(s, std::max(1, K / 128)));
-    // (gradients were zero-filled: one slice may store, several add)
-    return gemm_raw(h, true, true, A, lda, Bm, ldb, C, ldc, M, N, K, alpha, nullptr, 0, s, dynk, dynk ? 2 : 0, thin, pair);
-}
+static bool tn16_ok(const avae_ctx* h, int M, int N) { return h->cfg.compute_dtype == 1 && h->bf16_tn && gemm_tn16_shape(M, N); }
 
 void gru_geometry(int D, int njobs, int B, int* G, int* rpg)
 {
@@ -790,13 +757,11 @@ int run_encoder(avae_ctx* h, Ws& w, int B, int Ss, bool save)
             const int32_t* cnt = id_groups_count(w.grp_src, rs, V);
             AV_CHECK(id_groups_build(h->stream, w.src_tm, rs, V, w.grp_src, save));
             AV_CHECK(rows_gather(h->stream, w.emb_src, h->P + h->oE, id_groups_uid(w.grp_src, rs, V), cnt, std::min(V, rs), D));
-            AV_TRY(gemm(h, false, false, w.emb_src, D, h->P + p.W, D, w.ew, 6 * D, std::min(V, rs), 6 * D, D, 1.f, h->P + p.bW, 0, 0, cnt, 1));
+            AV_TRY(gemm(h, nt(w.emb_src, D, h->P + p.W, D, w.ew, 6 * D, std::min(V, rs), 6 * D, D).biased(h->P + p.bW).rows(cnt)));
         } else if (i > 0 && w.act_e[i - 1]) {       // the layer below wrote its output as bf16: the A operand as it stands
-            AV_TRY(gemm_bf16_pre(h, w.e_hs16[i - 1], In, false, h->P + p.W, In, false, w.e_gi[i], 6 * D, rs, top1 ? 3 * D : 6 * D, In, 1.f, 0, 1, cdyn, cdyn ? 1 : 0, h->P + p.bW));
+            AV_TRY(gemm_bf16_pre(h, nt(nullptr, In, h->P + p.W, In, w.e_gi[i], 6 * D, rs, top1 ? 3 * D : 6 * D, In).a16(w.e_hs16[i - 1]).biased(h->P + p.bW).rows(cdyn)));
         } else {
-        h->keep_a16 = save ? w.x16_e[i] : nullptr;
-        AV_TRY(gemm(h, false, false, x, In, h->P + p.W, In, w.e_gi[i], 6 * D, rs, top1 ? 3 * D : 6 * D, In, 1.f, h->P + p.bW, 0, 0, cdyn, cdyn ? 1 : 0));
-        h->keep_a16 = nullptr;
+        AV_TRY(gemm(h, nt(x, In, h->P + p.W, In, w.e_gi[i], 6 * D, rs, top1 ? 3 * D : 6 * D, In).biased(h->P + p.bW).rows(cdyn).keep(save ? w.x16_e[i] : nullptr)));
         }
         GruArgs a{};
         gru_common(h, w, a, top1 ? 1 : 2, Ss, B, 6 * D, 2 * D, w.lens_src, w.bx_enc());
@@ -834,8 +799,7 @@ int run_encoder(avae_ctx* h, Ws& w, int B, int Ss, bool save)
             if (w.act_e[i - 1]) AV_CHECK(pick_last16(h->stream, w.xlast, w.e_hs16[i - 1], w.lens_src, B, In, cmap));
             else
             AV_CHECK(pick_last(h->stream, w.xlast, x, w.lens_src, B, In, cmap));
-            h->rows_form = 1;
-            AV_TRY(gemm(h, false, false, w.xlast, In, h->P + oWb, In, w.gib, 3 * D, B, 3 * D, In, 1.f, h->P + p.bW + 3 * D));
+            AV_TRY(gemm(h, nt(w.xlast, In, h->P + oWb, In, w.gib, 3 * D, B, 3 * D, In).biased(h->P + p.bW + 3 * D).batch_rows()));
         }
         x = w.e_hs[i]; In = 2 * D;
     }
@@ -852,7 +816,7 @@ int run_latent(avae_ctx* h, Ws& w, int B, bool train, uint64_t seed, const float
     const int D = h->cfg.dim_emb, R = h->cfg.dim_rep;
     {   // mu and lv (model.py:149-150): two affines of the same input, one launch
         const Pair lv{w.hpick, h->P + h->oWlv, w.lv, h->P + h->oBlv};
-        AV_TRY(gemm_raw(h, false, true, w.hpick, 2 * D, h->P + h->oWmu, R, w.mu, R, B, R, 2 * D, 1.f, h->P + h->oBmu, 0, 1, nullptr, 0, h->skinny ? 3 : (B <= 512 ? 1 : 0), &lv));      // (rows = the batch rows: the skinny form for every batch size)
+        AV_TRY(gemm(h, nn(w.hpick, 2 * D, h->P + h->oWmu, R, w.mu, R, B, R, 2 * D).biased(h->P + h->oBmu).with(&lv)));      // (rows = the batch rows: the skinny form for every batch size, gemm_plan)
     }
     AV_CHECK(latent_fwd(h->stream, w.mu, w.lv, eps, w.eps, w.z, w.kld, B * R, train ? 1 : 0, seed, h->cfg.free_bits, nullptr));      // (KL scalar: finalize_losses, fixed order)
     return 0;
@@ -878,15 +842,13 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
             const int32_t* cnt = id_groups_count(w.grp_tgt, rt, V);
             AV_CHECK(id_groups_build(h->stream, ids0, rt, V, w.grp_tgt, save));
             AV_CHECK(rows_gather(h->stream, w.emb_tgt, h->P + h->oE, id_groups_uid(w.grp_tgt, rt, V), cnt, std::min(V, rt), D));
-            AV_TRY(gemm(h, false, false, w.emb_tgt, D, h->P + p.W, D, w.ew, 3 * D, std::min(V, rt), 3 * D, D, 1.f, h->P + p.bW, 0, 0, cnt, 1));
+            AV_TRY(gemm(h, nt(w.emb_tgt, D, h->P + p.W, D, w.ew, 3 * D, std::min(V, rt), 3 * D, D).biased(h->P + p.bW).rows(cnt)));
         } else if (i == 0 && share_rows) {
-            AV_TRY(gemm(h, false, false, x, D, h->P + p.W, D, w.d_gi[0], 3 * D, share_n, 3 * D, D, 1.f, h->P + p.bW));
+            AV_TRY(gemm(h, nt(x, D, h->P + p.W, D, w.d_gi[0], 3 * D, share_n, 3 * D, D).biased(h->P + p.bW)));
         } else if (i > 0 && w.act_d[i - 1]) {
-            AV_TRY(gemm_bf16_pre(h, w.d_hd16[i - 1], D, false, h->P + p.W, D, false, w.d_gi[i], 3 * D, rt, 3 * D, D, 1.f, 0, 1, cdyn, cdyn ? 1 : 0, h->P + p.bW));
+            AV_TRY(gemm_bf16_pre(h, nt(nullptr, D, h->P + p.W, D, w.d_gi[i], 3 * D, rt, 3 * D, D).a16(w.d_hd16[i - 1]).biased(h->P + p.bW).rows(cdyn)));
         } else {
-        h->keep_a16 = save ? w.x16_d[i] : nullptr;
-        AV_TRY(gemm(h, false, false, x, D, h->P + p.W, D, w.d_gi[i], 3 * D, rt, 3 * D, D, 1.f, h->P + p.bW, 0, 0, cdyn, cdyn ? 1 : 0));
-        h->keep_a16 = nullptr;
+        AV_TRY(gemm(h, nt(x, D, h->P + p.W, D, w.d_gi[i], 3 * D, rt, 3 * D, D).biased(h->P + p.bW).rows(cdyn).keep(save ? w.x16_d[i] : nullptr)));
         }
         GruArgs a{};
         gru_common(h, w, a, 1, T, B, 3 * D, D, nullptr, compact ? w.Bx : 0);
@@ -936,8 +898,7 @@ int forward(avae_ctx* h, Ws& w, const int32_t* src, const int32_t* tgt, int B, i
     AV_TRY(build_compact(h, w, B, Ss, T, train));
     AV_TRY(run_encoder(h, w, B, Ss, train));
     AV_TRY(run_latent(h, w, B, train, seed, eps));
-    h->rows_form = 1;
-    AV_TRY(gemm(h, false, true, w.z, R, h->P + h->oWex, D, w.h0, D, B, D, R, 1.f, h->P + h->oBex));
+    AV_TRY(gemm(h, nn(w.z, R, h->P + h->oWex, D, w.h0, D, B, D, R).biased(h->P + h->oBex).batch_rows()));
     if (use_table(h, rt, B)) AV_TRY(run_decoder_rnn(h, w, B, T, w.h0, 0, train, w.lead, w.compact_d));
     else {
         AV_CHECK(embed_gather(h->stream, h->P + h->oE, w.lead, w.emb_tgt, rt, D, V));
@@ -955,7 +916,7 @@ int run_logits_ce(avae_ctx* h, Ws& w, int rt, bool train, float inv_n)
 {
     const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
     AV_CHECK(rows_gather(h->stream, w.hc, w.d_hd[L - 1], w.cidx, w.ntok, rt, D, w.compact_d ? w.map_tgt : nullptr));
-    AV_TRY(gemm(h, false, true, w.hc, D, h->P + h->oKout, D, w.ho, D, rt, D, D, 1.f, h->P + h->oBout, 0, 0, w.ntok, 1));
+    AV_TRY(gemm(h, nn(w.hc, D, h->P + h->oKout, D, w.ho, D, rt, D, D).biased(h->P + h->oBout).rows(w.ntok)));
     CeArgs c{};
     c.logits = w.logits; c.gold = w.gold; c.cidx = w.cidx; c.n_dev = w.ntok; c.n_max = rt; c.V = V;
     c.write_grad = train ? 1 : 0; c.inv_n = inv_n;
@@ -964,13 +925,11 @@ int run_logits_ce(avae_ctx* h, Ws& w, int rt, bool train, float inv_n)
         c.grad16 = h->bfP;
         // ... and where the phased GEMM takes the whole product, the logits themselves go THERE as fp16 (2^-11 relative, finer than the bf16
         // gradient they become): no fp32 logits are written or read -- 4.3 GB of 10.8 GB at configs[2]
-        GemmArgs probe{nullptr, nullptr, nullptr, nullptr, rt, V, D, D, D, V, 1.f, 0, 1, w.ntok, 1, 0, 0, nullptr, nullptr, nullptr, nullptr};
-        probe.nt8 = h->bf16_nt8;
-        if (h->logits16 && !h->bf16_direct && (D & 7) == 0 && gemm_bf16_c16_ok(probe, D, D)) c.logits16 = 1;
+        if (h->logits16 && !h->bf16_direct && gemm_bf16_c16_takes(rt, V, D, w.ntok, h->bf16_nt8)) c.logits16 = 1;
     }
-    if (c.logits16) AV_TRY(gemm_raw(h, false, false, w.ho, D, h->P + h->oE, D, w.logits, V, rt, V, D, 1.f / sqrtf((float)D), nullptr, 0, 1, w.ntok, 1, 0, nullptr, h->bfP));
-    else
-    AV_TRY(gemm(h, false, false, w.ho, D, h->P + h->oE, D, w.logits, V, rt, V, D, 1.f / sqrtf((float)D), nullptr, 0, 0, w.ntok, 1));
+    GemmCall lg = nt(w.ho, D, h->P + h->oE, D, w.logits, V, rt, V, D).scaled(1.f / sqrtf((float)D)).rows(w.ntok);
+    if (c.logits16) lg.form(0).c16 = h->bfP;      // (the panel: one launch of the phased kernel, as the probe above assumed)
+    AV_TRY(gemm(h, lg));
     c.loss_samp = w.loss_samp; c.errt_samp = w.errt_samp; c.pred = w.pred; c.loss_acc = nullptr;      // (the scalar is summed from loss_samp in a fixed order: finalize_losses)
     AV_CHECK(softmax_ce(h->stream, c));
     return 0;
@@ -1012,22 +971,19 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
         // bf16 mode: softmax_ce_kernel left the gradient as bf16 (h->bfP): the first GEMM reads it as its A panel, the
         // second transposes the 2-byte source once -- no fp32 gradient is written or converted (10.7 GB less traffic per
         // step at configs[2]); same values as rounding the fp32 gradient, so the results do not change
-        AV_TRY(gemm_bf16_pre(h, h->bfP, V, false, P + h->oE, D, true, w.dho, D, rt, D, V, isd, 0, 1, w.ntok, 1));
-        if (tn16_ok(h, V, D)) AV_TRY(gemm_tn16(h, h->bfP, nullptr, V, nullptr, w.ho, D, G + h->oE, D, V, D, rt, isd, w.ntok));      // (no transposed copy of the 2-byte gradient)
-        else {
-        const int s = grad_split(V, D, rt);
-        AV_TRY(gemm_bf16_pre(h, h->bfP, V, true, w.ho, D, true, G + h->oE, D, V, D, rt, isd, s > 1 ? 0 : 1, s, w.ntok, 2));
-        }
+        AV_TRY(gemm_bf16_pre(h, nn(nullptr, V, P + h->oE, D, w.dho, D, rt, D, V).a16(h->bfP).scaled(isd).rows(w.ntok)));
+        const GemmCall dE = tn_grad(nullptr, V, w.ho, D, G + h->oE, D, V, D, rt).a16(h->bfP).scaled(isd).depth(w.ntok);
+        AV_TRY(tn16_ok(h, V, D) ? gemm_tn16(h, dE) : gemm_bf16_pre(h, dE));      // (tn16: no transposed copy of the 2-byte gradient)
     } else {
-    AV_TRY(gemm(h, false, true, w.logits, V, P + h->oE, D, w.dho, D, rt, D, V, isd, nullptr, 0, 0, w.ntok, 1, true));
+    AV_TRY(gemm(h, nn(w.logits, V, P + h->oE, D, w.dho, D, rt, D, V).scaled(isd).rows(w.ntok).atomic()));
     // (V x D output over K = N rows: 256 tiles of 128x128 x 3 K slices, float atomics into the zero-filled G; the gather
     //  part is scatter-added at the end)
-    AV_TRY(gemm_tn_grad(h, w.logits, V, w.ho, D, G + h->oE, D, V, D, rt, isd, w.ntok));
+    AV_TRY(gemm(h, tn_grad(w.logits, V, w.ho, D, G + h->oE, D, V, D, rt).scaled(isd).depth(w.ntok)));
     }
     // out affine
-    AV_TRY(gemm_tn_grad(h, w.hc, D, w.dho, D, G + h->oKout, D, D, D, rt, 1.f, w.ntok));
+    AV_TRY(gemm(h, tn_grad(w.hc, D, w.dho, D, G + h->oKout, D, D, D, rt).depth(w.ntok)));
     AV_CHECK(colsum(st, w.dho, rt, D, D, G + h->oBout, w.ntok));
-    AV_TRY(gemm(h, false, false, w.dho, D, P + h->oKout, D, w.dhc, D, rt, D, D, 1.f, nullptr, 0, 0, w.ntok, 1, true));
+    AV_TRY(gemm(h, nt(w.dho, D, P + h->oKout, D, w.dhc, D, rt, D, D).rows(w.ntok).atomic()));
     fire_hook(h, 0);
     const int32_t* const ddyn = w.compact_d ? w.ntgt : nullptr;        // compact decoder layout (build_compact)
     const int32_t* const dmap = w.compact_d ? w.map_tgt : nullptr;
@@ -1068,26 +1024,26 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
             // table-fed layer: gate gradients summed by id, then dW = (sum)^T E and dE += (sum) W over V rows
             const int32_t* cnt = id_groups_count(w.grp_tgt, rt, V); const int U = std::min(V, rt);
             AV_CHECK(rows_group_sum(st, w.dew, w.lead, w.dgi_d, rt, 3 * D, V, w.grp_tgt));
-            AV_TRY(gemm_tn_grad(h, w.dew, 3 * D, w.emb_tgt, D, G + p.W, D, 3 * D, D, U, 1.f, cnt));
-            if (gh16) AV_TRY(gemm_tn16(h, w.dgh16_d, nullptr, 3 * D, w.d_hp16[i], nullptr, D, G + p.R, D, 3 * D, D, rt, 1.f, ddyn));
+            AV_TRY(gemm(h, tn_grad(w.dew, 3 * D, w.emb_tgt, D, G + p.W, D, 3 * D, D, U).depth(cnt)));
+            if (gh16) AV_TRY(gemm_tn16(h, tn_grad(nullptr, 3 * D, nullptr, D, G + p.R, D, 3 * D, D, rt).a16(w.dgh16_d).b16(w.d_hp16[i]).depth(ddyn)));
             else
-            AV_TRY(gemm_tn_grad(h, w.dgh_d, 3 * D, w.d_hp[i], D, G + p.R, D, 3 * D, D, rt, 1.f, ddyn));
-            AV_TRY(gemm(h, false, true, w.dew, 3 * D, P + p.W, D, w.demb_tgt, D, U, D, 3 * D, 1.f, nullptr, 0, 0, cnt, 1, true));
+            AV_TRY(gemm(h, tn_grad(w.dgh_d, 3 * D, w.d_hp[i], D, G + p.R, D, 3 * D, D, rt).depth(ddyn)));
+            AV_TRY(gemm(h, nn(w.dew, 3 * D, P + p.W, D, w.demb_tgt, D, U, D, 3 * D).rows(cnt).atomic()));
             AV_CHECK(rows_add_indexed(st, G + h->oE, w.demb_tgt, id_groups_uid(w.grp_tgt, rt, V), cnt, U, D));
         } else if (g16) {
             const float* x = i == 0 ? w.emb_tgt : w.d_hd[i - 1];
-            AV_TRY(gemm_tn16(h, w.dgi16_d, nullptr, 3 * D, (i > 0 && w.act_d[i - 1]) ? w.d_hd16[i - 1] : w.x16_kept_d(i), x, D, G + p.W, D, 3 * D, D, rt, 1.f, ddyn));
-            AV_TRY(gemm_tn16(h, w.dgh16_d, nullptr, 3 * D, w.acth_d[i] ? w.d_hp16[i] : nullptr, w.d_hp[i], D, G + p.R, D, 3 * D, D, rt, 1.f, ddyn));
+            AV_TRY(gemm_tn16(h, tn_grad(nullptr, 3 * D, x, D, G + p.W, D, 3 * D, D, rt).a16(w.dgi16_d).b16((i > 0 && w.act_d[i - 1]) ? w.d_hd16[i - 1] : w.x16_kept_d(i)).depth(ddyn)));
+            AV_TRY(gemm_tn16(h, tn_grad(nullptr, 3 * D, w.d_hp[i], D, G + p.R, D, 3 * D, D, rt).a16(w.dgh16_d).b16(w.acth_d[i] ? w.d_hp16[i] : nullptr).depth(ddyn)));
             float* dx = i == 0 ? w.demb_tgt : w.dhd[cur ^ 1];
-            AV_TRY(gemm_bf16_pre(h, w.dgi16_d, 3 * D, false, P + p.W, D, true, dx, D, rt, D, 3 * D, 1.f, 0, 1, ddyn, ddyn ? 1 : 0));
+            AV_TRY(gemm_bf16_pre(h, nn(nullptr, 3 * D, P + p.W, D, dx, D, rt, D, 3 * D).a16(w.dgi16_d).rows(ddyn)));
         } else {
         const float* x = i == 0 ? w.emb_tgt : w.d_hd[i - 1];
         {   // dW = dgi^T x and dR = dgh^T h_prev: same shape over the same rows, one launch
             const Pair dR{w.dgh_d, w.d_hp[i], G + p.R, nullptr};
-            AV_TRY(gemm_tn_grad(h, w.dgi_d, 3 * D, x, D, G + p.W, D, 3 * D, D, rt, 1.f, ddyn, &dR));
+            AV_TRY(gemm(h, tn_grad(w.dgi_d, 3 * D, x, D, G + p.W, D, 3 * D, D, rt).depth(ddyn).with(&dR)));
         }
         float* dx = i == 0 ? w.demb_tgt : w.dhd[cur ^ 1];
-        AV_TRY(gemm(h, false, true, w.dgi_d, 3 * D, P + p.W, D, dx, D, rt, D, 3 * D, 1.f, nullptr, 0, 0, ddyn, ddyn ? 1 : 0, true));
+        AV_TRY(gemm(h, nn(w.dgi_d, 3 * D, P + p.W, D, dx, D, rt, D, 3 * D).rows(ddyn).atomic()));
         }
         cur ^= 1;
         fire_hook(h, 1 + (L - 1 - i));
@@ -1096,19 +1052,19 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
     // latent
     AV_CHECK(add3(st, w.dh0sum, w.dh0, L > 1 ? w.dh0 + (size_t)B * D : nullptr, L > 2 ? w.dh0 + (size_t)2 * B * D : nullptr, (int64_t)B * D));
     for (int i = 3; i < L; ++i) AV_CHECK(add3(st, w.dh0sum, w.dh0sum, w.dh0 + (size_t)i * B * D, nullptr, (int64_t)B * D));
-    AV_TRY(gemm_tn_grad(h, w.z, R, w.dh0sum, D, G + h->oWex, D, R, D, B));
+    AV_TRY(gemm(h, tn_grad(w.z, R, w.dh0sum, D, G + h->oWex, D, R, D, B)));
     AV_CHECK(colsum(st, w.dh0sum, B, D, D, G + h->oBex, nullptr));
-    AV_TRY(gemm(h, false, false, w.dh0sum, D, P + h->oWex, D, w.dz, R, B, R, D));
+    AV_TRY(gemm(h, nt(w.dh0sum, D, P + h->oWex, D, w.dz, R, B, R, D)));
     float bg = b_global > 0.f ? b_global : (float)B;
     AV_CHECK(latent_bwd(st, w.dz, w.mu, w.lv, w.eps, w.dmu, w.dlv, B, R, sc.anneal * h->cfg.kl_beta / (bg * R), h->cfg.free_bits));
     {
         const Pair dlv{w.hpick, w.dlv, G + h->oWlv, nullptr};
-        AV_TRY(gemm_tn_grad(h, w.hpick, 2 * D, w.dmu, R, G + h->oWmu, R, 2 * D, R, B, 1.f, nullptr, &dlv));
+        AV_TRY(gemm(h, tn_grad(w.hpick, 2 * D, w.dmu, R, G + h->oWmu, R, 2 * D, R, B).with(&dlv)));
     }
     AV_CHECK(colsum(st, w.dmu, B, R, R, G + h->oBmu, nullptr));
     AV_CHECK(colsum(st, w.dlv, B, R, R, G + h->oBlv, nullptr));
-    AV_TRY(gemm(h, false, false, w.dmu, R, P + h->oWmu, R, w.dhpick, 2 * D, B, 2 * D, R));
-    AV_TRY(gemm(h, false, false, w.dlv, R, P + h->oWlv, R, w.dhpick, 2 * D, B, 2 * D, R, 1.f, nullptr, 1));
+    AV_TRY(gemm(h, nt(w.dmu, R, P + h->oWmu, R, w.dhpick, 2 * D, B, 2 * D, R)));
+    AV_TRY(gemm(h, nt(w.dlv, R, P + h->oWlv, R, w.dhpick, 2 * D, B, 2 * D, R).plus()));
     fire_hook(h, 1 + L);
     const int32_t* const cdyn = w.compact ? w.nsrc : nullptr;        // compact encoder layout (build_compact)
     const int32_t* const cmap = w.compact ? w.map_src : nullptr;
@@ -1165,18 +1121,18 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
             // bf16 mode, gate gradients written as bf16 by the BPTT kernels: every GEMM of the layer reads them as they stand
             const int Gc = a.njobs * 3 * D;                          // gate columns of the directions that ran
             if (i == 0) {     // first layer (per-token form): input gradient, scatter, embedding bucket -- the fixed order of announcements
-                AV_TRY(gemm_bf16_pre(h, w.dgi16_e, 6 * D, false, P + p.W, In, true, dx, In, rs, In, Gc, 1.f, 0, 1, nullptr, 0));
+                AV_TRY(gemm_bf16_pre(h, nn(nullptr, 6 * D, P + p.W, In, dx, In, rs, In, Gc).a16(w.dgi16_e)));
                 AV_CHECK(embed_scatter_add2(st, G + h->oE, w.src_tm, w.demb_src, rs, w.lead, w.demb_tgt, use_table(h, rt, B) ? 0 : rt, D, V, w.scat));
                 fire_hook(h, 2 + 2 * L);
                 hook_flush(h);
             }
-            AV_TRY(gemm_tn16(h, w.dgi16_e, nullptr, 6 * D, (i > 0 && w.act_e[i - 1]) ? w.e_hs16[i - 1] : w.x16_kept_e(i), x, In, G + p.W, In, Gc, In, rs, 1.f, cdyn));
-            if (top1) AV_TRY(gemm_tn_grad(h, w.dgib, 3 * D, w.xlast, In, G + oWb, In, 3 * D, In, B));
+            AV_TRY(gemm_tn16(h, tn_grad(nullptr, 6 * D, x, In, G + p.W, In, Gc, In, rs).a16(w.dgi16_e).b16((i > 0 && w.act_e[i - 1]) ? w.e_hs16[i - 1] : w.x16_kept_e(i)).depth(cdyn)));
+            if (top1) AV_TRY(gemm(h, tn_grad(w.dgib, 3 * D, w.xlast, In, G + oWb, In, 3 * D, In, B)));
             for (int d = 0; d < a.njobs; ++d)
-                AV_TRY(gemm_tn16(h, w.dgh16_e + d * 3 * D, nullptr, 6 * D, w.acth_e[i] ? w.e_hp16[d][i] : nullptr, w.e_hp[d][i], D, G + p.R + (int64_t)d * 3 * D * D, D, 3 * D, D, rs, 1.f, cdyn));
-            if (i > 0) AV_TRY(gemm_bf16_pre(h, w.dgi16_e, 6 * D, false, P + p.W, In, true, dx, In, rs, In, Gc, 1.f, 0, 1, cdyn, cdyn ? 1 : 0));
+                AV_TRY(gemm_tn16(h, tn_grad(nullptr, 6 * D, w.e_hp[d][i], D, G + p.R + (int64_t)d * 3 * D * D, D, 3 * D, D, rs).a16(w.dgh16_e + d * 3 * D).b16(w.acth_e[i] ? w.e_hp16[d][i] : nullptr).depth(cdyn)));
+            if (i > 0) AV_TRY(gemm_bf16_pre(h, nn(nullptr, 6 * D, P + p.W, In, dx, In, rs, In, Gc).a16(w.dgi16_e).rows(cdyn)));
             if (top1) {
-                AV_TRY(gemm(h, false, true, w.dgib, 3 * D, P + oWb, In, w.dxl, In, B, In, 3 * D, 1.f, nullptr, 0, 0, nullptr, 0, true));
+                AV_TRY(gemm(h, nn(w.dgib, 3 * D, P + oWb, In, w.dxl, In, B, In, 3 * D).atomic()));
                 AV_CHECK(pick_last_add(st, dx, w.dxl, w.lens_src, B, In, cmap));
             }
             cur ^= 1;
@@ -1193,36 +1149,36 @@ int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
                 // table-fed layer (use_table): gate gradients summed by id, dE[present] += (sum) W over U rows
                 const int32_t* cnt = id_groups_count(w.grp_src, rs, V); const int U = std::min(V, rs);
                 AV_CHECK(rows_group_sum(st, w.dew, w.src_tm, w.dgi_e, rs, 6 * D, V, w.grp_src));
-                AV_TRY(gemm(h, false, true, w.dew, 6 * D, P + p.W, D, w.demb_src, D, U, D, 6 * D, 1.f, nullptr, 0, 0, cnt, 1, true));
+                AV_TRY(gemm(h, nn(w.dew, 6 * D, P + p.W, D, w.demb_src, D, U, D, 6 * D).rows(cnt).atomic()));
                 AV_CHECK(rows_add_indexed(st, G + h->oE, w.demb_src, id_groups_uid(w.grp_src, rs, V), cnt, U, D));
             } else
-            AV_TRY(gemm(h, false, true, w.dgi_e, 6 * D, P + p.W, In, dx, In, rs, In, 6 * D, 1.f, nullptr, 0, 0, nullptr, 0, true));
+            AV_TRY(gemm(h, nn(w.dgi_e, 6 * D, P + p.W, In, dx, In, rs, In, 6 * D).atomic()));
             // gather gradients of the per-token forms on top of the logits term (a table-fed side has added its rows already)
             AV_CHECK(embed_scatter_add2(st, G + h->oE, w.src_tm, w.demb_src, table ? 0 : rs, w.lead, w.demb_tgt, use_table(h, rt, B) ? 0 : rt, D, V, w.scat));
             fire_hook(h, 2 + 2 * L);
             hook_flush(h);
             if (table) {
                 const int32_t* cnt = id_groups_count(w.grp_src, rs, V); const int U = std::min(V, rs);
-                AV_TRY(gemm_tn_grad(h, w.dew, 6 * D, w.emb_src, D, G + p.W, D, 6 * D, D, U, 1.f, cnt));
+                AV_TRY(gemm(h, tn_grad(w.dew, 6 * D, w.emb_src, D, G + p.W, D, 6 * D, D, U).depth(cnt)));
             } else
-            AV_TRY(gemm_tn_grad(h, w.dgi_e, 6 * D, x, In, G + p.W, In, 6 * D, In, rs));
+            AV_TRY(gemm(h, tn_grad(w.dgi_e, 6 * D, x, In, G + p.W, In, 6 * D, In, rs)));
         } else if (top1) {
-            AV_TRY(gemm_tn_grad(h, w.dgi_e, 6 * D, x, In, G + p.W, In, 3 * D, In, rs, 1.f, cdyn));       // forward direction's W
-            AV_TRY(gemm_tn_grad(h, w.dgib, 3 * D, w.xlast, In, G + oWb, In, 3 * D, In, B));              // backward direction's: B rows
+            AV_TRY(gemm(h, tn_grad(w.dgi_e, 6 * D, x, In, G + p.W, In, 3 * D, In, rs).depth(cdyn)));       // forward direction's W
+            AV_TRY(gemm(h, tn_grad(w.dgib, 3 * D, w.xlast, In, G + oWb, In, 3 * D, In, B)));              // backward direction's: B rows
         } else
-        AV_TRY(gemm_tn_grad(h, w.dgi_e, 6 * D, x, In, G + p.W, In, 6 * D, In, rs, 1.f, cdyn));
+        AV_TRY(gemm(h, tn_grad(w.dgi_e, 6 * D, x, In, G + p.W, In, 6 * D, In, rs).depth(cdyn)));
         if (gh16) {
             for (int d = 0; d < a.njobs; ++d)
-                AV_TRY(gemm_tn16(h, w.dgh16_e + d * 3 * D, nullptr, 6 * D, w.e_hp16[d][i], nullptr, D, G + p.R + (int64_t)d * 3 * D * D, D, 3 * D, D, rs, 1.f, cdyn));
-        } else if (top1) AV_TRY(gemm_tn_grad(h, w.dgh_e, 6 * D, w.e_hp[0][i], D, G + p.R, D, 3 * D, D, rs, 1.f, cdyn));
+                AV_TRY(gemm_tn16(h, tn_grad(nullptr, 6 * D, nullptr, D, G + p.R + (int64_t)d * 3 * D * D, D, 3 * D, D, rs).a16(w.dgh16_e + d * 3 * D).b16(w.e_hp16[d][i]).depth(cdyn)));
+        } else if (top1) AV_TRY(gemm(h, tn_grad(w.dgh_e, 6 * D, w.e_hp[0][i], D, G + p.R, D, 3 * D, D, rs).depth(cdyn)));
         else {   // dR of the two directions: same shape, one launch
             const Pair bwd{w.dgh_e + 3 * D, w.e_hp[1][i], G + p.R + (int64_t)3 * D * D, nullptr};
-            AV_TRY(gemm_tn_grad(h, w.dgh_e, 6 * D, w.e_hp[0][i], D, G + p.R, D, 3 * D, D, rs, 1.f, cdyn, &bwd));
+            AV_TRY(gemm(h, tn_grad(w.dgh_e, 6 * D, w.e_hp[0][i], D, G + p.R, D, 3 * D, D, rs).depth(cdyn).with(&bwd)));
         }
         if (i > 0)
-        AV_TRY(gemm(h, false, true, w.dgi_e, 6 * D, P + p.W, In, dx, In, rs, In, top1 ? 3 * D : 6 * D, 1.f, nullptr, 0, 0, cdyn, cdyn ? 1 : 0, true));
+        AV_TRY(gemm(h, nn(w.dgi_e, 6 * D, P + p.W, In, dx, In, rs, In, top1 ? 3 * D : 6 * D).rows(cdyn).atomic()));
         if (top1) {       // the backward direction's input gradient lands on the rows at len_b - 1
-            AV_TRY(gemm(h, false, true, w.dgib, 3 * D, P + oWb, In, w.dxl, In, B, In, 3 * D, 1.f, nullptr, 0, 0, nullptr, 0, true));      // (B rows: the skinny form, 43 -> 16 us)
+            AV_TRY(gemm(h, nn(w.dgib, 3 * D, P + oWb, In, w.dxl, In, B, In, 3 * D).atomic()));      // (B rows: the skinny form, 43 -> 16 us)
             AV_CHECK(pick_last_add(st, dx, w.dxl, w.lens_src, B, In, cmap));
         }
         cur ^= 1;
@@ -1412,8 +1368,7 @@ int score_rows_dev(avae_ctx* h, const ScorePlan& sp, const ScoreWs& s, const int
             AV_CHECK(prep_ids(h->stream, p));
             AV_TRY(build_row_orders(h, w, n, 1, T, true, false));
             AV_TRY(build_compact_dec(h, w, n, T));
-            h->rows_form = 1;
-            AV_TRY(gemm(h, false, true, z, R, h->P + h->oWex, D, w.h0, D, n, D, R, 1.f, h->P + h->oBex));
+            AV_TRY(gemm(h, nn(z, R, h->P + h->oWex, D, w.h0, D, n, D, R).biased(h->P + h->oBex).batch_rows()));
             if (use_table(h, rt, n)) AV_TRY(run_decoder_rnn(h, w, n, T, w.h0, 0, false, w.lead, w.compact_d));
             else {
                 GruArgs q{};
@@ -1640,6 +1595,44 @@ int avae_timing_collect(avae_handle h, double* out)
 // rows of the launch geometry the GRU team kernels take for a batch of B rows (gru_team_batch: B itself, the next row count with a
 // geometry -- the slots beyond B hold phantom rows --, or 0).  Host arithmetic only: callable without a GPU.
 int avae_debug_team_batch(int32_t B) { return B > 0 ? gru_team_batch(B) : 0; }
+// test hook: gemm_plan() for n shapes.  in: n x 19 int32, GemmShape's fields in their order; out: n x 15 -- the number of launches, then per
+// launch row0, rows, thin, split_k, accumulate, zero (GemmZero), dyn (an unused launch: zeros).  Host arithmetic only: callable without a GPU.
+int avae_debug_gemm_plan(const int32_t* in, int32_t n, int32_t* out)
+{
+    if (!in || !out || n < 0) return 1;
+    for (int r = 0; r < n; ++r, in += 19, out += 15) {
+        const GemmShape s{in[0] != 0, in[1] != 0, in[2], in[3], in[4], in[5], in[6], in[7], in[8], in[9], in[10], in[11] != 0, in[12] != 0,
+                          in[13] != 0, in[14] != 0, in[15], in[16] != 0, in[17] != 0, in[18] != 0};
+        const GemmPlan p = gemm_plan(s);
+        out[0] = p.n;
+        for (int i = 0; i < 2; ++i) {
+            const GemmLaunch l = i < p.n ? p.launch[i] : GemmLaunch{0, 0, 0, 0, 0, 0, 0};
+            const int32_t f[7] = {l.row0, l.rows, l.thin, l.split_k, l.accumulate, l.zero, l.dyn};
+            std::copy(f, f + 7, out + 1 + 7 * i);
+        }
+    }
+    return 0;
+}
+// test hook: one whole product through gemm() -- plan, clears, launches -- on caller buffers, with the handle's options.  flags: 1 allow_atomic,
+// 2 rows_are_batch, 4 weight gradient (a_mc = b_nc = 1).  count: the device-side count or null (rows; a weight gradient: depth), expect: what
+// the host is to expect of it (0: unknown).  A2 / B2 / C2: the second problem of a pair or null; keep16: GemmCall::keep_a16 or null.
+int avae_debug_gemm_call(avae_handle h, int a_mc, int b_nc, const float* A, const float* Bm, float* Cm, const float* bias, int M, int N, int K,
+                         int lda, int ldb, int ldc, float alpha, int accumulate, int flags, const int* count, int expect,
+                         const float* A2, const float* B2, float* C2, unsigned short* keep16)
+{
+    if (!h) return 1;
+    GemmCall c{A, lda, a_mc != 0, Bm, ldb, b_nc != 0, Cm, ldc, M, N, K};
+    c.alpha = alpha; c.bias = bias; c.accumulate = accumulate; c.keep_a16 = keep16;
+    c.allow_atomic = (flags & 1) != 0; c.rows_are_batch = (flags & 2) != 0; c.wgrad = (flags & 4) != 0;
+    if (c.wgrad) c.depth(count); else c.rows(count);
+    const Pair second{A2, B2, C2, nullptr};
+    if (A2) c.pair = &second;
+    const int* const was_ptr = h->expect_ptr[0]; const int was_val = h->expect_val[0];
+    h->expect_ptr[0] = count; h->expect_val[0] = expect;
+    const int r = gemm(h, c);
+    h->expect_ptr[0] = was_ptr; h->expect_val[0] = was_val;
+    return r;
+}
 // test hook: the decoder batches of the last avae_score / avae_score_z (score_plan): out = N, rc, kc, batches that ran the shared
 // first-layer projection of the non-table path (lead_rows + GruJob::gi_rows)
 int avae_debug_score_plan(avae_handle h, int32_t out[4])
@@ -1709,31 +1702,32 @@ int avae_debug_gemm(avae_handle h, int a_mc, int b_nc, const float* A, const flo
 {
     if (!h) return 1;
     // split_k == -1 selects the thin (32x128 tile) variant, -3 the skinny form, 1000 + s the 64x64-tile variant with s K slices
-    return gemm_raw(h, a_mc != 0, b_nc != 0, A, lda, Bm, ldb, Cm, ldc, M, N, K, alpha, bias, accumulate, split_k < 0 ? 1 : (split_k >= 1000 ? split_k - 1000 : split_k), nullptr, 0, split_k == -3 ? 3 : (split_k < 0 ? 1 : (split_k >= 1000 ? 2 : 0)));
+    GemmCall c{A, lda, a_mc != 0, Bm, ldb, b_nc != 0, Cm, ldc, M, N, K};
+    c.alpha = alpha; c.bias = bias; c.accumulate = accumulate;
+    return gemm(h, c.form(split_k == -3 ? 3 : (split_k < 0 ? 1 : (split_k >= 1000 ? 2 : 0)), split_k < 0 ? 1 : (split_k >= 1000 ? split_k - 1000 : split_k)));
 }
 // test hook: C = A B^T (A (M, K), B (N, K) row-major) over the first *rows rows of A only, rows read on the DEVICE (dyn_kind 1)
 int avae_debug_gemm_dyn(avae_handle h, const float* A, const float* Bm, float* Cm, int M, int N, int K, const int* rows)
 {
     if (!h) return 1;
-    return gemm_raw(h, false, false, A, K, Bm, K, Cm, N, M, N, K, 1.f, nullptr, 0, 1, rows, 1, 0);
+    return gemm(h, nt(A, K, Bm, K, Cm, N, M, N, K).rows(rows).form(0));
 }
 // test hook (compute_dtype 1): the fp16 output panel of the phased NT GEMM, C16 (M x N) = fp16(alpha * A B^T) over the first *rows rows (rows == nullptr: all);
 // returns 3 where the phased kernel does not take the shape
 int avae_debug_gemm_c16(avae_handle h, const float* A, const float* Bm, unsigned short* C16, int M, int N, int K, float alpha, const int* rows)
 {
     if (!h) return 1;
-    if (h->cfg.compute_dtype != 1 || (K & 7)) return 3;
-    GemmArgs probe{nullptr, nullptr, nullptr, nullptr, M, N, K, K, K, N, alpha, 0, 1, rows, rows ? 1 : 0, 0, 0, nullptr, nullptr, nullptr, nullptr};
-    probe.nt8 = h->bf16_nt8;
-    if (!gemm_bf16_c16_ok(probe, K, K)) return 3;
-    return gemm_raw(h, false, false, A, K, Bm, K, nullptr, N, M, N, K, alpha, nullptr, 0, 1, rows, rows ? 1 : 0, 0, nullptr, C16);
+    if (h->cfg.compute_dtype != 1 || !gemm_bf16_c16_takes(M, N, K, rows, h->bf16_nt8)) return 3;
+    GemmCall c = nt(A, K, Bm, K, nullptr, N, M, N, K).scaled(alpha).rows(rows).form(0);
+    c.c16 = C16;
+    return gemm(h, c);
 }
 // test hook: C (M x N) += alpha * A^T B with A (K x M, lda), B (K x N, ldb) fp32 row-major, operands rounded to bf16 row by
 // row and read through the transposing-LDS-load GEMM (gemm_tn16 / gemm_bf16_tn); C must hold the value to add onto
 int avae_debug_gemm_tn16(avae_handle h, const float* A, const float* Bm, float* Cm, int M, int N, int K, int lda, int ldb, int ldc, float alpha)
 {
     if (!h) return 1;
-    return gemm_tn16(h, nullptr, A, lda, nullptr, Bm, ldb, Cm, ldc, M, N, K, alpha, nullptr);
+    return gemm_tn16(h, tn_grad(A, lda, Bm, ldb, Cm, ldc, M, N, K).scaled(alpha));
 }
 // test hook: softmax_ce (ops.hip) on caller buffers, enqueued on the handle's stream.  logits (n_max x V fp32) and panel (n_max x V,
 // 2-byte) as CeArgs::logits / grad16: with write_grad the gradient goes to panel as bf16 when panel is given, else over the logits;
@@ -1857,8 +1851,7 @@ int avae_decode_init(avae_handle h, const float* z, int32_t b, float* state_out)
     AV_TRY(check_bound(h));
     AV_CHECK(hipSetDevice(h->device));
     const int D = h->cfg.dim_emb, R = h->cfg.dim_rep, L = h->cfg.rnn_layers;
-    h->rows_form = 1;
-    AV_TRY(gemm(h, false, true, z, R, h->P + h->oWex, D, state_out, D, b, D, R, 1.f, h->P + h->oBex));
+    AV_TRY(gemm(h, nn(z, R, h->P + h->oWex, D, state_out, D, b, D, R).biased(h->P + h->oBex).batch_rows()));
     for (int i = 1; i < L; ++i)
         AV_CHECK(hipMemcpyAsync(state_out + (size_t)i * b * D, state_out, (size_t)b * D * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
     return 0;
@@ -1872,8 +1865,8 @@ static int decode_logits_ws(avae_handle h, Ws& w, const int32_t* lead, const flo
     AV_TRY(run_decoder_rnn(h, w, b, 1, state_in, (int64_t)b * D, false));
     for (int i = 0; i < L && state_out; ++i)      // (null: the caller takes the new state out of w.d_hd itself -- the beam search gathers it by parent)
         AV_CHECK(hipMemcpyAsync(state_out + (size_t)i * b * D, w.d_hd[i], (size_t)b * D * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    AV_TRY(gemm(h, false, true, w.d_hd[L - 1], D, h->P + h->oKout, D, w.ho, D, b, D, D, 1.f, h->P + h->oBout));
-    AV_TRY(gemm(h, false, false, w.ho, D, h->P + h->oE, D, w.logits, V, b, V, D, 1.f / sqrtf((float)D)));
+    AV_TRY(gemm(h, nn(w.d_hd[L - 1], D, h->P + h->oKout, D, w.ho, D, b, D, D).biased(h->P + h->oBout)));
+    AV_TRY(gemm(h, nt(w.ho, D, h->P + h->oE, D, w.logits, V, b, V, D).scaled(1.f / sqrtf((float)D))));
     return 0;
 }
 static int decode_step_ws(avae_handle h, Ws& w, const int32_t* lead, const float* state_in, int b, int32_t* pred_out, float* state_out)
@@ -1906,13 +1899,7 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
     float* state[2]; int32_t* ids_tm = nullptr;
     {
         size_t need = 2 * sn * sizeof(float) + (size_t)(steps + 1) * b * sizeof(int32_t) + (sp ? (size_t)steps * b * sizeof(float) : 0);
-        if (h->scratch_n < (int64_t)need) {
-            AV_CHECK(hipStreamSynchronize(h->stream));
-            if (h->scratch) AV_CHECK(hipFree(h->scratch));
-            h->scratch = nullptr; h->scratch_n = 0;
-            AV_CHECK(hipMalloc(reinterpret_cast<void**>(&h->scratch), need));
-            h->scratch_n = (int64_t)need;
-        }
+        AV_TRY(grow_scratch(h, need, "stepwise decoding: the states and ids"));
         state[0] = h->scratch; state[1] = h->scratch + sn;
         ids_tm = reinterpret_cast<int32_t*>(h->scratch + 2 * sn);
     }
@@ -1986,13 +1973,7 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     const size_t nf = 2 * sn + (size_t)b * D + (size_t)G * b + nfs;                           // floats: state x2, o, part_val
     const size_t ni = (size_t)G * b + (size_t)(steps + 1) * b + 16;                            // ints: part_idx, ids_tm, kept, barrier
     const size_t need = (nf + ni) * 4;
-    if (h->scratch_n < (int64_t)need) {
-        AV_CHECK(hipStreamSynchronize(h->stream));
-        if (h->scratch) AV_CHECK(hipFree(h->scratch));
-        h->scratch = nullptr; h->scratch_n = 0;
-        AV_CHECK(hipMalloc(reinterpret_cast<void**>(&h->scratch), need));
-        h->scratch_n = (int64_t)need;
-    }
+    AV_TRY(grow_scratch(h, need, "decoding in one launch: the states, partial results and ids"));
     DecodeArgs a{};
     a.E = h->P + h->oE;
     for (int l = 0; l < L; ++l) { a.W[l] = h->P + h->dec[l].W; a.R[l] = h->P + h->dec[l].R; a.bW[l] = h->P + h->dec[l].bW; a.bR[l] = h->P + h->dec[l].bR; }
@@ -2072,25 +2053,6 @@ int avae_debug_sample_rows(avae_handle h, const float* logits, int n, int V, int
 }
 
 // ---------------------------------------------------------------- beam search (contract: include/argsim_vae.h, avae_decode_beam; kernels: beam.hip)
-// h->scratch is ONE buffer shared by get / set_tensor staging, the greedy and sampled loops, the beam search and its debug hook: every
-// user lays it out afresh per call and all work is ordered on the handle's stream, so no call sees another's data.  (decode_stepwise
-// and decode_loop keep their own inline copies of this growth step.)
-static int grow_scratch(avae_handle h, size_t need, const char* what)
-{
-    if (h->scratch_n >= (int64_t)need) return 0;
-    AV_CHECK(hipStreamSynchronize(h->stream));
-    if (h->scratch) AV_CHECK(hipFree(h->scratch));
-    h->scratch = nullptr; h->scratch_n = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&h->scratch), need) != hipSuccess) {
-        (void)hipGetLastError();
-        h->scratch = nullptr;
-        char b_[256]; snprintf(b_, sizeof b_, "%s: %.0f MB of scratch could not be allocated on the device", what, (double)need / 1048576.0);
-        return fail(h, b_);
-    }
-    h->scratch_n = (int64_t)need;
-    return 0;
-}
-
 int avae_decode_beam(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_beam_config* bc, int32_t* out_ids, float* score,
                      float* cum, int32_t* len, int32_t* lat_parent, int32_t* lat_token, float* lat_cum, int32_t* n_steps)
 {

@@ -66,6 +66,76 @@ def test_gemm(a_mc, b_nc, M, N, K):
     l.avae_destroy(h)
 
 
+@pytest.mark.parametrize("case", ['split', 'split_bf16_keep', 'dyn_rows_split', 'paired_wgrad'])
+def test_gemm_whole_call(case):
+    """one product through gemm() as the model calls it -- plan, clears, launches (avae_debug_gemm_call) -- at the smallest shapes
+    where the plan moves pointers, against float64 at the tolerances of test_gemm / test_gemm_bf16_operands:
+    split: 9472 x 512 x 64 = 296 tiles, 256 in the main launch + 40 in the tail: result rows on both sides of row 8192;
+    split_bf16_keep: the same in bf16 mode with GemmCall::keep_a16: the kept panel is the bf16 rounding of ALL 9472 rows of A;
+    dyn_rows_split: backward form, 2048 static rows of which *count = 700 exist (expected: 700), K = 1536: the first 700 rows are
+    cleared and K-split, the rows from 700 on keep the sentinel; paired_wgrad: two 128 x 128 weight gradients over K = 2048 in one launch"""
+    import torch
+    from argsim_amd import lib
+    l = lib.load()
+    bf16 = case == 'split_bf16_keep'
+    M, N, K = {'split': (9472, 512, 64), 'split_bf16_keep': (9472, 512, 64), 'dyn_rows_split': (2048, 512, 1536), 'paired_wgrad': (128, 128, 2048)}[case]
+    rng = np.random.default_rng(M + N + K)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = rng.standard_normal((K, N)).astype(np.float32)
+    cfg = lib.AvaeConfig(32, 16, 8, 1, 1e-4, 1e-3, 2, 1, 0, 0, 1.0, 0.0, 1 if bf16 else 0)
+    h = C.c_void_p()
+    assert l.avae_create(C.byref(cfg), 0, C.byref(h)) == 0
+    dev = torch.device('cuda', 0)
+    shape = np.array([[0, 0, M, N, K, N, 0, 0, -1, 0, 0, 0, 0, 0, 0, int(bf16), 1, 1, 1]], dtype=np.int32)      # (GemmShape: tests/test_gemm_plan.py)
+    plan = np.zeros((1, 15), dtype=np.int32)
+
+    def call(a_mc, b_nc, At, Bt, Ct, flags=0, count=None, expect=0, pair=(None, None, None), keep=None):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = l.avae_debug_gemm_call(h, a_mc, b_nc, At.data_ptr(), Bt.data_ptr(), Ct.data_ptr(), None, M, N, K, At.shape[1], Bt.shape[1], N, 1.0, 0,
+                                    flags, ptr(count), expect, ptr(pair[0]), ptr(pair[1]), ptr(pair[2]), ptr(keep))
+        assert rc == 0, l.avae_last_error(h)
+        torch.cuda.synchronize()
+        return Ct.cpu().numpy()
+
+    def close(got, want, tol):
+        err = np.abs(got - want).max()
+        print(case, 'max abs error', err, 'bound', tol * max(1.0, np.abs(want).max()))
+        assert err <= tol * max(1.0, np.abs(want).max())
+
+    if case in ('split', 'split_bf16_keep'):
+        assert l.avae_debug_gemm_plan(shape.ctypes.data, 1, plan.ctypes.data) == 0
+        assert plan[0, 0] == 2 and plan[0, 8] == 8192 and plan[0, 9] == M - 8192, plan      # main + tail, the tail from row 8192
+        At, Bt = torch.tensor(A, device=dev), torch.tensor(B.T.copy(), device=dev)
+        Ct = torch.full((M, N), 777.0, device=dev)
+        if bf16:
+            keep = torch.full((M, K), 777.0, device=dev, dtype=torch.bfloat16)
+            got = call(0, 0, At, Bt, Ct, keep=keep)
+            assert torch.equal(keep.view(torch.int16), At.to(torch.bfloat16).view(torch.int16))
+            Ar, Br = (torch.tensor(x).to(torch.bfloat16).to(torch.float64).numpy() for x in (A, B))
+            close(got, Ar @ Br, 3e-5)
+        else:
+            close(call(0, 0, At, Bt, Ct), A.astype(np.float64) @ B.astype(np.float64), 2e-5)
+    elif case == 'dyn_rows_split':
+        shape[0, 1] = 1; shape[0, 9] = 1; shape[0, 10] = 700; shape[0, 11] = 1
+        assert l.avae_debug_gemm_plan(shape.ctypes.data, 1, plan.ctypes.data) == 0
+        assert plan[0, 0] == 1 and plan[0, 4] >= 2 and plan[0, 6] == 2 and plan[0, 7] == 1, plan      # K slices into the cleared first *count rows
+        At, Bt = torch.tensor(A, device=dev), torch.tensor(B, device=dev)
+        Ct = torch.full((M, N), 777.0, device=dev)
+        count = torch.tensor([700], dtype=torch.int32, device=dev)
+        got = call(0, 1, At, Bt, Ct, flags=1, count=count, expect=700)
+        close(got[:700], A[:700].astype(np.float64) @ B.astype(np.float64), 2e-5)
+        assert (got[700:] == 777.0).all()
+    else:
+        A2 = rng.standard_normal((K, M)).astype(np.float32)
+        B2 = rng.standard_normal((K, N)).astype(np.float32)
+        At, Bt, A2t, B2t = (torch.tensor(x, device=dev) for x in (A.T.copy(), B, A2, B2))
+        Ct, C2t = torch.zeros((M, N), device=dev), torch.zeros((M, N), device=dev)      # (the zero-filled gradients)
+        got = call(1, 1, At, Bt, Ct, flags=4, pair=(A2t, B2t, C2t))
+        close(got, A.astype(np.float64) @ B.astype(np.float64), 2e-5)
+        close(C2t.cpu().numpy(), A2.T.astype(np.float64) @ B2.astype(np.float64), 2e-5)
+    l.avae_destroy(h)
+
+
 @pytest.mark.parametrize("name", list(CASES))
 def test_encode_z(name):
     cfg, P, ids, keep, eps = make_case(name)
