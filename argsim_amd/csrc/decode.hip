@@ -29,6 +29,10 @@
 //     the first maximum of the noisy scores and the log-sum-exp over the kept set.
 //   * a row is finished at step t > 0 iff the id it is fed is eos (a finished row is fed eos from then on), so the id
 //     log itself is the finished flag: the row's owner reads one id and publishes eos with logp 0.
+//   * nucleus (kMode 3, avae_decode_sample_p): kMode 2's logits phase; the owner runs the top-k select where top-k is on, takes
+//     the workgroup maximum of l / T over that set, forms the fixed-point weights once in registers and finds the mass threshold
+//     by the second radix select of sample_dev.h (64-bit weight histogram); the same merge over the final set, and the size of
+//     that set goes beside logp into a time-major scratch.
 // The greedy instantiation's device code is the parent's instruction for instruction (one kernel-argument offset moved).
 #include "kernels.h"
 #include "sample_dev.h"
@@ -103,8 +107,11 @@ constexpr int kDecThreads = 1024, kDecWaves = kDecThreads / 64;     // sixteen r
 
 constexpr int kSelMax = 8;          // sampled decoding with top-k: logits per thread of the row's owner (V <= 8192)
 constexpr int kSelWords = 512;      // its LDS behind the weights: 258 words of the radix select, 16 x 5 of the wave results
+constexpr int kMassAt = 344;        // nucleus: the mass select's 260 x 8 bytes start at this word, the 16 wave maxima follow them
+constexpr int kSelWordsP = 896;
 
-// kMode 0: greedy (model.py:204-219).  1: sampled, every logit kept.  2: sampled, top-k (see the header: sampled decoding)
+// kMode 0: greedy (model.py:204-219).  1: sampled, every logit kept.  2: sampled, top-k.  3: sampled, nucleus with or without top-k
+// (see the header: sampled decoding)
 template <int kMode>
 __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
 {
@@ -140,7 +147,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
         for (int i = tid; i < (v1 - v0) * D; i += kDecThreads) El[i] = a.E[(size_t)v0 * D + i];
     __syncthreads();
 
-    [[maybe_unused]] unsigned* sel = reinterpret_cast<unsigned*>(El + (a.cache_e ? (size_t)vp * D : 0));      // kMode 2: kSelWords
+    [[maybe_unused]] unsigned* sel = reinterpret_cast<unsigned*>(El + (a.cache_e ? (size_t)vp * D : 0));      // kMode 2: kSelWords, 3: kSelWordsP
     [[maybe_unused]] const uint64_t skey = kMode != 0 ? sample_key(a.sp.seed) : 0;
     unsigned target = 0;
     int cur = 0, kept = a.steps;
@@ -283,7 +290,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
                     if constexpr (kMode != 0) {
                         const int bb = bb0 + r * kDecWaves, v = vb + lane;
                         if (lane < 8 && v < v1 && bb < b) {
-                            if constexpr (kMode == 2) st4_sc1(a.logits + (size_t)bb * V + v, mine);
+                            if constexpr (kMode >= 2) st4_sc1(a.logits + (size_t)bb * V + v, mine);
                             else {
                                 const float xs = mine * a.sp.inv_t;
                                 const float sc = a.sp.noise ? xs + gumbel(skey, sample_base(bb, t), v) : mine;
@@ -309,7 +316,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
                         st4_sc1(a.part_x + (size_t)w * b + bb, bx[r]); st4_sc1(a.part_m + (size_t)w * b + bb, lm[r]); st4_sc1(a.part_s + (size_t)w * b + bb, ls[r]);
                     }
                 }
-                if constexpr (kMode != 2)
+                if constexpr (kMode < 2)
                     if (lane == 0 && bb < b) { st4_sc1(a.part_val + (size_t)w * b + bb, best[r]); st4i_sc1(a.part_idx + (size_t)w * b + bb, besti[r]); }
             }
         }
@@ -361,7 +368,10 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
         // largest by the radix select, then first maximum and log-sum-exp over the kept set
         for (int bb = w; bb < b; bb += G) {
             if (t > 0 && ld4i_sc1(lead + bb) == a.eos) {                      // (uniform over the workgroup)
-                if (tid == 0) { st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, a.eos); if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, 0.f); }
+                if (tid == 0) {
+                    st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, a.eos); if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, 0.f);
+                    if constexpr (kMode == 3) if (a.nkept_tm) st4i_sc1(a.nkept_tm + (size_t)t * b + bb, 0);
+                }
                 continue;
             }
             const float* lr = a.logits + (size_t)bb * V;
@@ -370,10 +380,38 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
             for (int i = 0; i < kSelMax; ++i) { const int c = tid + i * kDecThreads; lv[i] = c < V ? ld4_sc1(lr + c) : 0.f; }
 #pragma unroll
             for (int i = 0; i < kSelMax; ++i) key[i] = order_key(lv[i]);
-            const unsigned thr = kth_largest_key([&](auto f) {
+            auto keys = [&](auto f) {
 #pragma unroll
                 for (int i = 0; i < kSelMax; ++i) if (tid + i * kDecThreads < V) f(key[i]);
-            }, (unsigned)a.sp.top_k, sel);
+            };
+            unsigned thr;
+            [[maybe_unused]] unsigned nkept = 0;
+            if constexpr (kMode == 2) thr = kth_largest_key(keys, (unsigned)a.sp.top_k, sel);
+            else {
+                // K0 = the top-k set (everything at top_k 0) without NaN; its maximum of l inv_t over the workgroup, the weights once
+                // in registers, then the largest key whose mass from the top reaches top_p of the whole
+                thr = a.sp.top_k > 0 ? kth_largest_key(keys, (unsigned)a.sp.top_k, sel) : 0u;
+                unsigned long long* msh = reinterpret_cast<unsigned long long*>(sel + kMassAt);
+                float* wmx = reinterpret_cast<float*>(msh + 260);
+                float mx = -INFINITY;
+#pragma unroll
+                for (int i = 0; i < kSelMax; ++i)
+                    if (tid + i * kDecThreads < V && lv[i] == lv[i] && key[i] >= thr) mx = fmaxf(mx, lv[i] * a.sp.inv_t);
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+                if (lane == 0) wmx[wave] = mx;
+                __syncthreads();
+#pragma unroll
+                for (int o = 0; o < kDecWaves; ++o) mx = fmaxf(mx, wmx[o]);
+                unsigned long long wt[kSelMax];
+#pragma unroll
+                for (int i = 0; i < kSelMax; ++i)
+                    wt[i] = (tid + i * kDecThreads < V && lv[i] == lv[i] && key[i] >= thr) ? mass_weight(lv[i] * a.sp.inv_t, mx) : 0ULL;
+                thr = mass_threshold_key([&](auto f) {
+#pragma unroll
+                    for (int i = 0; i < kSelMax; ++i) if (tid + i * kDecThreads < V && lv[i] == lv[i] && key[i] >= thr) f(key[i], wt[i]);
+                }, a.top_p, msh, &nkept);
+            }
             float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
             const uint64_t base = sample_base(bb, t);
 #pragma unroll
@@ -403,6 +441,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
                 }
                 st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, besti == 0x7fffffff ? 0 : besti);
                 if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, lse_logp(bx, m, s));
+                if constexpr (kMode == 3) if (a.nkept_tm) st4i_sc1(a.nkept_tm + (size_t)t * b + bb, (int)nkept);
             }
             __syncthreads();
         }
@@ -421,6 +460,8 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
         a.out_ids[i] = s < kept ? ld4i_sc1(a.ids_tm + (size_t)(s + 1) * b + bb) : a.eos;
         if constexpr (kMode != 0)            // the step that ended the loop (s == kept) holds the closing eos of the longest rows
             if (a.logp_out) a.logp_out[i] = s <= kept ? ld4_sc1(a.logp_tm + (size_t)s * b + bb) : 0.f;
+        if constexpr (kMode == 3)
+            if (a.nkept_out) a.nkept_out[i] = s <= kept ? ld4i_sc1(a.nkept_tm + (size_t)s * b + bb) : 0;
     }
     if (w == 0 && tid == 0) *a.kept = kept;
 }
@@ -446,7 +487,7 @@ static hipError_t decode_launch(hipStream_t st, DecodeArgs a, int* grid_out)
     if (nu > 2 || a.L > 8 || (a.D & 3) || a.D > 512) return hipErrorInvalidValue;
     size_t floats = (size_t)a.L * nu * 6 * a.D + (size_t)nu * a.D;
     const size_t with_e = floats + (size_t)vp * a.D;
-    const size_t extra = kMode == 2 ? kSelWords * 4 : 0;
+    const size_t extra = kMode == 2 ? kSelWords * 4 : kMode == 3 ? kSelWordsP * 4 : 0;
     a.cache_e = with_e * 4 + 64 + extra <= (size_t)lds_max - 1024 ? 1 : 0;
     if (a.cache_e) floats = with_e;
     const int lds_bytes = (int)(floats * 4 + 64 + extra);
@@ -471,6 +512,11 @@ hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out) { return d
 hipError_t decode_sample(hipStream_t st, DecodeArgs a, int* grid_out)
 {
     if (a.V > (1 << 20) || a.steps > (1 << 20) || a.sp.top_k < 0) return hipErrorInvalidValue;
+    if (a.top_p > 0.f) {                // the nucleus is on (the caller routes top_p 0 or >= 1 and the noiseless forms here with top_p 0)
+        if (!(a.top_p < 1.f) || !a.sp.noise || a.V > kSelMax * kDecThreads || !a.logits) return hipErrorInvalidValue;
+        if (a.sp.top_k >= a.V) a.sp.top_k = 0;
+        return decode_launch<3>(st, a, grid_out);
+    }
     if (a.sp.top_k == 0 || a.sp.top_k >= a.V) { a.sp.top_k = 0; return decode_launch<1>(st, a, grid_out); }
     if (a.V > kSelMax * kDecThreads || !a.logits) return hipErrorInvalidValue;
     return decode_launch<2>(st, a, grid_out);

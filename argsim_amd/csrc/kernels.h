@@ -248,6 +248,11 @@ struct SampleParams { float inv_t; int top_k; int noise; uint64_t seed; };
 // at this step, a row fed eos at t > 0 is finished (token eos, logp 0)
 hipError_t sample_rows(hipStream_t st, const float* logits, int n, int V, int t, const SampleParams& sp, const int32_t* lead, int eos,
                        int32_t* pred, float* logp);
+// the same with a nucleus (avae_decode_sample_p): 0 < top_p < 1 and sp.noise != 0; the kept set is the smallest prefix of whole tie
+// groups of the top-k set (all of V at top_k 0) that holds top_p of its mass in the fixed-point weights of sample_dev.h;
+// nkept (n, optional): its size, 0 for a finished row.  V <= 8192 keeps the row in registers, above that it is re-read per pass
+hipError_t sample_rows_p(hipStream_t st, const float* logits, int n, int V, int t, const SampleParams& sp, float top_p, const int32_t* lead,
+                         int eos, int32_t* pred, float* logp, int32_t* nkept);
 
 // out[n] (+)= sum_m X[m, n]
 hipError_t colsum(hipStream_t st, const float* X, int M, int N, int ldx, float* out, const int32_t* m_dev);
@@ -337,11 +342,15 @@ struct DecodeArgs {
     float* logits;                                  // (b, V), top_k > 0: the step's logits for the row's owner
     float* logp_tm;                                 // (steps, b) time-major log-probabilities, or null
     float* logp_out;                                // (b, steps) result, 0 beyond a row's eos, or null
+    // nucleus (decode_sample with 0 < top_p < 1) only
+    float top_p;
+    int32_t* nkept_tm;                              // (steps, b) time-major sizes of the kept sets, or null
+    int32_t* nkept_out;                             // (b, steps) result, 0 where the row had finished, or null
 };
 // returns hipErrorInvalidValue where the geometry does not fit (D / CUs > 2 units per workgroup, LDS), the caller
 // then falls back to one launch sequence per token; *grid_out = workgroups launched
 hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out);
-// the sampled loop in the same persistent form (a.sp; finished rows emit eos).  Also refuses top_k > 0 with V > 8192
+// the sampled loop in the same persistent form (a.sp; finished rows emit eos).  Also refuses top_k > 0 or top_p > 0 with V > 8192
 hipError_t decode_sample(hipStream_t st, DecodeArgs a, int* grid_out);
 int decode_workgroups();                            // CU count of the current device (size of part_val / part_idx rows)
 

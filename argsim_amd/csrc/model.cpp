@@ -1889,8 +1889,10 @@ int avae_decode_step(avae_handle h, const int32_t* lead, const float* state_in, 
 
 // one launch sequence per token with a host check every 16 tokens: the fallback where the persistent kernel's geometry
 // does not fit (decode.hip) and the reference form for tests (option "persistent" = 0).  sp: null = the greedy loop of
-// model.py:204-219; else sampled decoding (sample_rows per token: a row that has emitted eos stays eos, logp_out optional)
-static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps)
+// model.py:204-219; else sampled decoding (sample_rows per token: a row that has emitted eos stays eos, logp_out optional); top_p > 0:
+// with the nucleus (sample_rows_p; nkept_out optional)
+static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps,
+                           float top_p = 0.f, int32_t* nkept_out = nullptr)
 {
     const int D = h->cfg.dim_emb, L = h->cfg.rnn_layers;
     Ws w;
@@ -1898,12 +1900,14 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
     const size_t sn = (size_t)L * b * D;
     float* state[2]; int32_t* ids_tm = nullptr;
     {
-        size_t need = 2 * sn * sizeof(float) + (size_t)(steps + 1) * b * sizeof(int32_t) + (sp ? (size_t)steps * b * sizeof(float) : 0);
+        size_t need = 2 * sn * sizeof(float) + (size_t)(steps + 1) * b * sizeof(int32_t) + (sp ? (size_t)steps * b * sizeof(float) : 0) +
+                      (top_p > 0.f ? (size_t)steps * b * sizeof(int32_t) : 0);
         AV_TRY(grow_scratch(h, need, "stepwise decoding: the states and ids"));
         state[0] = h->scratch; state[1] = h->scratch + sn;
         ids_tm = reinterpret_cast<int32_t*>(h->scratch + 2 * sn);
     }
     float* const logp_tm = sp ? reinterpret_cast<float*>(ids_tm + (size_t)(steps + 1) * b) : nullptr;
+    int32_t* const nkept_tm = top_p > 0.f ? reinterpret_cast<int32_t*>(logp_tm + (size_t)steps * b) : nullptr;
     AV_TRY(avae_decode_init(h, z, b, state[0]));
     std::vector<int32_t> host((size_t)(steps + 1) * b);
     for (int i = 0; i < b; ++i) host[i] = h->cfg.bos;
@@ -1917,7 +1921,11 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
             if (!sp) AV_TRY(decode_step_ws(h, w, ids_tm + (size_t)t * b, state[cur], b, ids_tm + (size_t)(t + 1) * b, state[cur ^ 1]));
             else {
                 AV_TRY(decode_logits_ws(h, w, ids_tm + (size_t)t * b, state[cur], b, state[cur ^ 1]));
-                AV_CHECK(sample_rows(h->stream, w.logits, b, h->cfg.dim_tgt, t, *sp, ids_tm + (size_t)t * b, h->cfg.eos, ids_tm + (size_t)(t + 1) * b, logp_tm + (size_t)t * b));
+                if (top_p > 0.f)
+                    AV_CHECK(sample_rows_p(h->stream, w.logits, b, h->cfg.dim_tgt, t, *sp, top_p, ids_tm + (size_t)t * b, h->cfg.eos, ids_tm + (size_t)(t + 1) * b,
+                                           logp_tm + (size_t)t * b, nkept_tm + (size_t)t * b));
+                else
+                    AV_CHECK(sample_rows(h->stream, w.logits, b, h->cfg.dim_tgt, t, *sp, ids_tm + (size_t)t * b, h->cfg.eos, ids_tm + (size_t)(t + 1) * b, logp_tm + (size_t)t * b));
             }
             cur ^= 1;
         }
@@ -1938,22 +1946,35 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
     for (int s = 0; s < kept; ++s) for (int i = 0; i < b; ++i) outv[(size_t)i * steps + s] = host[(size_t)(s + 1) * b + i];
     AV_CHECK(hipMemcpyAsync(out_ids, outv.data(), outv.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     std::vector<float> lpv;
-    if (sp && logp_out) {        // the same transpose; position `kept` holds the closing eos of the longest rows, 0 beyond
-        const int nl = std::min(kept + 1, steps);
-        std::vector<float> lp((size_t)nl * b);
-        AV_CHECK(hipMemcpyAsync(lp.data(), logp_tm, lp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    std::vector<int32_t> nkv;
+    const bool want_lp = sp && logp_out, want_nk = nkept_tm && nkept_out;
+    if (want_lp || want_nk) {    // the same transpose; position `kept` holds the closing eos of the longest rows, 0 beyond (a finished row's
+        const int nl = std::min(kept + 1, steps);      // logp 0 and nkept 0 are already there); both arrays come back under one synchronise
+        std::vector<float> lp(want_lp ? (size_t)nl * b : 0);
+        std::vector<int32_t> nk(want_nk ? (size_t)nl * b : 0);
+        if (want_lp) AV_CHECK(hipMemcpyAsync(lp.data(), logp_tm, lp.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (want_nk) AV_CHECK(hipMemcpyAsync(nk.data(), nkept_tm, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         AV_CHECK(hipStreamSynchronize(h->stream));
-        lpv.assign((size_t)b * steps, 0.f);
-        for (int s = 0; s < nl; ++s) for (int i = 0; i < b; ++i) lpv[(size_t)i * steps + s] = lp[(size_t)s * b + i];
-        AV_CHECK(hipMemcpyAsync(logp_out, lpv.data(), lpv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if (want_lp) {
+            lpv.assign((size_t)b * steps, 0.f);
+            for (int s = 0; s < nl; ++s) for (int i = 0; i < b; ++i) lpv[(size_t)i * steps + s] = lp[(size_t)s * b + i];
+            AV_CHECK(hipMemcpyAsync(logp_out, lpv.data(), lpv.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        }
+        if (want_nk) {
+            nkv.assign((size_t)b * steps, 0);
+            for (int s = 0; s < nl; ++s) for (int i = 0; i < b; ++i) nkv[(size_t)i * steps + s] = nk[(size_t)s * b + i];
+            AV_CHECK(hipMemcpyAsync(nkept_out, nkv.data(), nkv.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+        }
     }
     AV_CHECK(hipStreamSynchronize(h->stream));
     if (n_steps) *n_steps = kept;
     return check_gru_err(h);
 }
 
-// the greedy (sp null) or sampled loop: one persistent launch where it serves, else the launch-per-token loop
-static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps)
+// the greedy (sp null) or sampled loop: one persistent launch where it serves, else the launch-per-token loop.  top_p > 0: the
+// nucleus is on (0 < top_p < 1, sp->noise), nkept_out optional
+static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps,
+                       float top_p = 0.f, int32_t* nkept_out = nullptr)
 {
     if (!h) return 1;
     AV_TRY(check_bound(h));
@@ -1962,16 +1983,17 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     // measured at D = 512, V = 8192, steps = 512 (scripts/decode_bench.py, profiles/r03_decode_bench.txt): the persistent launch
     // takes 42 / 74 / 145 us per token at b = 1 / 16 / 64, the launch-per-token loop 116-130 us at any b <= 128 (its
     // GEMMs are far from full): one launch up to 32 rows, the per-token loop above
-    if (!h->persistent || b > 32) return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps);
+    if (!h->persistent || b > 32) return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps, top_p, nkept_out);
     // the whole loop in ONE persistent launch (decode.hip); state, partial maxima and the id log live in the scratch buffer
     const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
     const int G = decode_workgroups();
     if (G < 1) return fail(h, "no HIP device");
     const size_t sn = (size_t)L * b * D;
-    const bool topk = sp && sp->top_k > 0;
+    const bool topk = sp && (sp->top_k > 0 || top_p > 0.f);          // the owner of a row reads its logits from the scratch
+    const bool want_nk = top_p > 0.f && nkept_out;
     const size_t nfs = sp ? 3 * (size_t)G * b + (topk ? (size_t)b * V : 0) + (logp_out ? (size_t)steps * b : 0) : 0;     // sampled: part_x/m/s, logits, logp_tm
     const size_t nf = 2 * sn + (size_t)b * D + (size_t)G * b + nfs;                           // floats: state x2, o, part_val
-    const size_t ni = (size_t)G * b + (size_t)(steps + 1) * b + 16;                            // ints: part_idx, ids_tm, kept, barrier
+    const size_t ni = (size_t)G * b + (size_t)(steps + 1) * b + 16 + (want_nk ? (size_t)steps * b : 0);      // ints: part_idx, ids_tm, kept, barrier, nkept_tm
     const size_t need = (nf + ni) * 4;
     AV_TRY(grow_scratch(h, need, "decoding in one launch: the states, partial results and ids"));
     DecodeArgs a{};
@@ -1990,6 +2012,8 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     int32_t* ip = reinterpret_cast<int32_t*>(h->scratch + nf);
     a.part_idx = ip; a.ids_tm = ip + (size_t)G * b;
     a.kept = a.ids_tm + (size_t)(steps + 1) * b; a.bar = reinterpret_cast<unsigned*>(a.kept + 8);
+    a.top_p = top_p;
+    if (want_nk) { a.nkept_tm = a.kept + 16; a.nkept_out = nkept_out; }
     a.out_ids = out_ids; a.err = h->errw;
     a.b = b; a.steps = steps; a.D = D; a.V = V; a.L = L; a.eos = h->cfg.eos; a.isd = 1.f / sqrtf((float)D);
     AV_TRY(avae_decode_init(h, z, b, a.state[0]));
@@ -2000,7 +2024,7 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     hipError_t e = sp ? decode_sample(h->stream, a, &grid) : decode_greedy(h->stream, a, &grid);
     if (e == hipErrorInvalidValue) {                       // geometry outside the persistent kernel: same results, more launches
         AV_CHECK(hipStreamSynchronize(h->stream));           // (bos.data() is still being read)
-        return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps);
+        return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps, top_p, nkept_out);
     }
     if (e == hipErrorCooperativeLaunchTooLarge) return fail(h, "persistent decode kernel: one workgroup per CU does not fit this device");
     AV_CHECK(e);
@@ -2049,6 +2073,53 @@ int avae_debug_sample_rows(avae_handle h, const float* logits, int n, int V, int
     if (!sample_params(h, sc, V, &sp)) return 1;
     if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
     AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, nullptr, h->cfg.eos, pred, logp));
+    return 0;
+}
+
+// avae_sample_p_config -> the kernels' parameters and *top_p: the nucleus share, 0 where the nucleus is off (top_p 0 or >= 1,
+// temperature 0, top_k 1: the call is avae_decode_sample's); false with the message set
+static bool sample_params_p(avae_handle h, const avae_sample_p_config* sc, int V, SampleParams* sp, float* top_p)
+{
+    if (!sc) { fail(h, "sample config is null"); return false; }
+    const avae_sample_config base{sc->temperature, sc->top_k, sc->seed};
+    if (!sample_params(h, &base, V, sp)) return false;
+    if (!(sc->top_p >= 0.f)) { fail(h, "sample: top_p must be a number >= 0"); return false; }
+    if (sc->reserved != 0) { fail(h, "sample: the reserved field must be 0"); return false; }
+    *top_p = sp->noise && sc->top_p > 0.f && sc->top_p < 1.f ? sc->top_p : 0.f;
+    return true;
+}
+
+int avae_decode_sample_p(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_p_config* sc,
+                         int32_t* out_ids, float* logp_out, int32_t* nkept_out, int32_t* n_steps)
+{
+    if (!h) return 1;
+    SampleParams sp{};
+    float top_p = 0.f;
+    if (!sample_params_p(h, sc, h->cfg.dim_tgt, &sp, &top_p)) return 1;
+    if (steps > (1 << 20)) return fail(h, "sample: the noise index holds 2^20 steps");
+    AV_TRY(decode_loop(h, z, b, steps, &sp, out_ids, logp_out, n_steps, top_p, nkept_out));
+    if (top_p == 0.f && nkept_out) {            // nucleus off: avae_decode_sample's own path above; there is no nucleus to size
+        AV_CHECK(hipMemsetAsync(nkept_out, 0xff, (size_t)b * steps * sizeof(int32_t), h->stream));
+        AV_CHECK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
+}
+
+// test hook: sample_rows_p on caller buffers at step t0, row index = batch row; lead (n, optional) as sample_rows_p takes it.  With the
+// nucleus off it is avae_debug_sample_rows and nkept is filled with -1
+int avae_debug_sample_rows_p(avae_handle h, const float* logits, int n, int V, int t0, const avae_sample_p_config* sc, int32_t* pred, float* logp,
+                             int32_t* nkept, const int32_t* lead)
+{
+    if (!h) return 1;
+    SampleParams sp{};
+    float top_p = 0.f;
+    if (!sample_params_p(h, sc, V, &sp, &top_p)) return 1;
+    if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
+    if (top_p > 0.f) AV_CHECK(sample_rows_p(h->stream, logits, n, V, t0, sp, top_p, lead, h->cfg.eos, pred, logp, nkept));
+    else {
+        AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, lead, h->cfg.eos, pred, logp));
+        if (nkept) AV_CHECK(hipMemsetAsync(nkept, 0xff, (size_t)n * sizeof(int32_t), h->stream));
+    }
     return 0;
 }
 

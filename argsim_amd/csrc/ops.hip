@@ -1121,6 +1121,105 @@ hipError_t sample_rows(hipStream_t st, const float* logits, int n, int V, int t,
     return hipGetLastError();
 }
 
+// sample_rows with a nucleus (avae_decode_sample_p): K0 = the top-k set (all of V at top_k 0) without NaN, the maximum of l inv_t over
+// it, the fixed-point weights under that maximum, the mass select of sample_dev.h, then sample_rows' merge over the final set.
+// kReg: V <= 8192, the row's logits and weights stay in registers across the passes (32 per thread; beam_rows showed what a re-read
+// per pass costs); else every pass streams the row and forms the weights again.  An id beyond V reads as NaN: absent everywhere.
+constexpr int kRowRegs = 32;
+template <bool kReg>
+__global__ __launch_bounds__(256) void sample_rows_p_kernel(const float* __restrict__ logits, int n, int V, int t, SampleParams sp, float top_p,
+                                                            const int32_t* __restrict__ lead, int eos,
+                                                            int32_t* __restrict__ pred, float* __restrict__ logp, int32_t* __restrict__ nkept)
+{
+    __shared__ unsigned s_sel[258];
+    __shared__ unsigned long long s_mass[260];
+    __shared__ float s_f[4][4]; __shared__ int s_i[4]; __shared__ float s_mx[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t key = sample_key(sp.seed);
+    for (int row = blockIdx.x; row < n; row += gridDim.x) {
+        if (lead && t > 0 && lead[row] == eos) {                  // (uniform over the workgroup)
+            if (tid == 0) { pred[row] = eos; if (logp) logp[row] = 0.f; if (nkept) nkept[row] = 0; }
+            continue;
+        }
+        const float* x = logits + (size_t)row * V;
+        [[maybe_unused]] float lv[kReg ? kRowRegs : 1];
+        [[maybe_unused]] unsigned long long wt[kReg ? kRowRegs : 1];
+        if constexpr (kReg) {
+#pragma unroll
+            for (int i = 0; i < kRowRegs; ++i) { const int c = tid + i * 256; lv[i] = c < V ? x[c] : __int_as_float(0x7fc00000); }
+        }
+        // f(i, c, l) for every logit of this thread that is a number
+        auto each = [&](auto f) {
+            if constexpr (kReg) {
+#pragma unroll
+                for (int i = 0; i < kRowRegs; ++i) if (lv[i] == lv[i]) f(i, tid + i * 256, lv[i]);
+            } else {
+                for (int c = tid; c < V; c += 256) { const float l = x[c]; if (l == l) f(0, c, l); }
+            }
+        };
+        unsigned thr = 0;
+        if (sp.top_k > 0 && sp.top_k < V)
+            thr = kth_largest_key([&](auto f) { each([&](int, int, float l) { f(order_key(l)); }); }, (unsigned)sp.top_k, s_sel);
+        float mx = -INFINITY;
+        each([&](int, int, float l) { if (order_key(l) >= thr) mx = fmaxf(mx, l * sp.inv_t); });
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        if (lane == 0) s_mx[wave] = mx;
+        __syncthreads();
+        mx = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+        if constexpr (kReg) {
+#pragma unroll
+            for (int i = 0; i < kRowRegs; ++i) wt[i] = mass_weight(lv[i] * sp.inv_t, mx);      // (only read where the logit is in K0)
+        }
+        unsigned nk = 0;
+        thr = mass_threshold_key([&](auto f) {
+            each([&](int i, int, float l) {
+                const unsigned k = order_key(l);
+                if (k < thr) return;
+                if constexpr (kReg) f(k, wt[i]); else f(k, mass_weight(l * sp.inv_t, mx));
+            });
+        }, top_p, s_mass, &nk);
+        const uint64_t base = sample_base(row, t);
+        float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
+        each([&](int, int c, float l) {
+            if (order_key(l) < thr) return;
+            const float xs = l * sp.inv_t;
+            const float sc = xs + gumbel(key, base, c);
+            if (sc > best) { best = sc; besti = c; bx = xs; }      // ascending c: the first maximum stays
+            lse_add(m, s, xs);
+        });
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+            const int oi = __shfl_xor(besti, o, 64);
+            if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
+            lse_merge(m, s, om, os);
+        }
+        if (lane == 0) { s_f[wave][0] = best; s_f[wave][1] = bx; s_f[wave][2] = m; s_f[wave][3] = s; s_i[wave] = besti; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < 4; ++w) {
+                if (cand_better(s_f[w][0], s_i[w], best, besti)) { best = s_f[w][0]; besti = s_i[w]; bx = s_f[w][1]; }
+                lse_merge(m, s, s_f[w][2], s_f[w][3]);
+            }
+            const bool none = besti == 0x7fffffff;
+            pred[row] = none ? 0 : besti;
+            if (logp) logp[row] = none ? __int_as_float(0x7fc00000) : lse_logp(bx, m, s);
+            if (nkept) nkept[row] = (int)nk;
+        }
+        __syncthreads();                                          // s_f, s_i and s_mx are free for the next row
+    }
+}
+hipError_t sample_rows_p(hipStream_t st, const float* logits, int n, int V, int t, const SampleParams& sp, float top_p, const int32_t* lead,
+                         int eos, int32_t* pred, float* logp, int32_t* nkept)
+{
+    if (n <= 0) return hipSuccess;
+    if (V < 1 || V > (1 << 20) || t < 0 || t >= (1 << 20) || sp.top_k < 0 || !sp.noise || !(top_p > 0.f && top_p < 1.f)) return hipErrorInvalidValue;
+    if (V <= kRowRegs * 256)
+        hipLaunchKernelGGL(sample_rows_p_kernel<true>, dim3(min(n, 4096)), dim3(256), 0, st, logits, n, V, t, sp, top_p, lead, eos, pred, logp, nkept);
+    else
+        hipLaunchKernelGGL(sample_rows_p_kernel<false>, dim3(min(n, 4096)), dim3(256), 0, st, logits, n, V, t, sp, top_p, lead, eos, pred, logp, nkept);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- column sums (bias gradients)
 // block = 64 columns x 4 row lanes; grid.y chunks of `chunk` rows, sized so that ~1024 workgroups share the rows (with
 // 1024-row chunks the 16 640 x 512 sum ran on 136 workgroups of 256 dependent loads each: 62 us for 34 MB); float atomics

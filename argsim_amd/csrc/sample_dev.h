@@ -1,7 +1,8 @@
 // sample_dev.h -- device helpers shared by the two samplers (decode.hip: the persistent launch; ops.hip: sample_rows):
 // the counter RNG's mixer, the Gumbel noise of stream 3, order-preserving keys with a workgroup radix select of the
-// k-th largest, and the running (max, sum exp) pair of a log-sum-exp.  The contract is in include/argsim_vae.h
-// (avae_decode_sample); both samplers and the float64 reference of tests/sampling_ref.py implement exactly it.
+// k-th largest and one by probability mass (the nucleus), and the running (max, sum exp) pair of a log-sum-exp.  The
+// contract is in include/argsim_vae.h (avae_decode_sample, avae_decode_sample_p); both samplers and the float64
+// references of tests/sampling_ref.py and tests/nucleus_ref.py implement exactly it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -85,6 +86,66 @@ __device__ __forceinline__ unsigned kth_largest_key(Each each, unsigned k, unsig
         prefix |= sh[256] << shift; mask |= 255u << shift; k = sh[257];
     }
     if (need) { *need = k; *ties = sh[prefix & 255u]; __syncthreads(); }      // (the last pass' histogram: keys that share the top 24 bits, by their low 8)
+    return prefix;
+}
+
+// nucleus (top-p) sampling, contract in include/argsim_vae.h (avae_decode_sample_p): the fixed-point weight of a token whose
+// scaled logit is x under the kept set's maximum m: floor(exp(x - m) 2^40), the maximum itself exactly 2^40 without an
+// exponential (the lse_add convention: +inf weighs 2^40 and everything beside it 0).  Integer weights sum to the same
+// total in any order: the mass select below is bit-reproducible without a fixed reduction tree.
+__device__ __forceinline__ unsigned long long mass_weight(float x, float m)
+{
+    return x == m ? (1ULL << 40) : (unsigned long long)(expf(x - m) * 1099511627776.f);
+}
+
+// the sibling of kth_largest_key that selects by MASS: the largest key with (sum of the weights of the keys >= it) >= need,
+// need = ceil(top_p W) clamped to [1, W], W = the sum of all weights.  The same 4 passes of 8 bits from the top; the 256
+// bins hold 64-bit weight sums (64-bit integer LDS atomics), the 64-lane suffix scan runs over them, and the pass ends in
+// the bin in which the running mass crosses need, less the mass above that bin.  each(f) calls f(key, weight) for every
+// member of THIS thread (the caller leaves out what is not in the set: NaN, below the top-k threshold); sh: 260 x 8 bytes
+// of LDS.  Every thread of the workgroup must call it; all return the same key and *nkept = how many members have a key
+// >= it (0 for an empty set, whose key is 0).  Ends in a barrier: sh is free again at once.
+template <class Each>
+__device__ __forceinline__ unsigned mass_threshold_key(Each each, float top_p, unsigned long long* sh, unsigned* nkept)
+{
+    const int tid = threadIdx.x, nth = blockDim.x;
+    unsigned prefix = 0, mask = 0;
+    unsigned long long need = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int i = tid; i < 256; i += nth) sh[i] = 0;
+        if (tid == 0) sh[258] = 0;
+        __syncthreads();
+        each([&](unsigned key, unsigned long long w) { if (w != 0 && (key & mask) == prefix) atomicAdd(&sh[(key >> shift) & 255u], w); });
+        __syncthreads();
+        if (tid < 64) {                         // lane i owns bins 4 i .. 4 i + 3; suffix sums run from the top bin down
+            const unsigned long long c0 = sh[4 * tid], c1 = sh[4 * tid + 1], c2 = sh[4 * tid + 2], c3 = sh[4 * tid + 3];
+            unsigned long long suf = c0 + c1 + c2 + c3;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned long long v = __shfl_down(suf, o, 64); if (tid + o < 64) suf += v; }
+            if (shift == 24) {                  // lane 0's suffix is the whole mass W
+                const unsigned long long W = __shfl(suf, 0, 64);
+                const double dn = ceil((double)top_p * (double)W);
+                need = !(dn >= 1.0) ? 1ULL : (dn >= (double)W ? W : (unsigned long long)dn);
+                if (W == 0) { need = 0; if (tid == 0) { sh[256] = 0; sh[257] = 0; } }      // nothing in the set: key 0, nobody crosses
+            }
+            unsigned long long above = suf - (c0 + c1 + c2 + c3);       // mass in bins above this lane's
+            if (above < need && need <= suf) {                            // exactly one lane: the mass crosses need inside its bins
+                int bin = 4 * tid + 3;
+                if (above + c3 < need) { above += c3; bin = 4 * tid + 2;
+                    if (above + c2 < need) { above += c2; bin = 4 * tid + 1;
+                        if (above + c1 < need) { above += c1; bin = 4 * tid; } } }
+                sh[256] = (unsigned long long)bin; sh[257] = need - above;
+            }
+        }
+        __syncthreads();
+        prefix |= (unsigned)sh[256] << shift; mask |= 255u << shift; need = sh[257];
+    }
+    unsigned cnt = 0;
+    each([&](unsigned key, unsigned long long) { cnt += key >= prefix ? 1u : 0u; });
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((tid & 63) == 0 && cnt) atomicAdd(reinterpret_cast<unsigned*>(&sh[258]), cnt);      // (sh[258] was zeroed before the last pass' barriers)
+    __syncthreads();
+    *nkept = *reinterpret_cast<unsigned*>(&sh[258]);
+    __syncthreads();
     return prefix;
 }
 

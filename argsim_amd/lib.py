@@ -40,6 +40,10 @@ class AvaeSampleConfig(C.Structure):
     _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64)]
 
 
+class AvaeSamplePConfig(C.Structure):
+    _fields_ = [('temperature', C.c_float), ('top_k', C.c_int32), ('seed', C.c_uint64), ('top_p', C.c_float), ('reserved', C.c_int32)]
+
+
 class AvaeBeamConfig(C.Structure):
     _fields_ = [('width', C.c_int32), ('length_alpha', C.c_float)]
 
@@ -77,6 +81,7 @@ SIGNATURES = {
     'avae_decode_step': (C.c_int, [_P, _P, _P, C.c_int32, _P, _P]),
     'avae_decode_greedy': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     'avae_decode_sample': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSampleConfig), _P, _P, C.POINTER(C.c_int32)]),
+    'avae_decode_sample_p': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSamplePConfig), _P, _P, _P, C.POINTER(C.c_int32)]),
     'avae_decode_beam': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeBeamConfig), _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     'avae_score': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AvaeScoreConfig), _P, _P, _P, _P, _P, _P]),
     'avae_score_z': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
@@ -89,6 +94,7 @@ SIGNATURES = {
     'avae_debug_softmax_ce': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.POINTER(C.c_int)]),
     'avae_debug_argmax_rows': (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     'avae_debug_sample_rows': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AvaeSampleConfig), _P, _P]),
+    'avae_debug_sample_rows_p': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AvaeSamplePConfig), _P, _P, _P, _P]),
     'avae_debug_beam_select': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
     'avae_timing_collect': (C.c_int, [_P, C.POINTER(C.c_double)]),
     'avae_debug_timing': (C.c_int, [_P, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]),

@@ -324,12 +324,16 @@ class VAE:
         return out[:, :n.value].cpu().numpy()
 
 
-    def sample(self, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
+    def sample(self, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False, top_p=0.0, return_nkept=False):
         """sampled decoding (include/argsim_vae.h, avae_decode_sample): array i32 (b, t<=steps) drawn from softmax(logits / temperature)
         over the top_k most likely pieces (0: all), reproducible from seed; a row is eos from its first eos on.  temperature 0 or
         top_k 1 is the argmax.  With return_logp also f32 (b, min(t + 1, steps)): the log-probability of every token, the closing eos
-        included (column t for the longest rows), 0 behind it -- a row's sum is the log-probability of its sentence."""
+        included (column t for the longest rows), 0 behind it -- a row's sum is the log-probability of its sentence.
+        0 < top_p < 1 (avae_decode_sample_p): of those pieces only the nucleus, the most likely ones that hold top_p of the mass; 0 or
+        >= 1 is off.  With return_nkept also i32, shaped as logp: the size of the kept set at every position, 0 behind a row's eos,
+        -1 everywhere when the nucleus is off."""
         steps, top_k, seed = _check_sample_args(steps, temperature, top_k, seed)
+        top_p = _check_top_p(top_p)
         z = torch.as_tensor(np.ascontiguousarray(z, dtype=np.float32)).to(self.device)
         if z.dim() != 2 or z.shape[1] != self.cfg['dim_rep'] or z.shape[0] < 1:
             raise ValueError("z must be (b, dim_rep) with b >= 1, got %s" % (tuple(z.shape),))
@@ -337,12 +341,23 @@ class VAE:
         out = torch.empty((b, steps), dtype=torch.int32, device=self.device)
         logp = torch.empty((b, steps), dtype=torch.float32, device=self.device) if return_logp else None
         n = C.c_int32()
-        sc = _lib.AvaeSampleConfig(float(temperature), top_k, seed)
         self._stream()
-        self._ck(self._l.avae_decode_sample(self._h, C.c_void_p(z.data_ptr()), b, steps, C.byref(sc), C.c_void_p(out.data_ptr()),
-                                            C.c_void_p(logp.data_ptr()) if return_logp else None, C.byref(n)))
-        ids = out[:, :n.value].cpu().numpy()
-        return (ids, logp[:, :min(n.value + 1, steps)].cpu().numpy()) if return_logp else ids
+        if 0.0 < top_p < 1.0 or return_nkept:
+            nkept = torch.empty((b, steps), dtype=torch.int32, device=self.device) if return_nkept else None
+            sc = _lib.AvaeSamplePConfig(float(temperature), top_k, seed, top_p, 0)
+            self._ck(self._l.avae_decode_sample_p(self._h, C.c_void_p(z.data_ptr()), b, steps, C.byref(sc), C.c_void_p(out.data_ptr()),
+                                                  C.c_void_p(logp.data_ptr()) if return_logp else None,
+                                                  C.c_void_p(nkept.data_ptr()) if return_nkept else None, C.byref(n)))
+        else:
+            sc = _lib.AvaeSampleConfig(float(temperature), top_k, seed)
+            self._ck(self._l.avae_decode_sample(self._h, C.c_void_p(z.data_ptr()), b, steps, C.byref(sc), C.c_void_p(out.data_ptr()),
+                                                C.c_void_p(logp.data_ptr()) if return_logp else None, C.byref(n)))
+        res = [out[:, :n.value].cpu().numpy()]
+        if return_logp:
+            res.append(logp[:, :min(n.value + 1, steps)].cpu().numpy())
+        if return_nkept:
+            res.append(nkept[:, :min(n.value + 1, steps)].cpu().numpy())
+        return tuple(res) if len(res) > 1 else res[0]
 
     def beam(self, z, steps=256, width=4, length_alpha=0.0, return_all=False):
         """beam-search decoding (include/argsim_vae.h, avae_decode_beam): the `width` best continuations per sentence, ranked by
@@ -377,13 +392,14 @@ class VAE:
         return dict(ids=out[:, :, :n].cpu().numpy(), score=score.cpu().numpy(), cum=cum.cpu().numpy(), len=ln.cpu().numpy(), n=n,
                     lat_parent=lp[:n].cpu().numpy(), lat_token=lt[:n].cpu().numpy(), lat_cum=lc[:n].cpu().numpy())
 
-    def generate(self, n, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
+    def generate(self, n, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False, top_p=0.0):
         """n sentences from the prior: z ~ N(0, I) drawn on the host with np.random.default_rng(seed), then sample() with the same seed"""
         if int(n) != n or n < 1:
             raise ValueError("n must be an integer >= 1, got %r" % (n,))
         _check_sample_args(steps, temperature, top_k, seed)
+        _check_top_p(top_p)
         z = np.random.default_rng(seed).standard_normal((int(n), self.cfg['dim_rep'])).astype(np.float32)
-        return self.sample(z, steps, temperature, top_k, seed, return_logp)
+        return self.sample(z, steps, temperature, top_k, seed, return_logp, top_p)
 
 
     # ------------------------------------------------------------------ likelihood
@@ -459,6 +475,16 @@ def _check_sample_args(steps, temperature, top_k, seed):
     return int(steps), int(top_k), int(seed)
 
 
+def _check_top_p(top_p):
+    """the rule of avae_decode_sample_p for top_p, checked before anything touches the device -> float (0 or >= 1: the nucleus is off)"""
+    if isinstance(top_p, bool):
+        raise ValueError("top_p must be a number >= 0, got %r" % (top_p,))
+    p = float(top_p)
+    if not p >= 0.0:
+        raise ValueError("top_p must be a number >= 0, got %r" % (top_p,))
+    return p
+
+
 def _check_beam_args(steps, width, length_alpha):
     """the argument rules of avae_decode_beam, checked before anything touches the device -> (steps, width, length_alpha)"""
     if isinstance(steps, bool) or int(steps) != steps or not 1 <= steps <= 1 << 20:
@@ -487,9 +513,9 @@ def decode(vae, z, steps=256):
     return vae.decode(z, steps)
 
 
-def sample(vae, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False):
+def sample(vae, z, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False, top_p=0.0):
     """sampled counterpart of decode(): VAE.sample"""
-    return vae.sample(z, steps, temperature, top_k, seed, return_logp)
+    return vae.sample(z, steps, temperature, top_k, seed, return_logp, top_p)
 
 
 def beam(vae, z, steps=256, width=4, length_alpha=0.0, return_all=False):

@@ -169,6 +169,37 @@ typedef struct avae_sample_config { float temperature; int32_t top_k; uint64_t s
 int  avae_decode_sample(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_config* sc,
                         int32_t* out_ids, float* logp_out, int32_t* n_steps);
 
+/* ---- nucleus (top-p) sampling ------------------------------------------------------------ */
+/* avae_decode_sample with a nucleus, alone or after top-k.  noise (stream 3), the top-k rule, the Gumbel-max token, the
+ * finished-row rule, the end of the loop, out_ids, logp_out and *n_steps are exactly avae_decode_sample's.  New, for batch
+ * row r at step t, with l[v] the tied logits:
+ *   K0      the set top-k keeps, or all of V when top-k is off; a NaN logit is absent.
+ *   weights x[v] = l[v] * (1 / temperature) in fp32, as the sampler forms it; m = max x over K0;
+ *           w[v] = (uint64) floor(expf(x[v] - m) 2^40), and x[v] == m gives exactly 2^40 without an exponential (the
+ *           convention of the sampler's log-sum-exp: a +inf logit weighs 2^40 and everything beside it 0; a row of -inf only
+ *           weighs 2^40 each).  A token more than about 27.7 below the maximum weighs 0.
+ *   mass    W = sum of w over K0, an integer: the same in any order of summation (no float atomics anywhere);
+ *           need = (uint64) ceil((double) top_p * (double) W), clamped to [1, W].
+ *   nucleus tau = the largest logit value among K0 with (sum of w[v] over l[v] >= tau) >= need; kept = {v in K0 : l[v] >= tau}.
+ *           Ties at tau are all kept, as top-k keeps them; the first maximum is always kept.
+ *   token   the first maximum of x + g over the kept set; logp = the log-softmax of x over the kept set at the token.
+ *   nkept   nkept_out, optional (b, steps) int32 device: the size of the kept set at every emitted position, the closing eos
+ *           included; 0 where the row had already finished and beyond column *n_steps.
+ *   off     top_p == 0, top_p >= 1, temperature == 0 or top_k == 1: the call IS avae_decode_sample with the first three fields
+ *           (the very same kernels: out_ids and logp_out are bit-equal); nkept_out, if given, is filled with -1.
+ * Errors: a null sc, a negative or NaN top_p, reserved != 0, and everything avae_decode_sample refuses.
+ * One persistent launch up to 32 rows with dim_tgt <= 8192, else one launch sequence per token (dim_tgt > 8192 is no error).
+ * expf is the device's: the two paths and the float64 reference of tests/nucleus_ref.py agree on the kept set wherever the
+ * boundary is further from top_p than the measured tolerance.                                           */
+typedef struct avae_sample_p_config { float temperature; int32_t top_k; uint64_t seed; float top_p; int32_t reserved; } avae_sample_p_config;
+int  avae_decode_sample_p(avae_handle h, const float* z, int32_t b, int32_t steps, const avae_sample_p_config* sc,
+                          int32_t* out_ids, float* logp_out, int32_t* nkept_out, int32_t* n_steps);
+/* test hook: the per-token nucleus kernel alone on caller logits (n, V) device at step t0, row index = batch row: pred (n) int32,
+ * logp (n) float and nkept (n) int32 device, the last two optional; lead (n) int32 device, optional: the ids fed at this step, a row
+ * fed eos at t0 > 0 is finished (token eos, logp 0, nkept 0)                                                              */
+int  avae_debug_sample_rows_p(avae_handle h, const float* logits, int n, int V, int t0, const avae_sample_p_config* sc,
+                              int32_t* pred, float* logp, int32_t* nkept, const int32_t* lead);
+
 /* ---- beam-search decoding --------------------------------------------------------------- */
 /* The third decoder beside avae_decode_greedy and avae_decode_sample: the `width` best continuations per sentence, on the device,
  * on the launch-per-token path (the b x width hypotheses are the decoder's batch rows).  For sentence r, step t (0-based) and the

@@ -1,5 +1,6 @@
 """greedy decoding, steps = 512 (explore_centroids.py:40): persistent launch vs one launch sequence per token.
---sample adds sampled decoding (temperature 1, top_k 0 and 40) at the same batch sizes on both paths.
+--sample adds sampled decoding (temperature 1, top_k 0 and 40, then the nucleus top_p 0.9 alone and after top_k 40) at the same batch
+sizes on both paths.
 --beam instead: beam search at (b, width) = (1, 4), (16, 4), (1, 16) against the launch-per-token greedy loop (persistent = 0) at
 b * width rows -- the same decoder work without select and gather -- in us per step, HIP events, three runs each (median, min - max)"""
 import os, sys, time
@@ -56,6 +57,8 @@ legs = [('greedy', lambda z: m.decode(z, steps=steps))]
 if '--sample' in sys.argv[1:]:
     for k in (0, 40):
         legs.append(('sample k=%d' % k, lambda z, k=k: m.sample(z, steps=steps, temperature=1.0, top_k=k, seed=1)))
+    for k in (0, 40):
+        legs.append(('k=%d p=0.9' % k, lambda z, k=k: m.sample(z, steps=steps, temperature=1.0, top_k=k, seed=1, top_p=0.9)))
 for b in (1, 16, 64, 128):
     z = np.random.default_rng(b).standard_normal((b, 128)).astype(np.float32)
     for mode in (1, 0):
