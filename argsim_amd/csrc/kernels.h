@@ -321,6 +321,23 @@ struct BeamEnd {
 };
 hipError_t beam_backtrack(hipStream_t st, const BeamEnd& a);
 
+// ---------------------------------------------------------------- nearest-neighbour search (knn.hip)
+// the k best bank rows per query row under a similarity (contract: include/argsim_vae.h, avae_knn): q (n, dim), bank (N, dim) fp32
+// row-major, 16-byte aligned, dim a multiple of 4 in 4..1024; out_idx (n, k) int64, out_score (n, k); carry: the outputs hold an
+// earlier call's list, merged in.  N <= 2^31 - 256.
+struct KnnArgs {
+    const float* q; const float* bank;
+    int n, N, dim, k, metric;             // metric: 0 dot, 1 cosine, 2 squared Euclidean (negated)
+    int64_t idx_base, self_base; int carry;
+    int64_t* out_idx; float* out_score;
+};
+// the launch shape (knn.hip, knn_plan: a pure host function of the problem shape): query tiles of qrows rows, the bank cut into
+// `parts` runs of `chunk` rows, one workgroup per (query tile, part); chunk_opt > 0 caps chunk (option knn_chunk)
+struct KnnPlan { int qrows, qtiles, parts, chunk; };
+KnnPlan knn_plan(int n, int N, int k, int chunk_opt);
+size_t knn_ws_bytes(const KnnPlan& p, int n, int N, int k);      // workspace: the rows' norms + the parts' lists (n x parts x k x 8 bytes)
+hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, void* ws);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

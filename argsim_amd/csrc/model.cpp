@@ -76,6 +76,7 @@ struct avae_ctx {
                           // step (spec_pick: RAGGED 256 x 64 10.41 -> 10.23 ms; always-on costs a FULL 100 x 512 batch 1 %, 71.5 -> 72.3 ms, and a FULL 256 x 64 nothing)
     int bwd_rs = 2;       // fp32 BPTT team kernels in the reduce-scatter form (gru_rs.hip: own gate columns x resident R slice, partial dH summed through the
                           // exchange): 0 never, 1 wherever the geometry allows, 2 auto -- where few rows are alive per step (rs_pick)
+    int knn_chunk = 0;    // avae_knn test aid: caps the bank rows one workgroup walks (small tests run many parts and the merge); 0: knn_plan decides
     int gru_bf16 = 1;     // compute_dtype 1 only: the recurrent product of the team kernels takes bf16 operands too (0: fp32 recurrence)
     // offsets
     int64_t oE = 0, oKout = 0, oBout = 0, oWmu = 0, oBmu = 0, oWlv = 0, oBlv = 0, oWex = 0, oBex = 0;
@@ -1545,6 +1546,7 @@ int avae_set_option(avae_handle h, const char* key, int value)
     if (!strcmp(key, "skip_pad")) { h->skip_pad = value != 0; return 0; }
     if (!strcmp(key, "compact")) { h->compact = value; return 0; }
     if (!strcmp(key, "skinny")) { h->skinny = value; return 0; }
+    if (!strcmp(key, "knn_chunk")) { if (value < 0) return fail(h, "knn_chunk must be >= 0"); h->knn_chunk = value; return 0; }
     if (!strcmp(key, "gru_ablate")) {
         // timing experiments that change results exist only in the diagnostic build (make DIAG=1)
         if (value && !gru_diag_build()) return fail(h, "gru_ablate needs the diagnostic build of libargsim_vae.so (make -C argsim_amd/csrc DIAG=1)");
@@ -2250,6 +2252,35 @@ int avae_debug_beam_select(avae_handle h, const float* logits, int n, int width,
     a.live = len_out + rows;
     AV_CHECK(hipMemsetAsync(a.live, 0, sizeof(int32_t), h->stream));
     AV_CHECK(beam_select(h->stream, a));
+    return 0;
+}
+
+// ---------------------------------------------------------------- nearest neighbours (contract: include/argsim_vae.h, avae_knn; kernels: knn.hip)
+int avae_knn(avae_handle h, const float* q, int32_t n, const float* bank, int32_t N, int32_t dim, const avae_knn_config* kc,
+             int64_t* out_idx, float* out_score)
+{
+    if (!h) return 1;
+    if (!kc) return fail(h, "knn config is null");
+    if (!q || !out_idx || !out_score) return fail(h, "knn: q, out_idx and out_score must be given");
+    if (n < 1 || N < 0) return fail(h, "knn: n must be >= 1 and N >= 0");
+    if (N > 0 && !bank) return fail(h, "knn: bank must be given");
+    if (N > 0x7fffffff - 256) return fail(h, "knn: at most 2^31 - 256 bank rows per call (stream a larger bank with carry)");
+    if (kc->k < 1 || kc->k > 32) return fail(h, "knn: k must be in [1, 32]");
+    if (kc->metric < 0 || kc->metric > 2) return fail(h, "knn: metric must be 0 (dot), 1 (cosine) or 2 (squared Euclidean)");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "knn: dim must be a multiple of 4 in [4, 1024]");
+    if (kc->idx_base < 0 || kc->self_base < -1) return fail(h, "knn: idx_base must be >= 0 and self_base >= -1");
+    if (kc->carry != 0 && kc->carry != 1) return fail(h, "knn: carry must be 0 or 1");
+    if (kc->reserved != 0) return fail(h, "knn: the reserved field must be 0");
+    if (((uintptr_t)q | (uintptr_t)bank) & 15) return fail(h, "knn: q and bank must be 16-byte aligned");
+    AV_CHECK(hipSetDevice(h->device));
+    const KnnPlan p = knn_plan(n, N, kc->k, h->knn_chunk);
+    if ((long long)p.qtiles * std::max(p.parts, 1) > 0x7fffffffLL) return fail(h, "knn: too many (query tile, bank part) workgroups for one launch");
+    const size_t need = knn_ws_bytes(p, n, N, kc->k);
+    AV_TRY(reserve_ws(h, need + 4096));                          // sized once per call; nothing is allocated between the launches
+    KnnArgs a{};
+    a.q = q; a.bank = bank; a.n = n; a.N = N; a.dim = dim; a.k = kc->k; a.metric = kc->metric;
+    a.idx_base = kc->idx_base; a.self_base = kc->self_base; a.carry = kc->carry; a.out_idx = out_idx; a.out_score = out_score;
+    AV_CHECK(knn_search(h->stream, a, p, h->ws));
     return 0;
 }
 

@@ -6,6 +6,8 @@ Writes the two arrays those scripts write, with the same shapes and dtype, so th
 untouched eval_classification*.py / eval_clustering*.py consume them:
     <out>.npy          (n, dim_rep) float32   z = mu of the deterministic segmentation, batches of 128
     <out>_sample.npy   (n, dim_rep) float32   mean z over `--samples` sampled segmentations (infer_avg)
+and, with --knn K, the K nearest other rows of every row of <out>.npy (VAE.neighbors, self excluded):
+    <out>_knn.npz      idx (n, K) int64, score (n, K) float32 under --metric (cos, dot or euc: minus the squared distance)
 
     python -m argsim_amd.eval_embed --ckpt trial/ckpt/kudo396 --vocab trial/data/vocab.model \
            --data data/test_data.npz --key posts --out data/test_data_emb --config config.json
@@ -43,6 +45,8 @@ def main(argv=None):
     ap.add_argument('--config', default='config.json')
     ap.add_argument('--samples', type=int, default=128)
     ap.add_argument('--no-sampled', action='store_true')
+    ap.add_argument('--knn', type=int, default=0, help="also write <out>_knn.npz: the K nearest other rows of every row")
+    ap.add_argument('--metric', default='cos', choices=('cos', 'dot', 'euc'))
     A = ap.parse_args(argv)
     from . import ckpt
     from .model import VAE
@@ -52,7 +56,11 @@ def main(argv=None):
     vocab = load_spm(A.vocab)
     model = VAE('infer', init=False, **load_json(A.config)['model'])
     ckpt.restore(model, A.ckpt, strict=True)
-    np.save(A.out + '.npy', embed(model, vocab, text))
+    z = embed(model, vocab, text)
+    np.save(A.out + '.npy', z)
+    if A.knn:
+        idx, score = model.neighbors(z, z, k=A.knn, metric=A.metric, exclude_self=True)
+        np.savez(A.out + '_knn.npz', idx=idx, score=score)
     if not A.no_sampled:
         np.save(A.out + '_sample.npy', np.stack([infer_avg(model, vocab, t, A.samples) for t in text], axis=0))
 

@@ -52,6 +52,11 @@ class AvaeScoreConfig(C.Structure):
     _fields_ = [('k', C.c_int32), ('seed', C.c_uint64)]
 
 
+class AvaeKnnConfig(C.Structure):
+    _fields_ = [('k', C.c_int32), ('metric', C.c_int32), ('idx_base', C.c_int64), ('self_base', C.c_int64), ('carry', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -85,6 +90,7 @@ SIGNATURES = {
     'avae_decode_beam': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeBeamConfig), _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     'avae_score': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(AvaeScoreConfig), _P, _P, _P, _P, _P, _P]),
     'avae_score_z': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    'avae_knn': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(AvaeKnnConfig), _P, _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),

@@ -13,6 +13,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) sampled decoding                             -> VAE.sample(z, ...) / VAE.generate(n, ...) / sample(vae, z, ...)
     (new) importance-weighted log p(x), k draws        -> VAE.score(src, tgt, k, ...) / score(vae, src, k, seed)
     (new) teacher-forced log p(tgt | z)                -> VAE.score_z(z, tgt)
+    (new) nearest neighbours among latent rows         -> VAE.neighbors(queries, bank, k, metric) / neighbors(vae, ...)
 """
 import ctypes as C
 
@@ -452,6 +453,81 @@ class VAE:
         return logpx.cpu().numpy(), ntok.cpu().numpy()
 
 
+    # ------------------------------------------------------------------ retrieval
+    def neighbors(self, queries, bank, k=10, metric='cos', exclude_self=False, block=None, return_distance=False):
+        """the k nearest bank rows of every query row (include/argsim_vae.h, avae_knn) -> (idx int64 (n, k), score float32 (n, k)),
+        best first: score descending, ties to the lower index; slots beyond the admissible rows hold -1 / -inf.
+        queries (n, dim) and bank (N, dim) are float32 numpy arrays or torch tensors, dim a multiple of 4 up to 1024 (any width, not
+        only dim_rep).  A tensor on this device is used in place; a host bank is uploaded in blocks of `block` rows (default: 256 MB
+        worth) and searched block by block with the carried list, which gives the same bits as one call; `block` also cuts a
+        device bank.  metric: 'dot', 'cos' or 'euc' -- the score of 'euc' is MINUS the squared distance (larger is better, as for
+        the others); with return_distance=True the second array is the squared distance itself (+inf in missing slots).
+        exclude_self: queries are rows of the bank and a row must not return itself -- True when queries is bank[0:n], an integer
+        i0 (or a 1-tuple (i0,)) when it is bank[i0:i0 + n].  The result is numpy, or tensors on the device when queries is a torch
+        tensor."""
+        k, mid, i0, block = _check_knn_args(queries, bank, k, metric, exclude_self, block)
+        if return_distance and mid != 2:
+            raise ValueError("return_distance needs metric 'euc', got %r" % (metric,))
+        as_torch = isinstance(queries, torch.Tensor)
+        dev = lambda x: (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.array(x, order='C'))).to(self.device).contiguous()
+        q = dev(queries)
+        n, dim, N = q.shape[0], q.shape[1], bank.shape[0]
+        on_dev = isinstance(bank, torch.Tensor) and bank.is_cuda
+        if block is None:
+            block = max(N, 1) if on_dev else max(1, (256 << 20) // (4 * dim))
+        idx = torch.empty((n, k), dtype=torch.int64, device=self.device)
+        score = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        self._stream()
+        for j, b0 in enumerate(range(0, max(N, 1), block)):
+            part = dev(bank[b0:b0 + block])
+            kc = _lib.AvaeKnnConfig(k, mid, b0, i0, 1 if j else 0, 0)
+            self._ck(self._l.avae_knn(self._h, C.c_void_p(q.data_ptr()), n, C.c_void_p(part.data_ptr()), part.shape[0], dim, C.byref(kc),
+                                      C.c_void_p(idx.data_ptr()), C.c_void_p(score.data_ptr())))
+            if not on_dev:
+                torch.cuda.current_stream(self.device).synchronize()      # the uploaded block is freed when `part` goes
+        if return_distance:
+            score = 0.0 - score
+        return (idx, score) if as_torch else (idx.cpu().numpy(), score.cpu().numpy())
+
+
+KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
+
+
+def _check_knn_args(queries, bank, k, metric, exclude_self=False, block=None):
+    """the argument rules of avae_knn, checked before anything touches the device -> (k, metric id, self_base or -1, block or None)"""
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= 32:
+        raise ValueError("k must be an integer in [1, 32], got %r" % (k,))
+    if not isinstance(metric, str) or metric not in KNN_METRICS:
+        raise ValueError("metric must be one of 'dot', 'cos', 'euc', got %r" % (metric,))
+    for name, x in (('queries', queries), ('bank', bank)):
+        if not isinstance(x, (np.ndarray, torch.Tensor)):
+            raise ValueError("%s must be a numpy array or a torch tensor, got %s" % (name, type(x).__name__))
+        if x.dtype not in (np.float32, torch.float32):
+            raise ValueError("%s must be float32, got %s" % (name, x.dtype))
+        if len(x.shape) != 2:
+            raise ValueError("%s must be (rows, dim), got %s" % (name, tuple(x.shape)))
+    if queries.shape[0] < 1:
+        raise ValueError("queries must have at least one row, got %s" % (tuple(queries.shape),))
+    dim = queries.shape[1]
+    if bank.shape[1] != dim:
+        raise ValueError("queries and bank must have the same dim, got %d and %d" % (dim, bank.shape[1]))
+    if dim % 4 or not 4 <= dim <= 1024:
+        raise ValueError("dim must be a multiple of 4 in [4, 1024], got %d" % (dim,))
+    if isinstance(exclude_self, (tuple, list)):
+        if len(exclude_self) != 1:
+            raise ValueError("exclude_self must be a bool, an integer i0 or (i0,), got %r" % (exclude_self,))
+        exclude_self = exclude_self[0]
+    if isinstance(exclude_self, (bool, np.bool_)):
+        i0 = 0 if exclude_self else -1
+    else:
+        if int(exclude_self) != exclude_self or exclude_self < 0:
+            raise ValueError("exclude_self must be a bool, an integer i0 >= 0 or (i0,), got %r" % (exclude_self,))
+        i0 = int(exclude_self)
+    if block is not None and (isinstance(block, bool) or int(block) != block or not 1 <= block < (1 << 31) - 256):
+        raise ValueError("block must be an integer in [1, 2^31 - 256), got %r" % (block,))
+    return int(k), KNN_METRICS[metric], i0, None if block is None else int(block)
+
+
 def _check_score_args(k, seed):
     """the argument rules of avae_score, checked before anything touches the device -> (k, seed) as ints"""
     if isinstance(k, bool) or int(k) != k or not 1 <= k <= 1 << 20:
@@ -526,3 +602,8 @@ def beam(vae, z, steps=256, width=4, length_alpha=0.0, return_all=False):
 def score(vae, src, k=1, seed=0):
     """importance-weighted log p(src row) per sentence, k draws: VAE.score"""
     return vae.score(src, None, k, seed)
+
+
+def neighbors(vae, queries, bank, k=10, metric='cos', exclude_self=False, block=None, return_distance=False):
+    """the k nearest bank rows of every query row: VAE.neighbors"""
+    return vae.neighbors(queries, bank, k, metric, exclude_self, block, return_distance)

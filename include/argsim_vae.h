@@ -278,6 +278,50 @@ int  avae_score(avae_handle h, const int32_t* src, const int32_t* tgt, int32_t B
 int  avae_score_z(avae_handle h, const float* z, const int32_t* tgt, int32_t b, int32_t S_tgt,
                   float* logpx /* (b) */, int32_t* ntok /* optional (b) */);
 
+/* ---- nearest neighbours among latent rows ------------------------------------------------ */
+/* The encoder-side counterpart of the decoders above: for each of n query rows the k best of N bank rows under a similarity,
+ * on the device, without the (n, N) score panel ever reaching memory.  q (n, dim) and bank (N, dim) are row-major float32
+ * device arrays, 16-byte aligned (e.g. z of avae_encode); dim is a multiple of 4 in [4, 1024] and independent of the handle's
+ * dim_rep; n >= 1, 0 <= N <= 2^31 - 256.  The work is enqueued on the handle's stream; nothing is synchronised.
+ *   score   of a pair depends on the two rows and the metric ALONE -- not on n, N, k, the rows' positions, the tile a pair falls
+ *           in or the launch shape:
+ *           dot (0)    d = sum_j q_j b_j in fp32 on v_mfma_f32_32x32x2_f32, in this fixed order: j in blocks of 32, ascending
+ *                      (the last block zero filled); inside a block 16 steps s = 0 .. 15, step s adding the two products
+ *                      j = 8 (s >> 2) + (s & 3) and j + 4 to the running sum in one matrix instruction.
+ *           cosine (1) d / (|q| |b|): the fp32 product of the norms, then an IEEE division.  |x| = the fp32 square root of the
+ *                      sum of squares of that row alone, in a fixed order (lane l of a wave: elements 4 l .. 4 l + 3, then
+ *                      256 + 4 l .., fused multiply-adds in index order; the 64 lanes by an xor butterfly 32, 16, .., 1).
+ *                      A row of norm zero on either side scores 0.
+ *           Euclid (2) - max(0, (|q|^2 - 2 d) + |b|^2) in exactly that order of operations: the negated squared distance, so
+ *                      that larger is always better.  This form carries the cancellation error of the expansion, a few ulp of
+ *                      |q|^2 + |b|^2: an identical pair scores about -1e-7 for rows of norm 1, not exactly 0.  (A NaN is no
+ *                      number to clamp: it stays a NaN.)
+ *   order   score descending, then global index ascending.  Scores compare through the sampler's order_key: +0 and -0 are equal
+ *           and a NaN sorts below -inf (among NaNs the lower index first).  out_score holds the canonical value of the key: a -0
+ *           is returned as +0, any NaN as the quiet NaN 0x7fc00000.
+ *   index   bank row c of THIS call has global index idx_base + c (idx_base >= 0).
+ *   self    self_base >= 0: query i never returns global index self_base + i (queries that are rows of the bank); -1: off.
+ *   missing slots beyond the number of admissible rows hold index -1 and score -inf.
+ *   carry   carry = 1: out_idx / out_score hold the list of earlier calls (sorted as above, -1 entries empty); it is merged as one
+ *           more sorted list.  One call over bank rows [0, N) and carried calls over [0, N1), [N1, N) .. with idx_base = N1 ..
+ *           give the same bits of indices and scores: this is how a bank larger than device memory is streamed.
+ *   bits    no float atomics, fixed-order reductions: the same arguments give the same bits.
+ * Errors (text through avae_last_error): a null kc, q, out_idx or out_score; a null bank with N > 0; n < 1, N < 0 or N > 2^31 - 256;
+ * k outside [1, 32]; an unknown metric; dim not a multiple of 4 in [4, 1024]; idx_base < 0, self_base < -1; carry not 0 or 1;
+ * reserved != 0; q or bank not 16-byte aligned.
+ * Option knn_chunk (avae_set_option; a test aid): caps the bank rows one workgroup walks, so that small tests run many parts and
+ * the merge; 0 lets the planner decide.  A cap that would give more parts than the merge ranks at once is raised.           */
+typedef struct avae_knn_config {
+    int32_t k;          /* 1..32 */
+    int32_t metric;     /* 0 dot, 1 cosine, 2 squared Euclidean */
+    int64_t idx_base;   /* global index of bank row 0 of THIS call */
+    int64_t self_base;  /* -1: off; else query i never returns global index self_base + i */
+    int32_t carry;      /* 1: out_idx/out_score hold a list from earlier calls; merge into it */
+    int32_t reserved;
+} avae_knn_config;
+int  avae_knn(avae_handle h, const float* q, int32_t n, const float* bank, int32_t N, int32_t dim,
+              const avae_knn_config* kc, int64_t* out_idx /* (n,k) */, float* out_score /* (n,k) */);
+
 #ifdef __cplusplus
 }
 #endif
