@@ -1755,6 +1755,74 @@ int avae_debug_argmax_rows(avae_handle h, const float* logits, int32_t* pred, in
     AV_CHECK(argmax_rows(h->stream, logits, pred, n, V));
     return 0;
 }
+// test hook: the sizes and views of the token-group scratch, so that no test restates the layout.  out[0] = embed_scatter_scratch_ints,
+// out[1] = id_groups_ints, out[2..4] = offsets (in ints) of the id_groups_rank / uid / count views, out[5] = id_groups_supported.
+// Host arithmetic only: callable without a GPU.
+int avae_debug_op_layout(int64_t n, int64_t V, int64_t out[6])
+{
+    if (!out || n < 0 || V < 0) return 1;
+    int32_t base[1];
+    out[0] = (int64_t)embed_scatter_scratch_ints((size_t)n, (size_t)V);
+    out[1] = (int64_t)id_groups_ints((size_t)n, (size_t)V);
+    out[2] = id_groups_rank(base, (int)n, (int)V) - base;
+    out[3] = id_groups_uid(base, (int)n, (int)V) - base;
+    out[4] = id_groups_count(base, (int)n, (int)V) - base;
+    out[5] = id_groups_supported((int)V) ? 1 : 0;
+    return 0;
+}
+// test hook: ONE launcher of the small kernels (ops.hip) named by `op`, on caller-owned device buffers, on the handle's stream.  p: the
+// launcher's pointer arguments in the order of its declaration in kernels.h (struct arguments: the order of the fields), i: its integer
+// arguments likewise (a uint64 seed as its bit pattern, a bool as 0 / 1), f: its float arguments.  A launcher's refusal comes back as a
+// non-zero return with the hipError_t text in avae_last_error.  Nothing else happens here.
+//   row_order: p = (lens, perm, slens) per order, then steps_sum; i = n, Breal, B, S, sum_rows, then (add, T, cpj) per order (n <= 4 read)
+//   id_groups_build / rows_group_sum: the scratch is p's last entry
+int avae_debug_op(avae_handle h, const char* op, void* const* p, const int64_t* i, const float* f)
+{
+    if (!h || !op || !p || !i || !f) return 1;
+    const std::string o(op);
+    hipStream_t st = h->stream;
+    auto F = [&](int k) { return static_cast<float*>(p[k]); };
+    auto I = [&](int k) { return static_cast<int32_t*>(p[k]); };
+    if (o == "prep_ids") {
+        PrepArgs a{};
+        a.src = I(0); a.tgt = I(1); a.keep_mask = static_cast<const uint8_t*>(p[2]); a.src_tm = I(3); a.lens_src = I(4); a.lens_tgt = I(5);
+        a.lead = I(6); a.gold = I(7); a.rank = I(8); a.cidx = I(9); a.ntok = I(10); a.zero2 = F(11); a.chunk_counts = I(12);
+        a.B = (int)i[0]; a.Ss = (int)i[1]; a.St = (int)i[2]; a.eos = (int)i[3]; a.bos = (int)i[4]; a.train = (int)i[5]; a.seed = (uint64_t)i[6];
+        a.keepwd = f[0];
+        AV_CHECK(prep_ids(st, a));
+    } else if (o == "embed_gather") AV_CHECK(embed_gather(st, F(0), I(1), F(2), (int)i[0], (int)i[1], (int)i[2]));
+    else if (o == "embed_scatter_add2") AV_CHECK(embed_scatter_add2(st, F(0), I(1), F(2), (int)i[0], I(3), F(4), (int)i[1], (int)i[2], (int)i[3], I(5)));
+    else if (o == "id_groups_build") AV_CHECK(id_groups_build(st, I(0), (int)i[0], (int)i[1], I(1), i[2] != 0));
+    else if (o == "rank_rows") AV_CHECK(rank_rows(st, I(0), I(1), I(2), (int)i[0], (int)i[1]));
+    else if (o == "rows_gather_ranked") AV_CHECK(rows_gather_ranked(st, F(0), F(1), I(2), I(3), (int)i[0], (int)i[1], (int)i[2]));
+    else if (o == "rows_group_sum") AV_CHECK(rows_group_sum(st, F(0), I(1), F(2), (int)i[0], (int)i[1], (int)i[2], I(3)));
+    else if (o == "rows_add_indexed") AV_CHECK(rows_add_indexed(st, F(0), F(1), I(2), I(3), (int)i[0], (int)i[1]));
+    else if (o == "rows_gather") AV_CHECK(rows_gather(st, F(0), F(1), I(2), I(3), (int)i[0], (int)i[1], I(4)));
+    else if (o == "rows_expand") AV_CHECK(rows_expand(st, F(0), F(1), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "zero_rows_dyn") AV_CHECK(zero_rows_dyn(st, F(0), I(1), (int)i[0], (int)i[1]));
+    else if (o == "zero_fill") AV_CHECK(zero_fill(st, p[0], (size_t)i[0]));
+    else if (o == "row_order") {
+        RowOrder ro[4];
+        const int n = (int)i[0];
+        for (int k = 0; k < std::min(n, 4); ++k) ro[k] = RowOrder{I(3 * k), (int)i[5 + 3 * k], (int)i[6 + 3 * k], (int)i[7 + 3 * k], I(3 * k + 1), I(3 * k + 2)};
+        AV_CHECK(row_order(st, ro, n, (int)i[1], (int)i[2], (int)i[3], I(3 * std::min(std::max(n, 0), 4)), (int)i[4]));
+    } else if (o == "row_map") AV_CHECK(row_map(st, I(0), (int)i[0], (int)i[1], (int)i[2], I(1), I(2), I(3)));
+    else if (o == "pick_last") AV_CHECK(pick_last(st, F(0), F(1), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "pick_last16") AV_CHECK(pick_last16(st, F(0), static_cast<const unsigned short*>(p[1]), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "pick_last_add") AV_CHECK(pick_last_add(st, F(0), F(1), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "pick_last_bwd") AV_CHECK(pick_last_bwd(st, F(0), F(1), I(2), (int)i[0], (int)i[1], (int)i[2]));
+    else if (o == "latent_fwd") AV_CHECK(latent_fwd(st, F(0), F(1), F(2), F(3), F(4), F(5), (int)i[0], (int)i[1], (uint64_t)i[2], f[0], F(6)));
+    else if (o == "latent_bwd") AV_CHECK(latent_bwd(st, F(0), F(1), F(2), F(3), F(4), F(5), (int)i[0], (int)i[1], f[0], f[1]));
+    else if (o == "colsum") AV_CHECK(colsum(st, F(0), (int)i[0], (int)i[1], (int)i[2], F(1), I(2)));
+    else if (o == "add3") AV_CHECK(add3(st, F(0), F(1), F(2), F(3), i[0]));
+    else if (o == "finalize_losses") AV_CHECK(finalize_losses(st, F(0), F(1), I(2), (int)i[0], F(3), (int)i[1], f[0], f[1], f[2]));
+    else if (o == "adam_tf") {
+        const AdamArgs a{F(0), F(1), F(2), F(3), i[0], f[0], f[1], f[2], f[3], static_cast<const int*>(p[4])};
+        AV_CHECK(adam_tf(st, a));
+    } else if (o == "g16_permute") AV_CHECK(g16_permute(st, F(0), F(1), (int)i[0], (int)i[1], i[2] != 0));
+    else return fail(h, "avae_debug_op: no such launcher: " + o);
+    return 0;
+}
 int avae_bucket_count(avae_handle h) { return h ? (int)h->buckets.size() : 0; }
 int avae_bucket_info(avae_handle h, int i, int64_t* offset, int64_t* count)
 {

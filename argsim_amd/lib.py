@@ -99,6 +99,8 @@ SIGNATURES = {
     'avae_debug_gemm_tn16': (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float]),
     'avae_debug_softmax_ce': (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, C.POINTER(C.c_int)]),
     'avae_debug_argmax_rows': (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    'avae_debug_op': (C.c_int, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
+    'avae_debug_op_layout': (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     'avae_debug_sample_rows': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AvaeSampleConfig), _P, _P]),
     'avae_debug_sample_rows_p': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(AvaeSamplePConfig), _P, _P, _P, _P]),
     'avae_debug_beam_select': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
