@@ -1,0 +1,295 @@
+// hooks.cpp -- every avae_debug_* entry point: test surface, not product.  Each runs one piece of the library on caller buffers or
+// reports a host-side decision, so that tests restate neither.
+#include "ctx.h"
+
+using namespace avae;
+using namespace avae::host;
+
+extern "C" {
+
+// rows of the launch geometry the GRU team kernels take for a batch of B rows (gru_team_batch: B itself, the next row count with a
+// geometry -- the slots beyond B hold phantom rows --, or 0).  Host arithmetic only: callable without a GPU.
+int avae_debug_team_batch(int32_t B) { return B > 0 ? gru_team_batch(B) : 0; }
+// test hook: gemm_plan() for n shapes.  in: n x 19 int32, GemmShape's fields in their order; out: n x 15 -- the number of launches, then per
+// launch row0, rows, thin, split_k, accumulate, zero (GemmZero), dyn (an unused launch: zeros).  Host arithmetic only: callable without a GPU.
+int avae_debug_gemm_plan(const int32_t* in, int32_t n, int32_t* out)
+{
+    if (!in || !out || n < 0) return 1;
+    for (int r = 0; r < n; ++r, in += 19, out += 15) {
+        const GemmShape s{in[0] != 0, in[1] != 0, in[2], in[3], in[4], in[5], in[6], in[7], in[8], in[9], in[10], in[11] != 0, in[12] != 0,
+                          in[13] != 0, in[14] != 0, in[15], in[16] != 0, in[17] != 0, in[18] != 0};
+        const GemmPlan p = gemm_plan(s);
+        out[0] = p.n;
+        for (int i = 0; i < 2; ++i) {
+            const GemmLaunch l = i < p.n ? p.launch[i] : GemmLaunch{0, 0, 0, 0, 0, 0, 0};
+            const int32_t f[7] = {l.row0, l.rows, l.thin, l.split_k, l.accumulate, l.zero, l.dyn};
+            std::copy(f, f + 7, out + 1 + 7 * i);
+        }
+    }
+    return 0;
+}
+// test hook: one whole product through gemm() -- plan, clears, launches -- on caller buffers, with the handle's options.  flags: 1 allow_atomic,
+// 2 rows_are_batch, 4 weight gradient (a_mc = b_nc = 1).  count: the device-side count or null (rows; a weight gradient: depth), expect: what
+// the host is to expect of it (0: unknown).  A2 / B2 / C2: the second problem of a pair or null; keep16: GemmCall::keep_a16 or null.
+int avae_debug_gemm_call(avae_handle h, int a_mc, int b_nc, const float* A, const float* Bm, float* Cm, const float* bias, int M, int N, int K,
+                         int lda, int ldb, int ldc, float alpha, int accumulate, int flags, const int* count, int expect,
+                         const float* A2, const float* B2, float* C2, unsigned short* keep16)
+{
+    if (!h) return 1;
+    GemmCall c{A, lda, a_mc != 0, Bm, ldb, b_nc != 0, Cm, ldc, M, N, K};
+    c.alpha = alpha; c.bias = bias; c.accumulate = accumulate; c.keep_a16 = keep16;
+    c.allow_atomic = (flags & 1) != 0; c.rows_are_batch = (flags & 2) != 0; c.wgrad = (flags & 4) != 0;
+    if (c.wgrad) c.depth(count); else c.rows(count);
+    const Pair second{A2, B2, C2, nullptr};
+    if (A2) c.pair = &second;
+    const int* const was_ptr = h->expect_ptr[0]; const int was_val = h->expect_val[0];
+    h->expect_ptr[0] = count; h->expect_val[0] = expect;
+    const int r = gemm(h, c);
+    h->expect_ptr[0] = was_ptr; h->expect_val[0] = was_val;
+    return r;
+}
+// test hook: the decoder batches of the last avae_score / avae_score_z (score_plan): out = N, rc, kc, batches that ran the shared
+// first-layer projection of the non-table path (lead_rows + GruJob::gi_rows)
+int avae_debug_score_plan(avae_handle h, int32_t out[4])
+{
+    if (!h || !out) return 1;
+    for (int i = 0; i < 4; ++i) out[i] = h->score_plan[i];
+    return 0;
+}
+// ids present in the last forward's two id sources (encoder input, decoder input) where those layers were table-fed
+// (use_table), else -1: out[0] = src, out[1] = tgt.  Synchronises.
+int avae_debug_present_ids(avae_handle h, int32_t out[2])
+{
+    if (!h || !out) return 1;
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    out[0] = out[1] = -1;
+    if (h->cnt_src) AV_CHECK(hipMemcpy(&out[0], h->cnt_src, sizeof(int), hipMemcpyDeviceToHost));
+    if (h->cnt_tgt) AV_CHECK(hipMemcpy(&out[1], h->cnt_tgt, sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+// test hook: the per-token cross-entropy (model.py:180 loss_gen_samp) of the LAST avae_forward_backward / avae_train_step -- the
+// TRAIN forward, word dropout and the latent draw live -- copied to out (device memory, max_n floats); *n_out = its token count.
+// (The workspace layout is a pure function of the call geometry, so the array is found again without keeping a pointer.)
+int avae_debug_train_ce(avae_handle h, float* out, int32_t max_n, int32_t* n_out)
+{
+    if (!h || !out || !n_out) return 1;
+    if (h->B < 1) return fail(h, "avae_debug_train_ce: no training forward has run on this handle");
+    Ws w;
+    AV_TRY(get_ws(h, w, h->B, h->Ss, h->St, true));
+    int n = 0;
+    AV_CHECK(hipMemcpyAsync(&n, w.ntok, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    n = std::min(n, (int)max_n);
+    AV_CHECK(hipMemcpyAsync(out, w.loss_samp, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    *n_out = n;
+    return 0;
+}
+// diagnostic: per-launch (class, ms, FLOPs) triples of the stamps recorded since timing was switched on, in launch
+// order (does not reset them); returns the number of stamps through *n
+int avae_debug_timing(avae_handle h, double* out, int max_n, int* n)
+{
+    if (!h || !out || !n) return 1;
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    *n = (int)std::min<size_t>(h->stamps_used, (size_t)max_n);
+    std::vector<std::pair<const int*, int>> seen;
+    for (int i = 0; i < *n; ++i) {
+        float ms = 0.f;
+        AV_CHECK(hipEventElapsedTime(&ms, h->stamps[i].a, h->stamps[i].b));
+        double f = 1.0;
+        AV_TRY(dyn_fraction(h, h->stamps[i], seen, &f));
+        const double fl = h->stamps[i].flops * f;
+        out[3 * i] = h->stamps[i].cls; out[3 * i + 1] = ms; out[3 * i + 2] = fl;
+    }
+    return 0;
+}
+// diagnostic: reads and clears the 32 GRU phase-stamp words (option gru_ablate bit 32)
+int avae_debug_stamps(avae_handle h, unsigned long long* out)
+{
+    if (!h || !out) return 1;
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    AV_CHECK(hipMemcpy(out, h->errw + 16, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    AV_CHECK(hipMemset(h->errw + 16, 0, 32 * sizeof(unsigned long long)));
+    return 0;
+}
+// test hook: the MFMA GEMM on caller buffers (see kernels.h for the operand conventions)
+int avae_debug_gemm(avae_handle h, int a_mc, int b_nc, const float* A, const float* Bm, float* Cm, const float* bias,
+                    int M, int N, int K, int lda, int ldb, int ldc, float alpha, int accumulate, int split_k)
+{
+    if (!h) return 1;
+    // split_k == -1 selects the thin (32x128 tile) variant, -3 the skinny form, 1000 + s the 64x64-tile variant with s K slices
+    GemmCall c{A, lda, a_mc != 0, Bm, ldb, b_nc != 0, Cm, ldc, M, N, K};
+    c.alpha = alpha; c.bias = bias; c.accumulate = accumulate;
+    return gemm(h, c.form(split_k == -3 ? 3 : (split_k < 0 ? 1 : (split_k >= 1000 ? 2 : 0)), split_k < 0 ? 1 : (split_k >= 1000 ? split_k - 1000 : split_k)));
+}
+// test hook: C = A B^T (A (M, K), B (N, K) row-major) over the first *rows rows of A only, rows read on the DEVICE (dyn_kind 1)
+int avae_debug_gemm_dyn(avae_handle h, const float* A, const float* Bm, float* Cm, int M, int N, int K, const int* rows)
+{
+    if (!h) return 1;
+    return gemm(h, nt(A, K, Bm, K, Cm, N, M, N, K).rows(rows).form(0));
+}
+// test hook (compute_dtype 1): the fp16 output panel of the phased NT GEMM, C16 (M x N) = fp16(alpha * A B^T) over the first *rows rows (rows == nullptr: all);
+// returns 3 where the phased kernel does not take the shape
+int avae_debug_gemm_c16(avae_handle h, const float* A, const float* Bm, unsigned short* C16, int M, int N, int K, float alpha, const int* rows)
+{
+    if (!h) return 1;
+    if (h->cfg.compute_dtype != 1 || !gemm_bf16_c16_takes(M, N, K, rows, h->bf16_nt8)) return 3;
+    GemmCall c = nt(A, K, Bm, K, nullptr, N, M, N, K).scaled(alpha).rows(rows).form(0);
+    c.c16 = C16;
+    return gemm(h, c);
+}
+// test hook: C (M x N) += alpha * A^T B with A (K x M, lda), B (K x N, ldb) fp32 row-major, operands rounded to bf16 row by
+// row and read through the transposing-LDS-load GEMM (gemm_tn16 / gemm_bf16_tn); C must hold the value to add onto
+int avae_debug_gemm_tn16(avae_handle h, const float* A, const float* Bm, float* Cm, int M, int N, int K, int lda, int ldb, int ldc, float alpha)
+{
+    if (!h) return 1;
+    return gemm_tn16(h, tn_grad(A, lda, Bm, ldb, Cm, ldc, M, N, K).scaled(alpha));
+}
+// test hook: softmax_ce (ops.hip) on caller buffers, enqueued on the handle's stream.  logits (n_max x V fp32) and panel (n_max x V,
+// 2-byte) as CeArgs::logits / grad16: with write_grad the gradient goes to panel as bf16 when panel is given, else over the logits;
+// logits16 reads the logits from panel as fp16.  *form_out = softmax_ce_form (0 register, 1 fp16 panel, 2 streaming, -1 refused).
+int avae_debug_softmax_ce(avae_handle h, float* logits, unsigned short* panel, int logits16, const int32_t* gold, const int32_t* cidx,
+                          const int32_t* n_dev, int n_max, int V, int write_grad, float inv_n, float* loss_samp, float* errt,
+                          int32_t* pred, int* form_out)
+{
+    if (!h || !form_out) return 1;
+    CeArgs c{};
+    c.logits = logits; c.gold = gold; c.cidx = cidx; c.n_dev = n_dev; c.n_max = n_max; c.V = V;
+    c.write_grad = write_grad; c.inv_n = inv_n;
+    c.loss_samp = loss_samp; c.errt_samp = errt; c.pred = pred; c.loss_acc = nullptr;
+    c.grad16 = panel; c.logits16 = logits16;
+    *form_out = softmax_ce_form(c);
+    AV_CHECK(softmax_ce(h->stream, c));
+    return 0;
+}
+// test hook: argmax_rows (ops.hip, the stepwise decode's first-maximum) on caller buffers, enqueued on the handle's stream
+int avae_debug_argmax_rows(avae_handle h, const float* logits, int32_t* pred, int n, int V)
+{
+    if (!h) return 1;
+    AV_CHECK(argmax_rows(h->stream, logits, pred, n, V));
+    return 0;
+}
+// test hook: the sizes and views of the token-group scratch, so that no test restates the layout.  out[0] = embed_scatter_scratch_ints,
+// out[1] = id_groups_ints, out[2..4] = offsets (in ints) of the id_groups_rank / uid / count views, out[5] = id_groups_supported.
+// Host arithmetic only: callable without a GPU.
+int avae_debug_op_layout(int64_t n, int64_t V, int64_t out[6])
+{
+    if (!out || n < 0 || V < 0) return 1;
+    int32_t base[1];
+    out[0] = (int64_t)embed_scatter_scratch_ints((size_t)n, (size_t)V);
+    out[1] = (int64_t)id_groups_ints((size_t)n, (size_t)V);
+    out[2] = id_groups_rank(base, (int)n, (int)V) - base;
+    out[3] = id_groups_uid(base, (int)n, (int)V) - base;
+    out[4] = id_groups_count(base, (int)n, (int)V) - base;
+    out[5] = id_groups_supported((int)V) ? 1 : 0;
+    return 0;
+}
+// test hook: ONE launcher of the small kernels (ops.hip) named by `op`, on caller-owned device buffers, on the handle's stream.  p: the
+// launcher's pointer arguments in the order of its declaration in kernels.h (struct arguments: the order of the fields), i: its integer
+// arguments likewise (a uint64 seed as its bit pattern, a bool as 0 / 1), f: its float arguments.  A launcher's refusal comes back as a
+// non-zero return with the hipError_t text in avae_last_error.  Nothing else happens here.
+//   row_order: p = (lens, perm, slens) per order, then steps_sum; i = n, Breal, B, S, sum_rows, then (add, T, cpj) per order (n <= 4 read)
+//   id_groups_build / rows_group_sum: the scratch is p's last entry
+int avae_debug_op(avae_handle h, const char* op, void* const* p, const int64_t* i, const float* f)
+{
+    if (!h || !op || !p || !i || !f) return 1;
+    const std::string o(op);
+    hipStream_t st = h->stream;
+    auto F = [&](int k) { return static_cast<float*>(p[k]); };
+    auto I = [&](int k) { return static_cast<int32_t*>(p[k]); };
+    if (o == "prep_ids") {
+        PrepArgs a{};
+        a.src = I(0); a.tgt = I(1); a.keep_mask = static_cast<const uint8_t*>(p[2]); a.src_tm = I(3); a.lens_src = I(4); a.lens_tgt = I(5);
+        a.lead = I(6); a.gold = I(7); a.rank = I(8); a.cidx = I(9); a.ntok = I(10); a.zero2 = F(11); a.chunk_counts = I(12);
+        a.B = (int)i[0]; a.Ss = (int)i[1]; a.St = (int)i[2]; a.eos = (int)i[3]; a.bos = (int)i[4]; a.train = (int)i[5]; a.seed = (uint64_t)i[6];
+        a.keepwd = f[0];
+        AV_CHECK(prep_ids(st, a));
+    } else if (o == "embed_gather") AV_CHECK(embed_gather(st, F(0), I(1), F(2), (int)i[0], (int)i[1], (int)i[2]));
+    else if (o == "embed_scatter_add2") AV_CHECK(embed_scatter_add2(st, F(0), I(1), F(2), (int)i[0], I(3), F(4), (int)i[1], (int)i[2], (int)i[3], I(5)));
+    else if (o == "id_groups_build") AV_CHECK(id_groups_build(st, I(0), (int)i[0], (int)i[1], I(1), i[2] != 0));
+    else if (o == "rank_rows") AV_CHECK(rank_rows(st, I(0), I(1), I(2), (int)i[0], (int)i[1]));
+    else if (o == "rows_gather_ranked") AV_CHECK(rows_gather_ranked(st, F(0), F(1), I(2), I(3), (int)i[0], (int)i[1], (int)i[2]));
+    else if (o == "rows_group_sum") AV_CHECK(rows_group_sum(st, F(0), I(1), F(2), (int)i[0], (int)i[1], (int)i[2], I(3)));
+    else if (o == "rows_add_indexed") AV_CHECK(rows_add_indexed(st, F(0), F(1), I(2), I(3), (int)i[0], (int)i[1]));
+    else if (o == "rows_gather") AV_CHECK(rows_gather(st, F(0), F(1), I(2), I(3), (int)i[0], (int)i[1], I(4)));
+    else if (o == "rows_expand") AV_CHECK(rows_expand(st, F(0), F(1), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "zero_rows_dyn") AV_CHECK(zero_rows_dyn(st, F(0), I(1), (int)i[0], (int)i[1]));
+    else if (o == "zero_fill") AV_CHECK(zero_fill(st, p[0], (size_t)i[0]));
+    else if (o == "row_order") {
+        RowOrder ro[4];
+        const int n = (int)i[0];
+        for (int k = 0; k < std::min(n, 4); ++k) ro[k] = RowOrder{I(3 * k), (int)i[5 + 3 * k], (int)i[6 + 3 * k], (int)i[7 + 3 * k], I(3 * k + 1), I(3 * k + 2)};
+        AV_CHECK(row_order(st, ro, n, (int)i[1], (int)i[2], (int)i[3], I(3 * std::min(std::max(n, 0), 4)), (int)i[4]));
+    } else if (o == "row_map") AV_CHECK(row_map(st, I(0), (int)i[0], (int)i[1], (int)i[2], I(1), I(2), I(3)));
+    else if (o == "pick_last") AV_CHECK(pick_last(st, F(0), F(1), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "pick_last16") AV_CHECK(pick_last16(st, F(0), static_cast<const unsigned short*>(p[1]), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "pick_last_add") AV_CHECK(pick_last_add(st, F(0), F(1), I(2), (int)i[0], (int)i[1], I(3)));
+    else if (o == "pick_last_bwd") AV_CHECK(pick_last_bwd(st, F(0), F(1), I(2), (int)i[0], (int)i[1], (int)i[2]));
+    else if (o == "latent_fwd") AV_CHECK(latent_fwd(st, F(0), F(1), F(2), F(3), F(4), F(5), (int)i[0], (int)i[1], (uint64_t)i[2], f[0], F(6)));
+    else if (o == "latent_bwd") AV_CHECK(latent_bwd(st, F(0), F(1), F(2), F(3), F(4), F(5), (int)i[0], (int)i[1], f[0], f[1]));
+    else if (o == "colsum") AV_CHECK(colsum(st, F(0), (int)i[0], (int)i[1], (int)i[2], F(1), I(2)));
+    else if (o == "add3") AV_CHECK(add3(st, F(0), F(1), F(2), F(3), i[0]));
+    else if (o == "finalize_losses") AV_CHECK(finalize_losses(st, F(0), F(1), I(2), (int)i[0], F(3), (int)i[1], f[0], f[1], f[2]));
+    else if (o == "adam_tf") {
+        const AdamArgs a{F(0), F(1), F(2), F(3), i[0], f[0], f[1], f[2], f[3], static_cast<const int*>(p[4])};
+        AV_CHECK(adam_tf(st, a));
+    } else if (o == "g16_permute") AV_CHECK(g16_permute(st, F(0), F(1), (int)i[0], (int)i[1], i[2] != 0));
+    else return fail(h, "avae_debug_op: no such launcher: " + o);
+    return 0;
+}
+
+// test hook: sample_rows (ops.hip, the launch-per-token sampler) on caller buffers at step t0, row index = batch row
+int avae_debug_sample_rows(avae_handle h, const float* logits, int n, int V, int t0, const avae_sample_config* sc, int32_t* pred, float* logp)
+{
+    if (!h) return 1;
+    SampleParams sp{};
+    if (!sample_params(h, sc, V, &sp)) return 1;
+    if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
+    AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, nullptr, h->cfg.eos, pred, logp));
+    return 0;
+}
+
+// test hook: sample_rows_p on caller buffers at step t0, row index = batch row; lead (n, optional) as sample_rows_p takes it.  With the
+// nucleus off it is avae_debug_sample_rows and nkept is filled with -1
+int avae_debug_sample_rows_p(avae_handle h, const float* logits, int n, int V, int t0, const avae_sample_p_config* sc, int32_t* pred, float* logp,
+                             int32_t* nkept, const int32_t* lead)
+{
+    if (!h) return 1;
+    SampleParams sp{};
+    float top_p = 0.f;
+    if (!sample_params_p(h, sc, V, &sp, &top_p)) return 1;
+    if (n < 1 || V < 1 || t0 < 0 || t0 >= (1 << 20)) return fail(h, "sample rows: bad shape or step");
+    if (top_p > 0.f) AV_CHECK(sample_rows_p(h->stream, logits, n, V, t0, sp, top_p, lead, h->cfg.eos, pred, logp, nkept));
+    else {
+        AV_CHECK(sample_rows(h->stream, logits, n, V, t0, sp, lead, h->cfg.eos, pred, logp));
+        if (nkept) AV_CHECK(hipMemsetAsync(nkept, 0xff, (size_t)n * sizeof(int32_t), h->stream));
+    }
+    return 0;
+}
+
+// test hook: one selection step of the beam search (beam_rows + beam_select, beam.hip) on caller buffers: logits (n * width, V), cum and
+// fin (n * width) -> parent, token, cum_out, fin_out (n * width)
+int avae_debug_beam_select(avae_handle h, const float* logits, int n, int width, int V, const float* cum, const int32_t* fin,
+                           int32_t* parent, int32_t* token, float* cum_out, int32_t* fin_out)
+{
+    if (!h) return 1;
+    if (!logits || !cum || !fin || !parent || !token || !cum_out || !fin_out) return fail(h, "beam select: every array must be given");
+    if (n < 1 || n > (1 << 20) || V < 1 || width < 1 || width > 32 || width > V) return fail(h, "beam select: bad shape or width");
+    AV_CHECK(hipSetDevice(h->device));
+    const size_t rows = (size_t)n * width;
+    float *cand_sc, *lat_cum; int32_t *cand_tok, *cand_cnt, *len_out, *live;      // (the lengths and the live count are not returned)
+    AV_TRY(place_scratch(h, "beam select", [&](Bump& b) {
+        cand_sc = b.take<float>(rows * width); lat_cum = b.take<float>(rows);
+        cand_tok = b.take<int32_t>(rows * width); cand_cnt = b.take<int32_t>(rows); len_out = b.take<int32_t>(rows); live = b.take<int32_t>(1);
+    }));
+    AV_CHECK(beam_rows(h->stream, logits, (int)rows, V, width, cum, fin, h->cfg.eos, cand_sc, cand_tok, cand_cnt));
+    BeamStep a{};
+    a.n = n; a.Win = width; a.W = width; a.eos = h->cfg.eos;
+    a.cand_sc = cand_sc; a.cand_tok = cand_tok; a.cand_cnt = cand_cnt; a.fin_in = fin; a.len_in = nullptr;
+    a.lat_parent = parent; a.lat_token = token; a.lat_cum = lat_cum; a.cum_out = cum_out; a.fin_out = fin_out; a.len_out = len_out;
+    a.live = live;
+    AV_CHECK(hipMemsetAsync(a.live, 0, sizeof(int32_t), h->stream));
+    AV_CHECK(beam_select(h->stream, a));
+    return 0;
+}
+
+}  // extern "C"

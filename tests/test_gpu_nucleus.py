@@ -270,6 +270,25 @@ def test_same_call_same_bits_and_the_step_cap_cuts_a_prefix(persistent):
     m.set_option('persistent', 1)
 
 
+@pytest.mark.parametrize("top_p", [0.0, 0.8])
+@pytest.mark.parametrize("top_k", [0, 4])
+@pytest.mark.parametrize("persistent", [1, 0])
+def test_optional_outputs_do_not_change_the_others(persistent, top_k, top_p):
+    """logp_out and nkept_out are optional buffers of both loops' scratch: every combination of given / null returns the bits of the
+    call that asks for both (which the cases above hold against the float64 reference).  Nucleus off: nkept is -1 throughout."""
+    m, cfg, P, z = _model('tiny')
+    m.set_option('persistent', persistent)
+    kw = dict(steps=5, temperature=0.9, top_k=top_k, seed=5, top_p=top_p)
+    ids, logp, nk = m.sample(z[:3], return_logp=True, return_nkept=True, **kw)
+    i1, l1 = m.sample(z[:3], return_logp=True, **kw)
+    i2, n2 = m.sample(z[:3], return_nkept=True, **kw)
+    i3 = m.sample(z[:3], **kw)
+    m.set_option('persistent', 1)
+    assert np.array_equal(ids, i1) and np.array_equal(ids, i2) and np.array_equal(ids, i3)
+    assert np.array_equal(logp.view(np.int32), l1.view(np.int32)) and np.array_equal(nk, n2)
+    assert (nk >= 1).any() if top_p else (nk == -1).all()
+
+
 def test_bad_arguments_are_errors_and_the_handle_works_afterwards():
     import torch
     m, cfg, P, z = _model('mid')
