@@ -587,6 +587,7 @@ hipError_t gemm_bf16_nt(hipStream_t st, const unsigned short* A, int lda, const 
 {
     if (g.M <= 0 || g.N <= 0) return hipSuccess;
     if ((lda | ldb) & 7) return hipErrorInvalidValue;
+    if (g.dyn_kind == 2 && g.split_k > 1 && g.bias) return hipErrorInvalidValue;      // (a slice beyond a device-side depth returns before its epilogue: slice 0 of a zero depth would drop the bias)
     if (g.c16 && !gemm_bf16_c16_ok(g, lda, ldb)) return hipErrorInvalidValue;      // (only the phased kernel writes the 2-byte panel: the caller asks first)
     GemmBf16Args a{A, B, g.C, g.bias, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, g.split_k, g.dyn, g.dyn_kind};
     // large tiles where they fill the chip, by themselves or through the K split (re-derived for them: gemm_bf16_slices)

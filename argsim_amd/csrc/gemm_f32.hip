@@ -11,6 +11,7 @@
 // Within a 32-deep K tile, MFMA step j (0..15) of lane-half h consumes k = 8*(j>>2) + 4*h + (j&3):
 // a k-contiguous operand row then feeds four consecutive steps from ONE ds_read_b128.
 #include "kernels.h"
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -471,9 +472,9 @@ static bool skinny_ok(bool a_mc, const GemmArgs& g)
 {
     return !a_mc && g.split_k <= 1 && g.dyn_kind == 0 && (g.K & 3) == 0 && (g.lda & 3) == 0 && g.K >= 64;
 }
-static void launch_skinny(hipStream_t st, bool b_nc, const GemmArgs& g)
+static void launch_skinny(hipStream_t st, bool b_nc, const GemmArgs& g, const GemmF32Form& f)
 {
-    dim3 grid(((g.M + 31) / 32) * ((g.N + 31) / 32), g.A2 ? 2 : 1);
+    const dim3 grid(f.gx, f.gy, f.gz);
     if (b_nc) hipLaunchKernelGGL(gemm_f32_skinny_kernel<true>, grid, dim3(512), 0, st, g);
     else      hipLaunchKernelGGL(gemm_f32_skinny_kernel<false>, grid, dim3(512), 0, st, g);
 }
@@ -488,43 +489,75 @@ static void with_layouts(bool a_mc, bool b_nc, F&& f)
     else                     f(std::true_type{}, std::false_type{});
 }
 
-template <int WM, int WN, int TM, int TN>
-static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g)
+// Which instantiation a problem takes, as a value: the refusals, the tile form, the staging, the launch form and the grid are decided HERE
+// and nowhere else -- gemm_f32() below launches what this returns, avae_debug_gemm_f32_form reports it.  Host arithmetic only (the
+// AVAE_F32_* environment overrides, for A/B experiments, are read once).
+GemmF32Form gemm_f32_form(bool a_mc, bool b_nc, const GemmArgs& g)
 {
-    constexpr int BM = 32 * WM * TM, BN = 32 * WN * TN;
-    int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-    dim3 grid(tiles, g.A2 ? 2 : 1, g.split_k > 1 ? g.split_k : 1);
+    GemmF32Form f{-1, false, false, false, 0, 0, 0, hipSuccess};
+    if (g.M <= 0 || g.N <= 0) return f;
+    f.err = hipErrorInvalidValue;
+    if ((g.lda | g.ldb) & 3) return f;
+    if (((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.A2 | (uintptr_t)g.B2) & 15) return f;
+    // contiguous extents must be multiples of 4 (float4 staging)
+    if (!a_mc && (g.K & 3)) return f;
+    if (a_mc && (g.M & 3)) return f;
+    if (!b_nc && (g.K & 3)) return f;
+    if (b_nc && (g.N & 3)) return f;
+    // a device-side depth: [k][x] operands only (the staging of a k-contiguous tile tests k < K_eff once per float4); a K split takes no bias with
+    // it (a slice that starts at or beyond K_eff returns before the epilogue, slice 0 of a zero depth included)
+    if (g.dyn_kind == 2 && (!a_mc || !b_nc || (g.split_k > 1 && g.bias))) return f;
+    f.err = hipSuccess;
+    // (256x128 and 128x256 tiles were measured 5-20 % slower: 1 workgroup per CU cannot hide its own staging)
+    if (g.thin == 3 && skinny_ok(a_mc, g) && (b_nc || (g.ldb & 3) == 0)) {      // a few rows: one 32x32 tile per workgroup, K split over its waves
+        f.tile = 3; f.gx = ((g.M + 31) / 32) * ((g.N + 31) / 32); f.gy = g.A2 ? 2 : 1; f.gz = 1;
+        return f;
+    }
+    // 2: 64x64 tiles: 4x the tiles of the 128x128 form -> a quarter of the split-K slices; 1 (and 3 where the skinny form does not apply): 32x128
+    f.tile = g.thin == 2 ? 2 : (g.thin ? 1 : 0);
+    const int BM = f.tile == 0 ? 128 : (f.tile == 1 ? 32 : 64), BN = f.tile == 2 ? 64 : 128;
+    const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+    f.gx = tiles; f.gy = g.A2 ? 2 : 1; f.gz = g.split_k > 1 ? g.split_k : 1;
     // fast staging: k-contiguous operand: K a multiple of BK, known on the host; [k][x] operand: x extent a multiple of the tile
     static const bool allow_fast = !getenv("AVAE_F32_NOFAST");
     // (measured: +4..9 % where an operand is stored [k][x] or the K extent is long; the NT shapes with K <= 1024
     //  lose 1..7 % to the longer prologue and stay on the predicated path)
     const int k_per_wg = g.split_k > 1 ? (g.K + g.split_k - 1) / g.split_k : g.K;
-    const bool fast = allow_fast && (a_mc ? (g.M % BM == 0) : (g.K % BK == 0 && g.dyn_kind != 2)) &&
-                      (b_nc ? (g.N % BN == 0) : (g.K % BK == 0 && g.dyn_kind != 2)) && (a_mc || b_nc || k_per_wg >= 1536);
-    // Two launch forms of the 128x128 kernel.  Default: single LDS stage, two barriers per K tile, 3 workgroups per CU
-    // (768 slots).  Double-buffered: one barrier per K tile, 2 workgroups per CU (512 slots); measured 3-8 % slower at
+    f.fast = allow_fast && (a_mc ? (g.M % BM == 0) : (g.K % BK == 0 && g.dyn_kind != 2)) &&
+             (b_nc ? (g.N % BN == 0) : (g.K % BK == 0 && g.dyn_kind != 2)) && (a_mc || b_nc || k_per_wg >= 1536);
+    if (f.tile == 1) return f;
+    // The two 2x2-wave forms (128x128, 64x64) have two more launch forms.  Default: single LDS stage, two barriers per K tile, 3 workgroups
+    // per CU (768 slots).  Double-buffered: one barrier per K tile, 2 workgroups per CU (512 slots); measured 3-8 % slower at
     // equal balance, but a tile count in (768, 1024] runs as ONE balanced round instead of a full round plus a round
     // that leaves most slots empty (1024 tiles: 112 -> 130 TFLOP/s, gpurun_out/gb_db.log).
-    // more than one round of tiles, no split-K: the persistent form (cross-tile prefetch)
+    // more than one round of tiles, no split-K: the persistent form (cross-tile prefetch), which walks 128x128 tiles whichever of the two asked
     static const char* ps_env = getenv("AVAE_F32_PERSIST");
-    if constexpr (WM == 2 && WN == 2) {
-        // (only with the buffer-load staging: the predicated staging needs more registers than three workgroups per
-        //  CU leave, and its longer prologue no longer matters once the prologue is prefetched)
-        const bool aligned = (a_mc ? (g.M % BM == 0) : (g.K % BK == 0)) && (b_nc ? (g.N % BN == 0) : (g.K % BK == 0));
-        const bool persist = (ps_env ? atoi(ps_env) != 0 : true) && allow_fast && aligned && !g.A2 && g.split_k <= 1 && g.dyn_kind != 2 && tiles > 1024;
-        if (persist) {
-            dim3 pg(768);
-            with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_persist_kernel<decltype(A)::value, decltype(B)::value, true>), pg, dim3(256), 0, st, g); });
-            return;
-        }
+    // (only with the buffer-load staging: the predicated staging needs more registers than three workgroups per
+    //  CU leave, and its longer prologue no longer matters once the prologue is prefetched)
+    const bool aligned = (a_mc ? (g.M % BM == 0) : (g.K % BK == 0)) && (b_nc ? (g.N % BN == 0) : (g.K % BK == 0));
+    const bool persist = (ps_env ? atoi(ps_env) != 0 : true) && allow_fast && aligned && !g.A2 && g.split_k <= 1 && g.dyn_kind != 2 && tiles > 1024;
+    if (persist) {
+        f.tile = 0; f.fast = true; f.persist = true; f.gx = 768; f.gy = f.gz = 1;
+        return f;
     }
     static const char* db_env = getenv("AVAE_F32_DB");
+    // (a device-side row count: where the host expects more than one round of the 768 single-stage slots to be real)
+    const int eff_tiles = (g.dyn_kind == 1 && g.dyn_expect > 0) ? std::min(tiles, ((g.dyn_expect + BM - 1) / BM) * ((g.N + BN - 1) / BN)) : (g.dyn_kind == 1 ? 0 : tiles);
+    f.db = db_env ? atoi(db_env) != 0 && !g.A2 : (!g.A2 && g.split_k <= 1 && eff_tiles > 768 && tiles <= 1024);
+    return f;
+}
+
+template <int WM, int WN, int TM, int TN>
+static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g, const GemmF32Form& f)
+{
+    const dim3 grid(f.gx, f.gy, f.gz);
     if constexpr (WM == 2 && WN == 2) {
-        // (a device-side row count: where the host expects more than one round of the 768 single-stage slots to be real)
-        const int eff_tiles = (g.dyn_kind == 1 && g.dyn_expect > 0) ? std::min(tiles, ((g.dyn_expect + BM - 1) / BM) * ((g.N + BN - 1) / BN)) : (g.dyn_kind == 1 ? 0 : tiles);
-        const bool use_db = db_env ? atoi(db_env) != 0 && !g.A2 : (!g.A2 && g.split_k <= 1 && eff_tiles > 768 && tiles <= 1024);
-        if (use_db) {
-            if (fast) {
+        if (f.persist) {
+            with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_persist_kernel<decltype(A)::value, decltype(B)::value, true>), grid, dim3(256), 0, st, g); });
+            return;
+        }
+        if (f.db) {
+            if (f.fast) {
                 with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN, true, true>), grid, dim3(256), 0, st, g); });
             } else {
                 with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN, false, true>), grid, dim3(256), 0, st, g); });
@@ -532,7 +565,7 @@ static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs&
             return;
         }
     }
-    if (fast) {
+    if (f.fast) {
         with_layouts(a_mc, b_nc, [&](auto A, auto B) { hipLaunchKernelGGL((gemm_f32_kernel<decltype(A)::value, decltype(B)::value, WM, WN, TM, TN, true>), grid, dim3(256), 0, st, g); });
         return;
     }
@@ -541,20 +574,14 @@ static void launch_variant(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs&
 
 hipError_t gemm_f32(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g)
 {
-    if (g.M <= 0 || g.N <= 0) return hipSuccess;
-    if ((g.lda | g.ldb) & 3) return hipErrorInvalidValue;
-    if (((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.A2 | (uintptr_t)g.B2) & 15) return hipErrorInvalidValue;
-    // contiguous extents must be multiples of 4 (float4 staging)
-    if (!a_mc && (g.K & 3)) return hipErrorInvalidValue;
-    if (a_mc && (g.M & 3)) return hipErrorInvalidValue;
-    if (!b_nc && (g.K & 3)) return hipErrorInvalidValue;
-    if (b_nc && (g.N & 3)) return hipErrorInvalidValue;
-    // (256x128 and 128x256 tiles were measured 5-20 % slower: 1 workgroup per CU cannot hide its own staging)
-    if (g.thin == 3 && skinny_ok(a_mc, g) && (b_nc || (g.ldb & 3) == 0)) launch_skinny(st, b_nc, g);      // a few rows: one 32x32 tile per workgroup, K split over its waves
-    else if (g.thin == 3) launch_variant<1, 4, 1, 1>(st, a_mc, b_nc, g);
-    else if (g.thin == 2) launch_variant<2, 2, 1, 1>(st, a_mc, b_nc, g);      // 64x64 tiles: 4x the tiles of the 128x128 form -> a quarter of the split-K slices
-    else if (g.thin) launch_variant<1, 4, 1, 1>(st, a_mc, b_nc, g);
-    else        launch_variant<2, 2, 2, 2>(st, a_mc, b_nc, g);
+    const GemmF32Form f = gemm_f32_form(a_mc, b_nc, g);
+    if (f.err != hipSuccess) return f.err;
+    if (f.tile < 0) return hipSuccess;
+    if (f.tile == 3) launch_skinny(st, b_nc, g, f);
+    else if (f.persist) launch_variant<2, 2, 2, 2>(st, a_mc, b_nc, g, f);
+    else if (f.tile == 2) launch_variant<2, 2, 1, 1>(st, a_mc, b_nc, g, f);
+    else if (f.tile == 1) launch_variant<1, 4, 1, 1>(st, a_mc, b_nc, g, f);
+    else launch_variant<2, 2, 2, 2>(st, a_mc, b_nc, g, f);
     return hipGetLastError();
 }
 

@@ -536,6 +536,7 @@ static hipError_t gemm_split(hipStream_t st, bool a_mc, bool b_nc, const GemmArg
     if (a_mc && (g.M & 3)) return hipErrorInvalidValue;
     if (!b_nc && (g.K & 3)) return hipErrorInvalidValue;
     if (b_nc && (g.N & 3)) return hipErrorInvalidValue;
+    if (g.dyn_kind == 2 && (!a_mc || !b_nc || (g.split_k > 1 && g.bias))) return hipErrorInvalidValue;      // (as gemm_f32: s_load tests k < K_eff once per float4)
     const int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
     dim3 grid(tiles, 1, g.split_k > 1 ? g.split_k : 1);
     const GemmArgs& gp = g;

@@ -48,6 +48,43 @@ int avae_debug_gemm_call(avae_handle h, int a_mc, int b_nc, const float* A, cons
     h->expect_ptr[0] = was_ptr; h->expect_val[0] = was_val;
     return r;
 }
+// test hook: one product through gemm() in the CALLER's form: thin (GemmArgs::thin, 0..3) and split_k (>= 1) reach the kernels as they stand, and
+// the plan adds no clear -- the caller owns what C holds beforehand.  count / dyn_kind (0 none, 1 rows, 2 depth) / expect: the device-side count as in
+// avae_debug_gemm_call; A2 / B2 / C2 / bias2: the second problem of a pair or null.  The handle's compute_dtype and options choose the kernel family.
+int avae_debug_gemm_forced(avae_handle h, int a_mc, int b_nc, const float* A, const float* Bm, float* Cm, const float* bias, int M, int N, int K,
+                           int lda, int ldb, int ldc, float alpha, int accumulate, int thin, int split_k, const int* count, int dyn_kind, int expect,
+                           const float* A2, const float* B2, float* C2, const float* bias2)
+{
+    if (!h) return 1;
+    if (thin < 0 || thin > 3 || split_k < 1 || dyn_kind < 0 || dyn_kind > 2 || (dyn_kind != 0) != (count != nullptr))
+        return fail(h, "avae_debug_gemm_forced: thin in 0..3, split_k >= 1, dyn_kind in 0..2 with a count exactly where it is not 0");
+    GemmCall c{A, lda, a_mc != 0, Bm, ldb, b_nc != 0, Cm, ldc, M, N, K};
+    c.alpha = alpha; c.bias = bias; c.accumulate = accumulate;
+    if (dyn_kind == 2) c.depth(count); else c.rows(count);
+    c.form(thin, split_k);
+    const Pair second{A2, B2, C2, bias2};
+    if (A2) c.pair = &second;
+    const int* const was_ptr = h->expect_ptr[0]; const int was_val = h->expect_val[0];
+    h->expect_ptr[0] = count; h->expect_val[0] = expect;
+    const int r = gemm(h, c);
+    h->expect_ptr[0] = was_ptr; h->expect_val[0] = was_val;
+    return r;
+}
+// test hook: what gemm_f32() launches for a problem (gemm_f32_form): out = tile form (0 128x128, 1 32x128, 2 64x64, 3 skinny, -1 nothing), fast, db,
+// persist, grid x, y, z, refused (1: gemm_f32 returns an error instead).  pair: a second problem rides along.  Host arithmetic only: callable
+// without a GPU.
+int avae_debug_gemm_f32_form(int a_mc, int b_nc, int M, int N, int K, int lda, int ldb, int ldc, int accumulate, int thin, int split_k, int dyn_kind,
+                             int expect, int pair, int32_t out[8])
+{
+    if (!out) return 1;
+    alignas(16) static const float other[4] = {0.f, 0.f, 0.f, 0.f};      // (the form looks at whether there is a second problem and how it is aligned)
+    const GemmArgs g{nullptr, nullptr, nullptr, nullptr, M, N, K, lda, ldb, ldc, 1.f, accumulate, split_k, nullptr, dyn_kind, expect, thin,
+                     pair ? other : nullptr, pair ? other : nullptr, nullptr, nullptr};
+    const GemmF32Form f = gemm_f32_form(a_mc != 0, b_nc != 0, g);
+    const int32_t v[8] = {f.tile, f.fast, f.db, f.persist, (int32_t)f.gx, (int32_t)f.gy, (int32_t)f.gz, f.err != hipSuccess};
+    std::copy(v, v + 8, out);
+    return 0;
+}
 // test hook: the decoder batches of the last avae_score / avae_score_z (score_plan): out = N, rc, kc, batches that ran the shared
 // first-layer projection of the non-table path (lead_rows + GruJob::gi_rows)
 int avae_debug_score_plan(avae_handle h, int32_t out[4])

@@ -16,6 +16,10 @@ namespace avae {
 // every base pointer 16-byte aligned.  M/N/K edges are predicated (zero filled).
 // dyn (optional, device): the real row count when it is only known on the device:
 //   dyn_kind 1 -> M_eff = min(M, *dyn) (row tiles beyond it exit),  2 -> K_eff = min(K, *dyn).
+//   dyn_kind 2 takes [k][x] operands only (a_mc && b_nc, the weight gradients): a k-contiguous tile is staged four k at a time with ONE
+//   test of k < K_eff, so a depth that is no multiple of 4 would bring in up to three elements beyond it.  gemm_f32, gemm_f32s and
+//   gemm_bf16_direct refuse the other layouts (the conversion passes + gemm_bf16_nt mask per element and take any layout).  With
+//   split_k > 1 it takes no bias either: a slice that starts at or beyond K_eff returns before its epilogue.
 // split_k > 1: grid.z slices of K, combined with float atomics INTO C (C must hold the value to
 // accumulate onto, e.g. zeros); bias is added by slice 0.
 struct GemmArgs {
@@ -37,6 +41,11 @@ struct GemmArgs {
     int nt8 = 1;         // bf16 NT form: the phased LDS-DMA kernel (gemm_bf16_p8.hip) where the shape allows; 0: gemm_bf16_nt256_kernel
 };
 hipError_t gemm_f32(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g);
+// what gemm_f32 launches for a problem, decided from the arguments alone (host arithmetic, no device): tile 0 128x128, 1 32x128, 2 64x64,
+// 3 skinny, -1 nothing to launch (no rows or columns); fast: buffer-load staging; db: double-buffered LDS; persist: the persistent
+// 128x128 kernel; the grid; err: the refusal gemm_f32 returns instead of launching
+struct GemmF32Form { int tile; bool fast, db, persist; unsigned gx, gy, gz; hipError_t err; };
+GemmF32Form gemm_f32_form(bool a_mc, bool b_nc, const GemmArgs& g);
 // same contract on the bf16 matrix cores: every fp32 operand element is split into three bf16 in registers and
 // six partial products are accumulated in fp32 (gemm_f32s.hip; fp32-accurate, 128x128 tiles only: g.thin ignored)
 hipError_t gemm_f32s(hipStream_t st, bool a_mc, bool b_nc, const GemmArgs& g);
