@@ -347,6 +347,27 @@ KnnPlan knn_plan(int n, int N, int k, int chunk_opt);
 size_t knn_ws_bytes(const KnnPlan& p, int n, int N, int k);      // workspace: the rows' norms + the parts' lists (n x parts x k x 8 bytes)
 hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, void* ws);
 
+// ---------------------------------------------------------------- aggregate-posterior diagnostics (agg.hip)
+// log q(z_i) under the aggregate posterior of N encoded rows (contract: include/argsim_vae.h, avae_agg_logq): z (n, dim), mu and
+// lv (N, dim) fp32 row-major, 16-byte aligned, dim a multiple of 4 in 4..1024, 1 <= N <= 2^31 - 256; logq (n); logqx (n) or null,
+// the own pair's density where self_base >= 0 (query i's own bank row is self_base + i)
+struct AggArgs {
+    const float* z; const float* mu; const float* lv;
+    int n, N, dim;
+    int64_t self_base;
+    float* logq; float* logqx;
+};
+// the launch shape (agg.hip, agg_plan: a pure host function of the problem shape): query tiles of 128 rows, the bank cut into
+// `parts` runs of `chunk` rows, one workgroup per (query tile, part); chunk_opt > 0 caps chunk (option agg_chunk)
+struct AggPlan { int qtiles, parts, chunk; };
+AggPlan agg_plan(int n, int N, int dim, int chunk_opt);
+size_t agg_ws_bytes(const AggPlan& p, int n);                    // workspace: the parts' (max, sum) pairs (parts x n x 8 bytes)
+hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, void* ws);
+// out (4, dim) = per dimension over the N rows: mean mu, unbiased variance of mu (0 for N = 1), mean exp(lv), mean KL term; sums in
+// double, fixed order
+size_t moments_ws_bytes(int N, int dim);
+hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, void* ws);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

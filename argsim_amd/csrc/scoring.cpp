@@ -1,5 +1,5 @@
 // scoring.cpp -- scoring and search over latent rows: the importance-weighted likelihood (avae_score, avae_score_z; score.hip) and
-// nearest neighbours (avae_knn; knn.hip).
+// nearest neighbours (avae_knn; knn.hip) and the aggregate-posterior diagnostics (avae_agg_logq, avae_latent_moments; agg.hip).
 #include "ctx.h"
 
 using namespace avae;
@@ -142,6 +142,46 @@ int avae_knn(avae_handle h, const float* q, int32_t n, const float* bank, int32_
     a.q = q; a.bank = bank; a.n = n; a.N = N; a.dim = dim; a.k = kc->k; a.metric = kc->metric;
     a.idx_base = kc->idx_base; a.self_base = kc->self_base; a.carry = kc->carry; a.out_idx = out_idx; a.out_score = out_score;
     AV_CHECK(knn_search(h->stream, a, p, h->ws));
+    return 0;
+}
+
+// ---------------------------------------------------------------- aggregate-posterior diagnostics (contract: include/argsim_vae.h, avae_agg_logq /
+// avae_latent_moments; kernels: agg.hip)
+int avae_agg_logq(avae_handle h, const float* z, int32_t n, const float* mu, const float* lv, int32_t N, int32_t dim, const avae_agg_config* ac,
+                  float* logq, float* logqx)
+{
+    if (!h) return 1;
+    if (!ac) return fail(h, "agg config is null");
+    if (!z || !mu || !lv || !logq) return fail(h, "agg: z, mu, lv and logq must be given");
+    if (n < 1 || N < 1) return fail(h, "agg: n and N must be >= 1");
+    if (N > 0x7fffffff - 256) return fail(h, "agg: at most 2^31 - 256 bank rows per call");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "agg: dim must be a multiple of 4 in [4, 1024]");
+    if (((uintptr_t)z | (uintptr_t)mu | (uintptr_t)lv) & 15) return fail(h, "agg: z, mu and lv must be 16-byte aligned");
+    if (ac->self_base < -1) return fail(h, "agg: self_base must be >= -1");
+    if (ac->self_base >= 0 && ac->self_base + (int64_t)n > (int64_t)N) return fail(h, "agg: self_base + n exceeds N (query i's own bank row is self_base + i)");
+    if (logqx && ac->self_base < 0) return fail(h, "agg: logqx needs self_base >= 0");
+    if (ac->reserved[0] != 0 || ac->reserved[1] != 0) return fail(h, "agg: the reserved fields must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    const AggPlan p = agg_plan(n, N, dim, h->agg_chunk);
+    if ((long long)p.qtiles * p.parts > 0x7fffffffLL) return fail(h, "agg: too many (query tile, bank part) workgroups for one launch");
+    AV_TRY(reserve_ws(h, agg_ws_bytes(p, n) + 4096));            // sized once per call; nothing is allocated between the launches
+    AggArgs a{};
+    a.z = z; a.mu = mu; a.lv = lv; a.n = n; a.N = N; a.dim = dim; a.self_base = ac->self_base; a.logq = logq; a.logqx = logqx;
+    AV_CHECK(agg_logq(h->stream, a, p, h->ws));
+    return 0;
+}
+
+int avae_latent_moments(avae_handle h, const float* mu, const float* lv, int32_t N, int32_t dim, float* out)
+{
+    if (!h) return 1;
+    if (!mu || !lv || !out) return fail(h, "moments: mu, lv and out must be given");
+    if (N < 1) return fail(h, "moments: N must be >= 1");
+    if (N > 0x7fffffff - 256) return fail(h, "moments: at most 2^31 - 256 rows per call");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "moments: dim must be a multiple of 4 in [4, 1024]");
+    if (((uintptr_t)mu | (uintptr_t)lv) & 15) return fail(h, "moments: mu and lv must be 16-byte aligned");
+    AV_CHECK(hipSetDevice(h->device));
+    AV_TRY(reserve_ws(h, moments_ws_bytes(N, dim) + 4096));
+    AV_CHECK(latent_moments(h->stream, mu, lv, N, dim, out, h->ws));
     return 0;
 }
 

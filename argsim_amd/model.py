@@ -14,6 +14,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) importance-weighted log p(x), k draws        -> VAE.score(src, tgt, k, ...) / score(vae, src, k, seed)
     (new) teacher-forced log p(tgt | z)                -> VAE.score_z(z, tgt)
     (new) nearest neighbours among latent rows         -> VAE.neighbors(queries, bank, k, metric) / neighbors(vae, ...)
+    (new) aggregate-posterior diagnostics (MI, AU)     -> VAE.posterior_stats(src) / VAE.log_q(z, mu, lv) / VAE.latent_moments(mu, lv)
 """
 import ctypes as C
 
@@ -489,6 +490,98 @@ class VAE:
             score = 0.0 - score
         return (idx, score) if as_torch else (idx.cpu().numpy(), score.cpu().numpy())
 
+    # ------------------------------------------------------------------ aggregate-posterior diagnostics
+    def _encode_dev(self, src):
+        """encode() whose results stay on the device: (mu, lv) float32 tensors (b, dim_rep)"""
+        src = self._ids(self.trim(src))
+        b, R = src.shape[0], self.cfg['dim_rep']
+        mu = torch.empty((b, R), dtype=torch.float32, device=self.device)
+        lv = torch.empty((b, R), dtype=torch.float32, device=self.device)
+        self._stream()
+        self._ck(self._l.avae_encode(self._h, C.c_void_p(src.data_ptr()), b, src.shape[1], C.c_void_p(mu.data_ptr()), C.c_void_p(lv.data_ptr())))
+        return mu, lv
+
+    def _dev_f32(self, x):
+        return (x if isinstance(x, torch.Tensor) else torch.as_tensor(np.array(x, order='C'))).to(self.device).contiguous()
+
+    def latent_moments(self, mu, lv):
+        """per-dimension moments of the posteriors N(mu_i, diag exp(lv_i)) over the N rows (include/argsim_vae.h, avae_latent_moments)
+        -> dict of float32 (dim,): mean (of mu), var (unbiased variance of mu, 0 for N = 1: a unit is active where it exceeds a
+        threshold), sigma2 (mean of exp(lv)) and kl_dim (mean of 1/2 (mu^2 + exp(lv) - lv - 1)).  mu and lv are (N, dim) float32 numpy
+        arrays or torch tensors, dim a multiple of 4 up to 1024; the result is numpy, or tensors on the device when mu is a tensor."""
+        _check_agg_args(mu, mu, lv, None)
+        as_torch = isinstance(mu, torch.Tensor)
+        mu, lv = self._dev_f32(mu), self._dev_f32(lv)
+        N, dim = mu.shape
+        out = torch.empty((4, dim), dtype=torch.float32, device=self.device)
+        self._stream()
+        self._ck(self._l.avae_latent_moments(self._h, C.c_void_p(mu.data_ptr()), C.c_void_p(lv.data_ptr()), N, dim, C.c_void_p(out.data_ptr())))
+        if not as_torch:
+            out = out.cpu().numpy()
+        return dict(mean=out[0], var=out[1], sigma2=out[2], kl_dim=out[3])
+
+    def log_q(self, z, mu, lv, self_index=None):
+        """log-density of every row of z (n, dim) under the aggregate posterior 1/N sum_j N(mu_j, diag exp(lv_j)) of the N rows of
+        mu, lv (include/argsim_vae.h, avae_agg_logq) -> logq float32 (n,).  self_index = i0 (True: 0): row i of z was drawn from
+        bank row i0 + i, and the result is (logq, logqx) with logqx[i] = log N(z_i; mu_{i0+i}, diag exp(lv_{i0+i})), the own pair's
+        term as it entered the sum.  Arrays are float32 numpy or torch, dim a multiple of 4 up to 1024 (any width, not only
+        dim_rep); the result is numpy, or tensors on the device when z is a tensor."""
+        i0 = _check_agg_args(z, mu, lv, self_index)
+        as_torch = isinstance(z, torch.Tensor)
+        z, mu, lv = self._dev_f32(z), self._dev_f32(mu), self._dev_f32(lv)
+        n, dim, N = z.shape[0], z.shape[1], mu.shape[0]
+        logq = torch.empty(n, dtype=torch.float32, device=self.device)
+        logqx = torch.empty(n, dtype=torch.float32, device=self.device) if i0 >= 0 else None
+        ac = _lib.AvaeAggConfig(i0, (C.c_int32 * 2)(0, 0))
+        self._stream()
+        self._ck(self._l.avae_agg_logq(self._h, C.c_void_p(z.data_ptr()), n, C.c_void_p(mu.data_ptr()), C.c_void_p(lv.data_ptr()), N, dim,
+                                       C.byref(ac), C.c_void_p(logq.data_ptr()), C.c_void_p(logqx.data_ptr()) if logqx is not None else None))
+        if not as_torch:
+            logq, logqx = logq.cpu().numpy(), (logqx.cpu().numpy() if logqx is not None else None)
+        return logq if logqx is None else (logq, logqx)
+
+    def posterior_stats(self, src, samples=1, seed=0, eps=None, batch=128, au_threshold=0.01, return_parts=False):
+        """whether the code carries information, over the N sentences of src (ids (N, S)): encodes in batches of `batch` rows (mu
+        and lv stay on the device), draws z = mu + exp(lv / 2) eps `samples` times per sentence -- eps is the caller's
+        (samples, N, dim_rep) array, or float32 values of numpy.random.default_rng(seed).standard_normal -- and returns a dict:
+            kl           sum_j kl_dim: the mean KL(q(z | x) || p(z)) per sentence, in nats
+            kl_dim       (R,) its share per latent dimension;  var_mu (R,) the unbiased variance of the posterior mean over the data
+            au           active units: how many dimensions have var_mu > au_threshold (Burda et al.)
+            mi           mean(logqx - logq): the mutual information I(x; z) under the encoder, at most log N (Hoffman & Johnson)
+            kl_marginal  mean(logq - logp): KL(q(z) || p(z)), p the standard normal;  in expectation kl = mi + kl_marginal
+            n            N
+        with return_parts also the per-sample arrays logq, logqx, logp (samples, N) and z (samples, N, R), and mu, lv (N, R)."""
+        samples, seed, batch, thr = _check_stats_args(samples, seed, batch, au_threshold)
+        src = np.asarray(src) if not isinstance(src, torch.Tensor) else src
+        if len(src.shape) != 2 or src.shape[0] < 1:
+            raise ValueError("src must be (N, S) with N >= 1, got %s" % (tuple(src.shape),))
+        N, R = src.shape[0], self.cfg['dim_rep']
+        if R % 4 or R > 1024:
+            raise ValueError("posterior_stats needs dim_rep a multiple of 4 up to 1024, got %d" % R)
+        if eps is None:
+            eps = np.random.default_rng(seed).standard_normal((samples, N, R), dtype=np.float32)
+        ep = torch.as_tensor(np.ascontiguousarray(eps, dtype=np.float32)).to(self.device).contiguous()
+        if tuple(ep.shape) != (samples, N, R):
+            raise ValueError("eps must be (samples, N, dim_rep) = %s, got %s" % ((samples, N, R), tuple(ep.shape)))
+        mu = torch.empty((N, R), dtype=torch.float32, device=self.device)
+        lv = torch.empty((N, R), dtype=torch.float32, device=self.device)
+        for b0 in range(0, N, batch):
+            mu[b0:b0 + batch], lv[b0:b0 + batch] = self._encode_dev(src[b0:b0 + batch])
+        mom = self.latent_moments(mu, lv)
+        z = mu[None] + torch.exp(0.5 * lv)[None] * ep
+        logq = torch.empty((samples, N), dtype=torch.float32, device=self.device)
+        logqx = torch.empty((samples, N), dtype=torch.float32, device=self.device)
+        for s in range(samples):
+            logq[s], logqx[s] = self.log_q(z[s], mu, lv, self_index=0)
+        logp = -0.5 * (z.double() ** 2).sum(-1) - 0.5 * R * float(np.log(2.0 * np.pi))
+        kl_dim, var_mu = mom['kl_dim'].cpu().numpy(), mom['var'].cpu().numpy()
+        res = dict(kl=float(kl_dim.astype(np.float64).sum()), kl_dim=kl_dim, var_mu=var_mu, au=int((var_mu > thr).sum()),
+                   mi=float((logqx.double() - logq.double()).mean()), kl_marginal=float((logq.double() - logp).mean()), n=N)
+        if return_parts:
+            res.update(logq=logq.cpu().numpy(), logqx=logqx.cpu().numpy(), logp=logp.cpu().numpy(), z=z.cpu().numpy(),
+                       mu=mu.cpu().numpy(), lv=lv.cpu().numpy())
+        return res
+
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
 
@@ -526,6 +619,54 @@ def _check_knn_args(queries, bank, k, metric, exclude_self=False, block=None):
     if block is not None and (isinstance(block, bool) or int(block) != block or not 1 <= block < (1 << 31) - 256):
         raise ValueError("block must be an integer in [1, 2^31 - 256), got %r" % (block,))
     return int(k), KNN_METRICS[metric], i0, None if block is None else int(block)
+
+
+def _check_agg_args(z, mu, lv, self_index=None):
+    """the argument rules of avae_agg_logq (and, with z = mu, of avae_latent_moments), checked before anything touches the device
+    -> self_base (-1: off)"""
+    for name, x in (('z', z), ('mu', mu), ('lv', lv)):
+        if not isinstance(x, (np.ndarray, torch.Tensor)):
+            raise ValueError("%s must be a numpy array or a torch tensor, got %s" % (name, type(x).__name__))
+        if x.dtype not in (np.float32, torch.float32):
+            raise ValueError("%s must be float32, got %s" % (name, x.dtype))
+        if len(x.shape) != 2:
+            raise ValueError("%s must be (rows, dim), got %s" % (name, tuple(x.shape)))
+        if isinstance(x, torch.Tensor) and x.is_contiguous() and x.data_ptr() % 16:
+            raise ValueError("%s must be 16-byte aligned (a view that starts inside a row block is not)" % name)
+    if tuple(mu.shape) != tuple(lv.shape):
+        raise ValueError("mu and lv must have the same shape, got %s and %s" % (tuple(mu.shape), tuple(lv.shape)))
+    n, dim, N = z.shape[0], z.shape[1], mu.shape[0]
+    if n < 1 or N < 1:
+        raise ValueError("z and mu must have at least one row, got %s and %s" % (tuple(z.shape), tuple(mu.shape)))
+    if N > (1 << 31) - 256 or n > (1 << 31) - 256:
+        raise ValueError("at most 2^31 - 256 rows per call, got %d and %d" % (n, N))
+    if mu.shape[1] != dim:
+        raise ValueError("z and mu must have the same dim, got %d and %d" % (dim, mu.shape[1]))
+    if dim % 4 or not 4 <= dim <= 1024:
+        raise ValueError("dim must be a multiple of 4 in [4, 1024], got %d" % (dim,))
+    if self_index is None or self_index is False:
+        return -1
+    if self_index is True:
+        self_index = 0
+    if isinstance(self_index, (bool, np.bool_)) or int(self_index) != self_index or self_index < 0:
+        raise ValueError("self_index must be None, True or an integer i0 >= 0, got %r" % (self_index,))
+    if int(self_index) + n > N:
+        raise ValueError("self_index + n = %d exceeds N = %d (row i of z is a sample of bank row self_index + i)" % (int(self_index) + n, N))
+    return int(self_index)
+
+
+def _check_stats_args(samples, seed, batch, au_threshold):
+    """the argument rules of VAE.posterior_stats -> (samples, seed, batch, au_threshold)"""
+    if isinstance(samples, bool) or int(samples) != samples or not 1 <= samples <= 1 << 20:
+        raise ValueError("samples must be an integer in [1, 2^20], got %r" % (samples,))
+    if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be an integer in [0, 2^64), got %r" % (seed,))
+    if isinstance(batch, bool) or int(batch) != batch or batch < 1:
+        raise ValueError("batch must be an integer >= 1, got %r" % (batch,))
+    t = float(au_threshold)
+    if not t >= 0.0:
+        raise ValueError("au_threshold must be a number >= 0, got %r" % (au_threshold,))
+    return int(samples), int(seed), int(batch), t
 
 
 def _check_score_args(k, seed):
@@ -607,3 +748,18 @@ def score(vae, src, k=1, seed=0):
 def neighbors(vae, queries, bank, k=10, metric='cos', exclude_self=False, block=None, return_distance=False):
     """the k nearest bank rows of every query row: VAE.neighbors"""
     return vae.neighbors(queries, bank, k, metric, exclude_self, block, return_distance)
+
+
+def latent_moments(vae, mu, lv):
+    """per-dimension moments of the posteriors over the rows: VAE.latent_moments"""
+    return vae.latent_moments(mu, lv)
+
+
+def log_q(vae, z, mu, lv, self_index=None):
+    """log-density of the rows of z under the aggregate posterior: VAE.log_q"""
+    return vae.log_q(z, mu, lv, self_index)
+
+
+def posterior_stats(vae, src, samples=1, seed=0, eps=None, batch=128, au_threshold=0.01, return_parts=False):
+    """active units, mutual information and marginal KL over the sentences of src: VAE.posterior_stats"""
+    return vae.posterior_stats(src, samples, seed, eps, batch, au_threshold, return_parts)

@@ -42,6 +42,9 @@ def parse_args(argv=None):
                    "names are unverified against a real TensorFlow (ckpt.py)")
     p.add_argument('--iw', default=0, type=int, help="validation also reports the K-sample importance-weighted NLL per sentence "
                    "and its per-token perplexity (nll_iw, ppl_iw); 0 = off")
+    p.add_argument('--collapse-stats', action='store_true', help="validation also logs the posterior-collapse diagnostics mi (mutual "
+                   "information I(x; z)), au (active units) and kl_marginal (KL(q(z) || p(z))) of VAE.posterior_stats, one draw per "
+                   "sentence; with several ranks they are computed by rank 0 over ITS share of the validation chunks only")
     p.add_argument('--profile-run', action='store_true', help=argparse.SUPPRESS)    # the child that --profile traces
     A = p.parse_args(argv)
     if not 0 <= A.iw <= 1 << 20:
@@ -150,6 +153,16 @@ def summ_iw(model, valid, batch_valid, k, seed, rank=0, world=1, group=None):
         sums = [float(x) for x in t]
     b, n, m = sums
     return -b / m, math.exp(-b / n)
+
+
+def collapse_stats(model, valid, batch_valid, seed, world=1):
+    """{mi, au, kl_marginal} of VAE.posterior_stats over rank 0's share of the validation chunks (the chunks ``summ`` deals to
+    it: all of them in a single process), one draw per sentence from ``seed``.  No collective: only rank 0 calls this."""
+    import numpy as np
+    from .util_np import partition
+    rows = np.concatenate([np.arange(i, j) for i, j in list(partition(len(valid), batch_valid, discard=False))[0::world]])
+    st = model.posterior_stats(valid[rows], samples=1, seed=seed)
+    return dict(mi=st['mi'], au=st['au'], kl_marginal=st['kl_marginal'])
 
 
 def with_global_counts(gen, eos, group):
@@ -288,6 +301,8 @@ def main(argv=None):
                            train_loss_gen=lg, train_loss_kld=lk, sentences_per_sec=A.valid_every * T.batch_train / dt)
                 if A.iw > 0:
                     rec.update(nll_iw=nll_iw, ppl_iw=ppl_iw)
+                if A.collapse_stats:
+                    rec.update(collapse_stats(model, valid, T.batch_valid, A.seed, world))
                 log.write(json.dumps(rec) + "\n")
                 log.flush()
                 print(rec)

@@ -322,6 +322,46 @@ typedef struct avae_knn_config {
 int  avae_knn(avae_handle h, const float* q, int32_t n, const float* bank, int32_t N, int32_t dim,
               const avae_knn_config* kc, int64_t* out_idx /* (n,k) */, float* out_score /* (n,k) */);
 
+/* ---- aggregate-posterior diagnostics ------------------------------------------------------ */
+/* Whether the latent code carries information: the density of samples under the AGGREGATE posterior q(z) = 1/N sum_j q(z | x_j)
+ * of N encoded sentences, from which the caller forms the mutual information I(x; z) = E[log q(z | x) - log q(z)] and the marginal
+ * KL(q(z) || p(z)) = E[log q(z) - log p(z)], and the per-dimension moments behind the active-unit count.  The (n, N) panel of pair
+ * terms never reaches memory.  z (n, dim), mu and lv (N, dim) are row-major float32 device arrays, 16-byte aligned (e.g. mu and
+ * lv of avae_encode); dim is a multiple of 4 in [4, 1024] and independent of the handle's dim_rep; n >= 1, 1 <= N <= 2^31 - 256.
+ * Both entries are enqueued on the handle's stream; nothing is synchronised.
+ *   pair    t(i, j) = -1/2 sum_d [(z_id - mu_jd)^2 a_jd + lv_jd], a_jd = expf(-lv_jd), in fp32 in its DIRECT form: the difference
+ *           is formed before the square, then one fused multiply-add of the square with a_jd; even and odd dims run in two
+ *           chains that are added at the end, then c_j = sum_d lv_jd (its own fixed-order fp32 sum) is added and the sum is
+ *           halved.  The expansion into z^2 a - 2 z mu a + mu^2 a is NOT used: it cancels in the own pair, where z - mu is
+ *           sigma eps while the three products are of size mu^2 / sigma^2.  A pair's value depends on the two
+ *           rows alone, not on n, N, the tile or the launch shape.
+ *   logq    logq[i] = logsumexp_j t(i, j) - log N - (dim / 2) log 2 pi, the maximum subtracted before the exponentials: an online
+ *           (max, sum) pair per query over 64-row bank tiles, the parts of the bank merged in part order.
+ *   logqx   self_base >= 0: logqx[i] = t(i, self_base + i) - (dim / 2) log 2 pi = log q(z_i | x_{self_base + i}), the very value
+ *           that entered the sum (queries that are samples from rows self_base .. self_base + n - 1 of the bank).
+ *   edges   a bank row whose t is -inf (lv = +inf, say) weighs 0; a query whose every term is -inf gets -inf, not NaN.  A NaN in a
+ *           bank row reaches every query, a NaN in a query row that row alone (logq, and logqx where the own pair holds it).
+ *           Inputs are not checked.  Rows beyond N and n are never read or stored.
+ *   bits    no float atomics, fixed-order reductions, a launch shape that is a function of (n, N, dim) and option agg_chunk
+ *           alone: the same arguments and options give the same bits.  Another agg_chunk sums in another order.
+ * avae_latent_moments: out (4, dim), per dimension j over the N rows
+ *           row 0  mean of mu_j
+ *           row 1  unbiased variance of mu_j (divisor N - 1; exactly 0 for N = 1), two passes: the mean, then centred squares
+ *           row 2  mean of exp(lv_j)
+ *           row 3  mean of KL_j = 1/2 (mu_j^2 + exp(lv_j) - lv_j - 1)
+ *           summed in double on the device in a fixed order, rounded to fp32 at the end.
+ * Errors (text through avae_last_error): a null ac, z, mu, lv, logq or out; n < 1, N < 1 or N > 2^31 - 256; dim not a multiple of
+ * 4 in [4, 1024]; z, mu or lv not 16-byte aligned; self_base < -1; self_base + n > N; a logqx with self_base = -1; reserved != 0.
+ * Option agg_chunk (avae_set_option; a test aid): caps the bank rows of a part, so that small tests run several parts and the
+ * merge; 0 lets the planner decide.  A cap that would give more than 1024 parts is raised.                                  */
+typedef struct avae_agg_config {
+    int64_t self_base;  /* -1: off; else query i's own bank row is self_base + i */
+    int32_t reserved[2];
+} avae_agg_config;
+int  avae_agg_logq(avae_handle h, const float* z, int32_t n, const float* mu, const float* lv, int32_t N, int32_t dim,
+                   const avae_agg_config* ac, float* logq /* (n) */, float* logqx /* (n), optional; needs self_base >= 0 */);
+int  avae_latent_moments(avae_handle h, const float* mu, const float* lv, int32_t N, int32_t dim, float* out /* (4, dim) */);
+
 #ifdef __cplusplus
 }
 #endif
