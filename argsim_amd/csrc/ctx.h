@@ -73,6 +73,7 @@ struct avae_ctx {
                           // exchange): 0 never, 1 wherever the geometry allows, 2 auto -- where few rows are alive per step (rs_pick)
     int knn_chunk = 0;    // avae_knn test aid: caps the bank rows one workgroup walks (small tests run many parts and the merge); 0: knn_plan decides
     int agg_chunk = 0;    // avae_agg_logq test aid: caps the bank rows of a part (small tests run several parts and the merge); 0: agg_plan decides
+    int probe_chunk = 0;  // avae_probe_fit / avae_probe_decision test aid: caps the rows of a part (small tests run several parts and the merge); 0: probe_plan decides
     int gru_bf16 = 1;     // compute_dtype 1 only: the recurrent product of the team kernels takes bf16 operands too (0: fp32 recurrence)
     // offsets
     int64_t oE = 0, oKout = 0, oBout = 0, oWmu = 0, oBmu = 0, oWlv = 0, oBlv = 0, oWex = 0, oBex = 0;

@@ -368,6 +368,34 @@ hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, void* ws
 size_t moments_ws_bytes(int N, int dim);
 hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, void* ws);
 
+// ---------------------------------------------------------------- linear probes of latent rows (probe.hip)
+// P independent L2 logistic regressions over x (N, dim) in lockstep (contract: include/argsim_vae.h, avae_probe_fit).  The host loop
+// (probing.cpp) strings these launches together; every buffer is workspace laid out by the caller.
+constexpr int kProbeTile = 32;        // problems per tile: P is padded to it with zero-cost problems
+constexpr int kProbeAlphas = 7;       // step lengths one probe_trial launch evaluates
+constexpr int kProbeMaxParts = 256;
+// the launch shape (probe.hip, probe_plan: a pure host function of the problem shape): problem tiles of 32, the rows cut into
+// `parts` runs of `chunk` rows, one workgroup per (part, problem tile); chunk_opt > 0 caps chunk (option probe_chunk).  parts and
+// chunk do not depend on P.  LD = dim + 4: the row stride of a problem's vectors, the bias at [dim]
+struct ProbePlan { int ptiles, Ppad, LD, parts, chunk; };
+ProbePlan probe_plan(int N, int P, int dim, int chunk_opt);
+struct ProbeWs {
+    float *sT, *z, *D, *u;            // (N, Ppad): signed costs, decisions x~ w, curvature, x~ p
+    float *W, *G, *Dv, *Rv, *Pv;      // (Ppad, LD), ONE run of 5 Ppad LD floats: iterate, gradient, CG direction, CG residual, Newton step
+    float *gp, *lp;                   // (parts, LD, Ppad) and (parts, Ppad): the parts' partials of a pass
+    double* tp;                       // (parts, kProbeAlphas, Ppad): the parts' trial loss sums
+    int* is; float* fs; double* ds;   // (Ppad, 8) each: per-problem state words (probe.hip)
+    int N, dim, LD, Ppad, parts, chunk;
+};
+struct ProbeAlphas { int n, last; float a[kProbeAlphas]; };      // a trial round: its step lengths; last: no round follows
+hipError_t probe_prepare(hipStream_t st, const ProbeWs& b, const float* s, int P);                 // state of a fresh fit, s (P, N) -> sT
+hipError_t probe_pass(hipStream_t st, const ProbeWs& b, const float* x, int mode);                 // 0 GRAD (W), 1 HV (Dv), 2 PANEL (Pv -> u)
+hipError_t probe_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_cg, float tol, const ProbeAlphas& al);
+hipError_t probe_trial(hipStream_t st, const ProbeWs& b, const ProbeAlphas& al);
+hipError_t probe_finish(hipStream_t st, const ProbeWs& b, int P, float* w, float* stats);
+// out (n, P) = x~ w^T; W: (Ppad, LD) floats of workspace
+hipError_t probe_decision(hipStream_t st, const ProbePlan& p, const float* x, int n, int dim, const float* w, int P, float* W, float* out);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

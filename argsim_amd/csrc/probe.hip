@@ -1,0 +1,585 @@
+// probe.hip -- linear probes of latent rows: P independent L2-regularised logistic regressions over one matrix X (N, dim), solved
+// in lockstep by a truncated Newton method (contract: include/argsim_vae.h, avae_probe_fit / avae_probe_decision).
+//
+//   probe_pass   grid = (row parts) x (problem tiles of 32).  A workgroup walks its part in tiles of 128 rows.  Per tile:
+//                  A  the 128 x 32 panel tile X V^T with the NT main loop of knn_tile (k-contiguous operands, 32-deep K tiles through
+//                     LDS, v_mfma_f32_32x32x2_f32, the next K tile's loads in flight), one 32 x 32 MFMA tile per wave; the bias
+//                     column of x~ = (x, 1) is never materialised: the bias component of the vector is added in the epilogue;
+//                  E  the epilogue in registers: GRAD stores the decision z and the curvature D = |s| sigma(m) sigma(-m) and forms
+//                     the residual -|s| sgn(s) sigma(-m) and the loss; HV forms D o u; both leave their 128 x 32 tile in LDS;
+//                  B  X_tile^T (dim x 128) times that tile, wave w owning dims [w dim4, (w + 1) dim4): the row pair (2 i, 2 i + 1) is
+//                     one MFMA step.  The 128 x dim row tile does not fit in LDS at dim 1024 (512 KB), so B RE-READS the tile's rows
+//                     from memory straight into the MFMA operand registers (for one row 32 lanes read consecutive floats): X comes
+//                     from HBM once per pass, the second read is served by L2 / the Infinity Cache while the tile is hot.  This is
+//                     done at every dim, not only where the tile would not fit.
+//                The (dim + 1) x 32 partial of the part goes to the workspace; the bias row is the column sum of the tile in E.
+//                PANEL mode is A + the bias alone: the panel X~ V^T (the Newton step's u, and avae_probe_decision).
+//   probe_vec    one workgroup per problem: merges the parts' partials in part order, does the CG and Newton vector updates (dot
+//                products over dim + 1 in double, a fixed tree), the Armijo bookkeeping and the freeze flags.
+//   probe_trial  elementwise over the kept panels z = X~ w and u = X~ p: the loss sums at up to 7 step lengths, in double (the
+//                Armijo test compares losses that differ in the 9th digit near the optimum), per part; X is not read.
+// A problem is one column of every MFMA tile and one column of every panel: its arithmetic does not see the other columns, and the
+// row parts are a function of (N, probe_chunk) alone, so its bits do not depend on P, on its position or on its companions.  A
+// launch whose 32 problems are all idle returns at once; an idle problem in a busy tile is computed and ignored.  No float atomics.
+#include "kernels.h"
+
+#include <algorithm>
+#include <type_traits>
+
+namespace avae {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kBK = 32;
+constexpr int kLDK = kBK + 4;      // k-contiguous tile row stride (floats): conflict-free b128 reads (gemm_f32.hip)
+constexpr int kTR = 128;           // rows per tile
+constexpr int kTP = kProbeTile;    // problems per tile
+constexpr int kNA = kProbeAlphas;  // step lengths per probe_trial launch
+
+// per-problem state words (ProbeWs::is, ::fs, ::ds)
+enum { I_ITER = 0, I_STATUS = 1, I_FROZEN = 2, I_CG = 3, I_LS = 4, I_ALIVE = 5 };
+enum { F_F = 0, F_GNORM = 1, F_G0 = 2 };
+enum { D_RR = 0, D_GTP = 1, D_WTP = 2, D_PP = 3, D_PHI0 = 4 };
+
+// stage one k-contiguous operand tile (ROWS x 32) global -> registers -> LDS; rows >= X and k >= K read as zero
+template <int ROWS>
+__device__ __forceinline__ void load_tile(float4 (&r)[(ROWS + 31) / 32], const float* __restrict__ P, int ld, int x0, int X, int k0, int K, int tid)
+{
+#pragma unroll
+    for (int rep = 0; rep < (ROWS + 31) / 32; ++rep) {
+        const int f = tid + 256 * rep;
+        const int x = x0 + (f >> 3), k = k0 + ((f & 7) << 2);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (x < X && k < K) v = *reinterpret_cast<const float4*>(P + (size_t)x * ld + k);
+        r[rep] = v;
+    }
+}
+template <int ROWS>
+__device__ __forceinline__ void store_tile(float* __restrict__ s, const float4 (&r)[(ROWS + 31) / 32], int tid)
+{
+#pragma unroll
+    for (int rep = 0; rep < (ROWS + 31) / 32; ++rep) {
+        const int f = tid + 256 * rep;
+        *reinterpret_cast<float4*>(s + (f >> 3) * kLDK + ((f & 7) << 2)) = r[rep];
+    }
+}
+
+struct ProbePassArgs {
+    const float* x;          // (N, dim)
+    const float* v;          // (Ppad, LD): the vector of every problem, its bias component at [dim]
+    const float* sT;         // (N, Ppad) signed costs
+    float* z; float* D;      // (N, Ppad) panels: GRAD writes both, HV reads D
+    float* out; int ldo, pout;      // PANEL: out[row * ldo + p] for p < pout
+    float* gp;               // (parts, LD, Ppad) partials of X~^T (tile)
+    float* lp;               // (parts, Ppad) loss partials (GRAD)
+    const int* flags; int flag;     // per-problem state words; the launch returns where no problem of the tile has is[flag] != 0
+    int N, dim, LD, Ppad, parts, chunk;
+};
+
+// MODE 0 GRAD, 1 HV, 2 PANEL.  DT: 32-dim MFMA tiles per wave in step B (4 x 32 x DT >= dim).
+template <int MODE, int DT>
+__global__ __launch_bounds__(256) void probe_pass_kernel(ProbePassArgs a)
+{
+    constexpr int VW = DT >= 4 ? 4 : DT;          // floats a lane loads per row in step B
+    __shared__ __attribute__((aligned(16))) float s_tile[(kTR + kTP) * kLDK];
+    __shared__ float s_R[kTR * kTP];
+    __shared__ float s_red[2][8][kTP];
+    float* As = s_tile;
+    float* Bs = s_tile + kTR * kLDK;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = lane >> 5, l31 = lane & 31;
+    const int part = blockIdx.x % a.parts, pt = blockIdx.x / a.parts;
+    const int p0 = pt * kTP, prob = p0 + l31;
+    const int dim = a.dim, Ppad = a.Ppad;
+    if (a.flags) {
+        const int busy = tid < kTP ? a.flags[(size_t)(p0 + tid) * 8 + a.flag] : 0;
+        if (!__syncthreads_or(busy)) return;
+    }
+    const long long c_begin = (long long)part * a.chunk;
+    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    const float vb = a.v[(size_t)prob * a.LD + dim];
+
+    f32x16 g[MODE == 2 ? 1 : DT];
+    if (MODE != 2) {
+#pragma unroll
+        for (int t = 0; t < DT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) g[t][r] = 0.f;
+    }
+    float bsum = 0.f, lsum = 0.f;
+
+    for (int row0 = (int)c_begin; row0 < c_end; row0 += kTR) {
+        // ---- A: acc = X[row0 + 32 wave ..][:] . V[p0 ..][:]^T
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        float4 ra[kTR / 32], rb[1];
+        load_tile<kTR>(ra, a.x, dim, row0, c_end, 0, dim, tid);
+        load_tile<kTP>(rb, a.v, a.LD, p0, Ppad, 0, dim, tid);
+        for (int k0 = 0; k0 < dim; k0 += kBK) {
+            store_tile<kTR>(As, ra, tid);
+            store_tile<kTP>(Bs, rb, tid);
+            if (k0 + kBK < dim) {         // the next K tile's loads go out before the barrier that publishes this one
+                load_tile<kTR>(ra, a.x, dim, row0, c_end, k0 + kBK, dim, tid);
+                load_tile<kTP>(rb, a.v, a.LD, p0, Ppad, k0 + kBK, dim, tid);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int qq = 0; qq < 4; ++qq) {
+                const float4 av = *reinterpret_cast<const float4*>(As + (32 * wave + l31) * kLDK + 8 * qq + 4 * h);
+                const float4 bv = *reinterpret_cast<const float4*>(Bs + l31 * kLDK + 8 * qq + 4 * h);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
+            }
+            __syncthreads();
+        }
+
+        // ---- E: C/D map of a 32x32 MFMA tile: col (problem) = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+        float pv[16];             // the tile's costs (GRAD) or curvature (HV): unconditional loads, all in flight at once
+        if (MODE != 2) {
+            const float* panel = MODE == 0 ? a.sT : a.D;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = row0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const float v = panel[(size_t)min(row, c_end - 1) * Ppad + prob];
+                pv[r] = row < c_end ? v : 0.f;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rl = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h, row = row0 + rl;
+            const bool valid = row < c_end;
+            const size_t at = (size_t)row * Ppad + prob;
+            const float zz = acc[r] + vb;
+            if (MODE == 2) {
+                if (valid && prob < a.pout) a.out[(size_t)row * a.ldo + prob] = zz;
+            } else {
+                float R = 0.f;
+                if (MODE == 0) {
+                    const float s = pv[r];
+                    float Dv = 0.f;
+                    if (s != 0.f) {                       // (a NaN cost is != 0: it ends the problem through the sums)
+                        const float c = fabsf(s), y = s > 0.f ? 1.f : -1.f;
+                        const float m = y * zz;
+                        const float e = expf(-fabsf(m));                  // in (0, 1]: nothing overflows whatever |m|
+                        const float big = 1.f / (1.f + e), small = e / (1.f + e);
+                        const float sig_neg = m >= 0.f ? small : big;    // sigma(-m)
+                        lsum += c * (fmaxf(-m, 0.f) + log1pf(e));
+                        Dv = c * big * small;
+                        R = -c * y * sig_neg;
+                    }
+                    if (valid) { a.z[at] = zz; a.D[at] = Dv; }
+                } else {
+                    const float Dv = pv[r];
+                    R = Dv != 0.f ? Dv * zz : 0.f;
+                }
+                s_R[rl * kTP + l31] = R;
+                bsum += R;
+            }
+        }
+        if (MODE == 2) continue;
+        __syncthreads();
+
+        // ---- B: g[d][p] += sum over the tile's rows of X[row][d] R[row][p]; one MFMA step takes rows 2 i (lanes 0..31) and 2 i + 1
+        // (lanes 32..63); MFMA tile t = blk VW + e of this wave holds dims d0 + blk 32 VW + VW j + e, j = 0..31 (a lane loads VW
+        // consecutive floats of its row)
+        const int d0 = wave * 32 * DT;
+        const int steps = min(kTR, c_end - row0 + 1) >> 1;
+        constexpr int U = DT >= 8 ? 4 : 8;        // row pairs whose loads are in flight at once (every load is unconditional: a
+                                                  // lane outside the matrix reads x[0] and drops it)
+        for (int i0 = 0; i0 < steps; i0 += U) {
+            float xv[U][DT], bval[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int k = 2 * (i0 + u) + h, row = row0 + k;      // (k <= 127: U divides 64)
+                bval[u] = s_R[k * kTP + l31];
+#pragma unroll
+                for (int blk = 0; blk < DT / VW; ++blk) {
+                    const int d = d0 + blk * 32 * VW + VW * l31;
+                    const bool ok = row < c_end && d < dim;
+                    const float* src = ok ? a.x + (size_t)row * dim + d : a.x;
+                    float t[4] = {0.f, 0.f, 0.f, 0.f};
+                    if (VW == 4) { const float4 v = *reinterpret_cast<const float4*>(src); t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w; }
+                    else if (VW == 2) { const float2 v = *reinterpret_cast<const float2*>(src); t[0] = v.x; t[1] = v.y; }
+                    else t[0] = *src;
+#pragma unroll
+                    for (int e = 0; e < VW; ++e) xv[u][blk * VW + e] = ok ? t[e] : 0.f;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);      // (keeps the scheduler from sinking every load to its first use)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int t = 0; t < DT; ++t) g[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[u][t], bval[u], g[t], 0, 0, 0);
+        }
+        __syncthreads();          // (s_R is rewritten by the next tile's epilogue)
+    }
+    if (MODE == 2) return;
+
+    // ---- the part's partial: rows d < dim from the accumulators, row dim (the bias) and the loss from the lanes' sums, added in
+    // a fixed order (wave 0..3, half 0..1)
+    float* gp = a.gp + (size_t)part * a.LD * Ppad;
+    const int d0 = wave * 32 * DT;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+        const int blk = t / VW, e = t % VW;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int d = d0 + blk * 32 * VW + VW * j + e;
+            if (d < dim) gp[(size_t)d * Ppad + prob] = g[t][r];
+        }
+    }
+    s_red[0][wave * 2 + h][l31] = bsum;
+    s_red[1][wave * 2 + h][l31] = lsum;
+    __syncthreads();
+    if (tid < kTP) {
+        float b = 0.f, l = 0.f;
+        for (int q = 0; q < 8; ++q) { b += s_red[0][q][tid]; l += s_red[1][q][tid]; }
+        gp[(size_t)dim * Ppad + p0 + tid] = b;
+        if (MODE == 0) a.lp[(size_t)part * Ppad + p0 + tid] = l;
+    }
+}
+
+// sT (N, Ppad) <- s (P, N): a 32 x 32 tile through LDS; problems >= P get cost 0
+__global__ __launch_bounds__(256) void probe_costs_kernel(const float* __restrict__ s, int P, int N, int Ppad, float* __restrict__ sT)
+{
+    __shared__ float t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long long r0 = (long long)blockIdx.x * 32; const int p0 = blockIdx.y * 32;
+    for (int j = ty; j < 32; j += 8) {
+        const int p = p0 + j; const long long row = r0 + tx;
+        t[j][tx] = (p < P && row < N) ? s[(size_t)p * N + row] : 0.f;
+    }
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8) {
+        const long long row = r0 + j;
+        if (row < N) sT[(size_t)row * Ppad + p0 + tx] = t[tx][j];
+    }
+}
+
+// state of a fit: every vector 0, problems >= P frozen from the start
+__global__ void probe_init_kernel(int* __restrict__ is, int P, int Ppad)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= Ppad) return;
+    for (int i = 0; i < 8; ++i) is[(size_t)p * 8 + i] = 0;
+    is[(size_t)p * 8 + I_FROZEN] = p < P ? 0 : 1;
+    is[(size_t)p * 8 + I_ALIVE] = p < P ? 1 : 0;
+}
+
+// (P, dim + 1) -> (Ppad, LD), rows >= P and the padding columns zero
+__global__ void probe_pack_kernel(const float* __restrict__ w, int P, int dim, int LD, int Ppad, float* __restrict__ W)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)Ppad * LD) return;
+    const int p = (int)(i / LD), d = (int)(i % LD);
+    W[i] = (p < P && d <= dim) ? w[(size_t)p * (dim + 1) + d] : 0.f;
+}
+
+__global__ void probe_finish_kernel(ProbeWs b, float* __restrict__ w, float* __restrict__ stats)
+{
+    const int p = blockIdx.x;
+    for (int d = threadIdx.x; d <= b.dim; d += 256) w[(size_t)p * (b.dim + 1) + d] = b.W[(size_t)p * b.LD + d];
+    if (stats && threadIdx.x == 0) {
+        stats[4 * p + 0] = b.fs[(size_t)p * 8 + F_F];
+        stats[4 * p + 1] = b.fs[(size_t)p * 8 + F_GNORM];
+        stats[4 * p + 2] = (float)b.is[(size_t)p * 8 + I_ITER];
+        stats[4 * p + 3] = (float)b.is[(size_t)p * 8 + I_STATUS];
+    }
+}
+
+// the sum of one double per thread over the 256 threads, as a fixed binary tree; every thread gets it
+__device__ __forceinline__ double block_sum(double v, double* s)
+{
+    const int tid = threadIdx.x;
+    s[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s[tid] += s[tid + o];
+        __syncthreads();
+    }
+    const double r = s[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
+
+constexpr int kVecPer = 5;      // (1024 + 1 + 255) / 256 elements of a vector per thread
+
+// partial of the last pass for element d of problem p, the parts added in part order
+__device__ __forceinline__ float merge_parts(const ProbeWs& b, int p, int d)
+{
+    float s = 0.f;
+#pragma unroll 8
+    for (int q = 0; q < b.parts; ++q) s += b.gp[((size_t)q * b.LD + d) * b.Ppad + p];
+    return s;
+}
+
+// PHASE 0: after a GRAD pass -- f, g, the stop rule, else the start of CG.  PHASE 1: after the k-th HV pass -- one CG iteration.
+// PHASE 2: after trial round k -- the Armijo test of its step lengths.
+template <int PHASE>
+__global__ __launch_bounds__(256) void probe_vec_kernel(ProbeWs b, int k, int max_newton, int max_cg, float tol, ProbeAlphas al)
+{
+    __shared__ double s_sum[256];
+    __shared__ float s_alpha;
+    const int p = blockIdx.x, tid = threadIdx.x, n = b.dim + 1;
+    int* is = b.is + (size_t)p * 8;
+    float* fs = b.fs + (size_t)p * 8;
+    double* ds = b.ds + (size_t)p * 8;
+    float* W = b.W + (size_t)p * b.LD;
+    float* G = b.G + (size_t)p * b.LD;
+    float* Dv = b.Dv + (size_t)p * b.LD;
+    float* Rv = b.Rv + (size_t)p * b.LD;
+    float* Pv = b.Pv + (size_t)p * b.LD;
+
+    if (PHASE == 0) {
+        if (is[I_FROZEN]) return;
+        double ww = 0.0, gg = 0.0;
+        for (int d = tid; d < n; d += 256) {
+            const float w = W[d], gv = w + merge_parts(b, p, d);
+            G[d] = gv;
+            ww += (double)w * w; gg += (double)gv * gv;
+        }
+        ww = block_sum(ww, s_sum); gg = block_sum(gg, s_sum);
+        float loss = 0.f;
+        for (int q = 0; q < b.parts; ++q) loss += b.lp[(size_t)q * b.Ppad + p];
+        const int it = is[I_ITER];
+        const float f = (float)(0.5 * ww) + loss, gnorm = (float)sqrt(gg);
+        const float g0 = it == 0 ? gnorm : fs[F_G0];
+        int status = -1;
+        if (!(f - f == 0.f) || !(gnorm - gnorm == 0.f)) status = 2;
+        else if (gnorm <= tol * g0) status = 0;
+        else if (it >= max_newton) status = 1;
+        if (status < 0)
+            for (int d = tid; d < n; d += 256) { const float gv = G[d]; Pv[d] = 0.f; Rv[d] = -gv; Dv[d] = -gv; }
+        if (tid == 0) {
+            fs[F_F] = f; fs[F_GNORM] = gnorm; fs[F_G0] = g0;
+            if (status >= 0) { is[I_STATUS] = status; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            else { ds[D_RR] = gg; is[I_CG] = 1; }
+        }
+    } else if (PHASE == 1) {
+        if (!is[I_CG]) return;
+        float hd[kVecPer];
+        double dhd = 0.0;
+#pragma unroll
+        for (int j = 0; j < kVecPer; ++j) {
+            const int d = tid + 256 * j;
+            hd[j] = 0.f;
+            if (d < n) { const float dv = Dv[d]; hd[j] = dv + merge_parts(b, p, d); dhd += (double)dv * hd[j]; }
+        }
+        dhd = block_sum(dhd, s_sum);
+        const double rr = ds[D_RR];
+        const bool ok = finite_d(dhd) && dhd > 0.0;
+        const float alpha = ok ? (float)(rr / dhd) : 0.f;
+        double rrn = 0.0;
+#pragma unroll
+        for (int j = 0; j < kVecPer; ++j) {
+            const int d = tid + 256 * j;
+            if (d < n && ok) {
+                Pv[d] = fmaf(alpha, Dv[d], Pv[d]);
+                const float r = fmaf(-alpha, hd[j], Rv[d]);
+                Rv[d] = r; rrn += (double)r * r;
+            }
+        }
+        rrn = block_sum(rrn, s_sum);
+        const double gnorm = fs[F_GNORM];
+        const bool stop = !ok || !finite_d(rrn) || sqrt(rrn) <= 0.1 * gnorm || k + 1 >= max_cg;
+        if (!stop) {
+            const float beta = (float)(rrn / rr);
+#pragma unroll
+            for (int j = 0; j < kVecPer; ++j) {
+                const int d = tid + 256 * j;
+                if (d < n) Dv[d] = fmaf(beta, Dv[d], Rv[d]);
+            }
+            if (tid == 0) ds[D_RR] = rrn;
+            return;
+        }
+        // the step is Pv: what the Armijo test needs of it
+        double gtp = 0.0, wtp = 0.0, pp = 0.0;
+        for (int d = tid; d < n; d += 256) { const double pv = Pv[d]; gtp += (double)G[d] * pv; wtp += (double)W[d] * pv; pp += pv * pv; }
+        gtp = block_sum(gtp, s_sum); wtp = block_sum(wtp, s_sum); pp = block_sum(pp, s_sum);
+        if (tid == 0) {
+            is[I_CG] = 0;
+            if (!finite_d(dhd) || !finite_d(rrn) || !finite_d(gtp) || !finite_d(pp)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            else { ds[D_GTP] = gtp; ds[D_WTP] = wtp; ds[D_PP] = pp; is[I_LS] = 1; }
+        }
+    } else {
+        if (!is[I_LS]) return;
+        if (tid == 0) {
+            // trial slot j of round k: its loss sum, the parts added in part order; slot 0 of round 0 is the step length 0
+            float take = -1.f; bool bad = false;
+            for (int j = 0; j < al.n && take < 0.f && !bad; ++j) {
+                double L = 0.0;
+                for (int q = 0; q < b.parts; ++q) L += b.tp[((size_t)q * kNA + j) * b.Ppad + p];
+                if (k == 0 && j == 0) { ds[D_PHI0] = L; if (!finite_d(L)) bad = true; continue; }
+                if (!finite_d(L)) { bad = true; break; }
+                const double a = al.a[j];
+                const double lhs = (L - ds[D_PHI0]) + (a * ds[D_WTP] + 0.5 * a * a * ds[D_PP]);
+                if (lhs <= 1e-4 * a * ds[D_GTP]) take = al.a[j];
+            }
+            if (bad || (take < 0.f && al.last)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; is[I_LS] = 0; }
+            else if (take >= 0.f) { is[I_LS] = 0; is[I_ITER] += 1; }
+            s_alpha = bad ? -1.f : take;
+        }
+        __syncthreads();
+        const float a = s_alpha;
+        if (a > 0.f)
+            for (int d = tid; d < n; d += 256) W[d] = fmaf(a, Pv[d], W[d]);
+    }
+}
+
+struct ProbeTrialArgs {
+    const float* sT; const float* z; const float* u;      // (N, Ppad)
+    double* tp;                                            // (parts, kNA, Ppad)
+    const int* flags;
+    int N, Ppad, parts, chunk;
+    ProbeAlphas al;
+};
+
+// sum over the part's rows of |s| softplus(-sgn(s) (z + alpha u)) for every step length of the round, in double: thread (rg, pl)
+// adds rows rg, rg + 8, .. of problem p0 + pl in row order, then the 8 row groups are added in order
+__global__ __launch_bounds__(256) void probe_trial_kernel(ProbeTrialArgs a)
+{
+    __shared__ double s_red[kNA][8][kTP];
+    const int tid = threadIdx.x, pl = tid & 31, rg = tid >> 5;
+    const int part = blockIdx.x % a.parts, p0 = (blockIdx.x / a.parts) * kTP, prob = p0 + pl;
+    const int active = a.flags[(size_t)prob * 8 + I_LS];
+    if (!__syncthreads_or(active)) return;
+    const long long c_begin = (long long)part * a.chunk;
+    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    double acc[kNA];
+#pragma unroll
+    for (int j = 0; j < kNA; ++j) acc[j] = 0.0;
+    if (active)
+        for (int row = (int)c_begin + rg; row < c_end; row += 8) {
+            const size_t at = (size_t)row * a.Ppad + prob;
+            const float s = a.sT[at];
+            if (s == 0.f) continue;
+            const double c = fabsf(s), y = s > 0.f ? 1.0 : -1.0, z = a.z[at], u = a.u[at];
+#pragma unroll
+            for (int j = 0; j < kNA; ++j) {
+                if (j >= a.al.n) break;
+                const double t = -y * (z + (double)a.al.a[j] * u);
+                acc[j] += c * (fmax(t, 0.0) + log1p(exp(-fabs(t))));
+            }
+        }
+#pragma unroll
+    for (int j = 0; j < kNA; ++j) s_red[j][rg][pl] = acc[j];
+    __syncthreads();
+    if (rg == 0 && active)
+        for (int j = 0; j < a.al.n; ++j) {
+            double t = 0.0;
+            for (int q = 0; q < 8; ++q) t += s_red[j][q][pl];
+            a.tp[((size_t)part * kNA + j) * a.Ppad + prob] = t;
+        }
+}
+
+int pick_dt(int dim) { return dim <= 128 ? 1 : dim <= 256 ? 2 : dim <= 512 ? 4 : 8; }
+
+}  // namespace
+
+// The launch shape, from the problem shape alone.  Problems go in tiles of 32 (one MFMA tile wide).  The rows are cut into parts of
+// `chunk` rows, a multiple of the 128-row tile: enough parts for one workgroup per CU on 256 CUs per problem tile, at most
+// kProbeMaxParts (the per-problem kernel adds the parts' partials one after the other).  The part count must NOT depend on P (a
+// problem's bits may not), so few problem tiles mean few workgroups.  Both figures are a first guess: scripts/probe_bench.py has run
+// with these values and no other.  chunk_opt > 0 (option probe_chunk, a test aid) caps the rows of a part instead; it
+// is raised where it would give more parts than that.
+ProbePlan probe_plan(int N, int P, int dim, int chunk_opt)
+{
+    ProbePlan p{};
+    p.ptiles = (P + kProbeTile - 1) / kProbeTile;
+    p.Ppad = p.ptiles * kProbeTile;
+    p.LD = dim + 4;
+    long long chunk;
+    if (chunk_opt > 0) chunk = chunk_opt;
+    else {
+        const long long tiles = ((long long)N + kTR - 1) / kTR;
+        const long long want = std::max<long long>(1, std::min<long long>(tiles, 256));
+        chunk = ((tiles + want - 1) / want) * kTR;
+    }
+    if (((long long)N + chunk - 1) / chunk > kProbeMaxParts) chunk = ((((long long)N + kProbeMaxParts - 1) / kProbeMaxParts + kTR - 1) / kTR) * kTR;
+    p.chunk = (int)std::min<long long>(chunk, 0x7fffff80);
+    p.parts = (int)(((long long)N + p.chunk - 1) / p.chunk);
+    return p;
+}
+
+hipError_t probe_prepare(hipStream_t st, const ProbeWs& b, const float* s, int P)
+{
+    hipError_t e = hipMemsetAsync(b.W, 0, (size_t)5 * b.Ppad * b.LD * sizeof(float), st);      // W, G, Dv, Rv, Pv are one run
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(b.fs, 0, (size_t)b.Ppad * 8 * sizeof(float), st);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(b.ds, 0, (size_t)b.Ppad * 8 * sizeof(double), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(probe_init_kernel, dim3((unsigned)((b.Ppad + 255) / 256)), dim3(256), 0, st, b.is, P, b.Ppad);
+    const dim3 grid((unsigned)(((long long)b.N + 31) / 32), (unsigned)(b.Ppad / 32));
+    hipLaunchKernelGGL(probe_costs_kernel, grid, dim3(256), 0, st, s, P, b.N, b.Ppad, b.sT);
+    return hipGetLastError();
+}
+
+hipError_t probe_pass(hipStream_t st, const ProbeWs& b, const float* x, int mode)
+{
+    ProbePassArgs a{};
+    a.x = x; a.sT = b.sT; a.z = b.z; a.D = b.D; a.gp = b.gp; a.lp = b.lp; a.flags = b.is;
+    a.N = b.N; a.dim = b.dim; a.LD = b.LD; a.Ppad = b.Ppad; a.parts = b.parts; a.chunk = b.chunk;
+    const dim3 grid((unsigned)(b.parts * (b.Ppad / kTP)));
+    auto launch = [&](auto dt) {
+        constexpr int DT = decltype(dt)::value;
+        if (mode == 0) { a.v = b.W; a.flag = I_ALIVE; hipLaunchKernelGGL((probe_pass_kernel<0, DT>), grid, dim3(256), 0, st, a); }
+        else { a.v = b.Dv; a.flag = I_CG; hipLaunchKernelGGL((probe_pass_kernel<1, DT>), grid, dim3(256), 0, st, a); }
+    };
+    if (mode == 2) {
+        a.v = b.Pv; a.flag = I_LS; a.out = b.u; a.ldo = b.Ppad; a.pout = b.Ppad;
+        hipLaunchKernelGGL((probe_pass_kernel<2, 1>), grid, dim3(256), 0, st, a);
+    } else switch (pick_dt(b.dim)) {
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        case 4: launch(std::integral_constant<int, 4>{}); break;
+        default: launch(std::integral_constant<int, 8>{}); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t probe_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_cg, float tol, const ProbeAlphas& al)
+{
+    const dim3 grid((unsigned)P);
+    if (phase == 0) hipLaunchKernelGGL(probe_vec_kernel<0>, grid, dim3(256), 0, st, b, k, max_newton, max_cg, tol, al);
+    else if (phase == 1) hipLaunchKernelGGL(probe_vec_kernel<1>, grid, dim3(256), 0, st, b, k, max_newton, max_cg, tol, al);
+    else hipLaunchKernelGGL(probe_vec_kernel<2>, grid, dim3(256), 0, st, b, k, max_newton, max_cg, tol, al);
+    return hipGetLastError();
+}
+
+hipError_t probe_trial(hipStream_t st, const ProbeWs& b, const ProbeAlphas& al)
+{
+    ProbeTrialArgs a{};
+    a.sT = b.sT; a.z = b.z; a.u = b.u; a.tp = b.tp; a.flags = b.is; a.N = b.N; a.Ppad = b.Ppad; a.parts = b.parts; a.chunk = b.chunk; a.al = al;
+    hipLaunchKernelGGL(probe_trial_kernel, dim3((unsigned)(b.parts * (b.Ppad / kTP))), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t probe_finish(hipStream_t st, const ProbeWs& b, int P, float* w, float* stats)
+{
+    hipLaunchKernelGGL(probe_finish_kernel, dim3((unsigned)P), dim3(256), 0, st, b, w, stats);
+    return hipGetLastError();
+}
+
+// out (n, P) = x~ w^T: w packed into W (Ppad, LD) first, then the PANEL pass
+hipError_t probe_decision(hipStream_t st, const ProbePlan& p, const float* x, int n, int dim, const float* w, int P, float* W, float* out)
+{
+    const size_t tot = (size_t)p.Ppad * p.LD;
+    hipLaunchKernelGGL(probe_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, w, P, dim, p.LD, p.Ppad, W);
+    ProbePassArgs a{};
+    a.x = x; a.v = W; a.out = out; a.ldo = P; a.pout = P; a.flags = nullptr;
+    a.N = n; a.dim = dim; a.LD = p.LD; a.Ppad = p.Ppad; a.parts = p.parts; a.chunk = p.chunk;
+    hipLaunchKernelGGL((probe_pass_kernel<2, 1>), dim3((unsigned)(p.parts * p.ptiles)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace avae

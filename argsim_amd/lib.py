@@ -61,6 +61,10 @@ class AvaeAggConfig(C.Structure):
     _fields_ = [('self_base', C.c_int64), ('reserved', C.c_int32 * 2)]
 
 
+class AvaeProbeConfig(C.Structure):
+    _fields_ = [('max_newton', C.c_int32), ('max_cg', C.c_int32), ('tol', C.c_float), ('reserved', C.c_int32)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -97,6 +101,8 @@ SIGNATURES = {
     'avae_knn': (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_int32, C.POINTER(AvaeKnnConfig), _P, _P]),
     'avae_agg_logq': (C.c_int, [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeAggConfig), _P, _P]),
     'avae_latent_moments': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P]),
+    'avae_probe_fit': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(AvaeProbeConfig), _P, _P]),
+    'avae_probe_decision': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),

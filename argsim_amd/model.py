@@ -15,6 +15,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) teacher-forced log p(tgt | z)                -> VAE.score_z(z, tgt)
     (new) nearest neighbours among latent rows         -> VAE.neighbors(queries, bank, k, metric) / neighbors(vae, ...)
     (new) aggregate-posterior diagnostics (MI, AU)     -> VAE.posterior_stats(src) / VAE.log_q(z, mu, lv) / VAE.latent_moments(mu, lv)
+    (new) linear probes of latent rows (liblinear CV)  -> VAE.probe_fit(z, labels) / VAE.probe_cv(z, labels, folds, groups)
 """
 import ctypes as C
 
@@ -582,6 +583,21 @@ class VAE:
                        mu=mu.cpu().numpy(), lv=lv.cpu().numpy())
         return res
 
+    def probe_fit(self, z, labels, C=0.001, class_weight='balanced', train=None, **solver):
+        """a one-vs-rest L2 logistic regression on the rows `train` (all rows: None) of z (N, dim), the model of scikit-learn's
+        LogisticRegression(C, solver='liblinear', class_weight) fitted on the device (include/argsim_vae.h, avae_probe_fit) -> an
+        object with classes_, coef_, intercept_, stats, decision(z) and predict(z) (argsim_amd/probe.py).  solver: tol, max_newton,
+        max_cg."""
+        from . import probe
+        return probe.fit(self, z, labels, C, class_weight, train, **solver)
+
+    def probe_cv(self, z, labels, folds, groups=None, C=0.001, class_weight='balanced', **solver):
+        """cross-validation of that model: every group x fold x class is one problem of ONE avae_probe_fit over the shared z -> dict
+        with pred (N,) the held-out predictions, scores {group: mean micro-F1 over its folds} and mean, the figures the reference's
+        src/eval_classification.py prints, and stats (P, 4) of the problems (argsim_amd/probe.py, cross_validate)."""
+        from . import probe
+        return probe.cross_validate(self, z, labels, folds, groups, C, class_weight, **solver)
+
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
 
@@ -763,3 +779,13 @@ def log_q(vae, z, mu, lv, self_index=None):
 def posterior_stats(vae, src, samples=1, seed=0, eps=None, batch=128, au_threshold=0.01, return_parts=False):
     """active units, mutual information and marginal KL over the sentences of src: VAE.posterior_stats"""
     return vae.posterior_stats(src, samples, seed, eps, batch, au_threshold, return_parts)
+
+
+def probe_fit(vae, z, labels, C=0.001, class_weight='balanced', train=None, **solver):
+    """functional form of VAE.probe_fit"""
+    return vae.probe_fit(z, labels, C, class_weight, train, **solver)
+
+
+def probe_cv(vae, z, labels, folds, groups=None, C=0.001, class_weight='balanced', **solver):
+    """functional form of VAE.probe_cv"""
+    return vae.probe_cv(z, labels, folds, groups, C, class_weight, **solver)

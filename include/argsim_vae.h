@@ -362,6 +362,47 @@ int  avae_agg_logq(avae_handle h, const float* z, int32_t n, const float* mu, co
                    const avae_agg_config* ac, float* logq /* (n) */, float* logqx /* (n), optional; needs self_base >= 0 */);
 int  avae_latent_moments(avae_handle h, const float* mu, const float* lv, int32_t N, int32_t dim, float* out /* (4, dim) */);
 
+/* ---- linear probes of latent rows ---------------------------------------------------------- */
+/* Whether a code is linearly useful: P independent L2-regularised logistic regressions over ONE matrix of latent rows, fitted in
+ * lockstep on the device -- a cross-validation over topics x folds x classes is one call.  x (N, dim), s (P, N), w (P, dim + 1),
+ * stats (P, 4) and out (n, P) are row-major float32 device arrays; x and w are 16-byte aligned; dim is a multiple of 4 in
+ * [4, 1024] and independent of the handle's dim_rep; 1 <= N <= 2^31 - 256, 1 <= P <= 2^20.
+ *   objective  problem p minimises f_p(w) = 1/2 |w|^2 + sum_i |s_pi| softplus(-sgn(s_pi) w . x~_i), x~_i = (x_i, 1): the SIGN of
+ *              s_pi is the label of row i in problem p, its MAGNITUDE the row's cost, and a cost of 0 leaves the row out of the
+ *              problem (a held-out fold, another topic's row): it contributes exactly nothing.  The last component of w is the
+ *              bias; it is penalised like the rest (liblinear with intercept_scaling = 1).  f_p is strongly convex with modulus 1:
+ *              one optimum w*, and any w carries the certificate |w - w*| <= |grad f_p(w)|.  softplus and the sigmoid are
+ *              evaluated from exp(-|margin|): nothing overflows whatever the margin.
+ *   method     truncated Newton from w = 0.  The Newton system H v = v + X~^T (D o (X~ v)), D_i = |s_i| sigma(m_i) sigma(-m_i), is
+ *              solved by conjugate gradients from 0 until |r| <= 0.1 |g| or max_cg iterations; the step p is taken with the first
+ *              alpha in 1, 1/2, .. 2^-20 for which f(w + alpha p) <= f(w) + 1e-4 alpha g . p.  Both sides of that test come from
+ *              the kept panels X~ w and X~ p (x is not read again) and are summed in double.  Every loop is bounded.
+ *   stop       a problem stops at the first Newton iteration where |grad f_p(w)| <= tol |grad f_p(0)| and is frozen from then on,
+ *              whatever its companions still do.  A problem whose costs are all 0 returns w = 0 exactly after 0 iterations.
+ *   stats      stats[p] = f_p(w), |grad f_p(w)| as the device evaluated it at the returned w, the Newton iterations taken, and a
+ *              status: 0 converged, 1 max_newton reached, 2 the line search was exhausted or a value that is not finite was met.
+ *              Inputs are NOT checked for finiteness: such a value ends the affected problem with status 2, never a hang.
+ *   bits       w[p] and stats[p] depend on x, on row p of s, on the config and on option probe_chunk alone -- not on P, on p or on
+ *              the other problems of the call.  No float atomics, fixed-order reductions: the same arguments give the same bits.
+ *   launches   per Newton iteration 11 + 2 max_cg, whatever the problems need (those of a tile of 32 problems that has finished a
+ *              phase return at once), and ONE stream synchronisation, after the gradient, to learn whether every problem is
+ *              frozen; what a problem does next is decided on the device, so the result does not depend on when the host looks.
+ *   workspace  4 (4 N Pp + 5 Pp (dim + 4) + parts (dim + 5) Pp) + 56 parts Pp + 128 Pp bytes, Pp = P rounded up to 32, parts <= 256
+ *              (DESIGN.md 4.3h), reserved once per call.
+ * avae_probe_decision: out[i, p] = w_p . x~_i in fp32 (dot product order of avae_knn, then the bias).  Enqueued only; nothing is
+ * synchronised.
+ * Errors (text through avae_last_error): a null pc, x, s, w or out; N, n or P < 1; N or n > 2^31 - 256; P > 2^20; max_newton < 1, max_cg < 1;
+ * a tol that is negative or NaN; reserved != 0; dim not a multiple of 4 in [4, 1024]; x or w not 16-byte aligned; a workspace the
+ * device cannot give (the text names its size).
+ * Option probe_chunk (avae_set_option; a test aid): caps the rows of a part, so that small tests run several parts and the merge;
+ * 0 lets the planner decide.  A cap that would give more than 256 parts is raised.  Another probe_chunk sums in another order. */
+typedef struct avae_probe_config { int32_t max_newton; int32_t max_cg; float tol; int32_t reserved; } avae_probe_config;
+int  avae_probe_fit(avae_handle h, const float* x /* (N, dim) */, int32_t N, int32_t dim,
+                    const float* s /* (P, N) signed costs */, int32_t P, const avae_probe_config* pc,
+                    float* w /* (P, dim + 1) out */, float* stats /* (P, 4) optional */);
+int  avae_probe_decision(avae_handle h, const float* x /* (n, dim) */, int32_t n, int32_t dim,
+                         const float* w /* (P, dim + 1) */, int32_t P, float* out /* (n, P) */);
+
 #ifdef __cplusplus
 }
 #endif
