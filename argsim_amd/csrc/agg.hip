@@ -15,6 +15,7 @@
 //              exp(lv), mean KL.  Row blocks sum in double, a second small kernel adds the blocks in block order.
 // No float atomics; every sum has a fixed order: the same arguments and options give the same bits.
 #include "kernels.h"
+#include "mfma_tile.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,13 +24,11 @@ namespace avae {
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kTQ = 128;           // query rows per tile: 16 thread rows x 8
 constexpr int kTB = 64;            // bank rows per tile: 16 thread columns x 4
 constexpr int kQPT = kTQ / 16, kBPT = kTB / 16;
 constexpr int kDC = 32;            // dims per LDS chunk
-constexpr int kLD = kDC + 4;       // LDS row stride (floats): conflict-free b128 reads along dim (gemm_f32.hip)
+constexpr int kLD = kDC + 4;       // LDS row stride (floats): conflict-free b128 reads along dim (as kTileLDK, mfma_tile.h)
 constexpr int kAggMaxParts = 1024;
 
 struct AggTileArgs {

@@ -35,13 +35,12 @@
 //     that set goes beside logp into a time-major scratch.
 // The greedy instantiation's device code is the parent's instruction for instruction (one kernel-argument offset moved).
 #include "kernels.h"
+#include "mfma_tile.h"
 #include "sample_dev.h"
 
 namespace avae {
 
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float sigm(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 __device__ __forceinline__ float tanh_(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }

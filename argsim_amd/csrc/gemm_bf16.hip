@@ -12,19 +12,9 @@
 // converted, so the GEMM never needs a transposing LDS access.
 #include <algorithm>
 #include "kernels.h"
+#include "mfma_tile.h"
 
 namespace avae {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 // ---------------------------------------------------------------- fp32 [rows][cols] -> bf16 [rows][ldd]
 // ldd = cols rounded up to 8; the pad columns are written as zeros.  One thread = 8 output elements.
@@ -183,13 +173,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(GemmBf16Args g)
     if (g.dyn_kind == 1) M = min(M, *g.dyn);
     if (g.dyn_kind == 2) K = min(K, *g.dyn);
     const int tiles_n = (g.N + 127) / 128;
-    int bid = blockIdx.x;
-    {
-        const int nblk = ((M + 127) / 128) * tiles_n;       // effective tiles (device-side row count), <= gridDim.x
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-        if (slot >= q + (xcd < r ? 1 : 0)) return;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int bid = xcd_tile(blockIdx.x, ((M + 127) / 128) * tiles_n);      // effective tiles (device-side row count), <= gridDim.x
+    if (bid < 0) return;
     const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
     const int m0 = tm * 128, n0 = tn * 128;
     if (m0 >= M) return;
@@ -200,12 +185,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(GemmBf16Args g)
         if (kb >= ke) return;
     }
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     uint4 ra[4], rb[4];
     load_panel(ra, g.A, g.lda, m0, M, kb, ke, tid);
@@ -236,25 +216,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(GemmBf16Args g)
     }
     const bool atomic = g.split_k > 1;
     const bool add_bias = g.bias != nullptr && (!atomic || blockIdx.z == 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int col = n0 + 64 * wn + 32 * j + l31;
-        if (col >= g.N) continue;
-        float bv = add_bias ? g.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row >= M) continue;
-                float v = g.alpha * acc[i][j][r] + bv;
-                float* c = g.C + (size_t)row * g.ldc + col;
-                if (atomic) atomicAdd(c, v);
-                else if (g.accumulate) *c += v;
-                else *c = v;
-            }
-        }
-    }
+    epilogue_generic(acc, g.C, g.ldc, M, g.N, m0 + 64 * wm, n0 + 64 * wn, h, l31, g.alpha, add_bias ? g.bias : nullptr,
+                     atomic ? kEpiAtomic : (g.accumulate ? kEpiAccumulate : kEpiStore));
 }
 
 // ---------------------------------------------------------------- the large-tile form
@@ -307,13 +270,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt256_kernel(GemmBf16Args g)
     if (g.dyn_kind == 1) M = min(M, *g.dyn);
     if (g.dyn_kind == 2) K = min(K, *g.dyn);
     const int tiles_n = (g.N + T2 - 1) / T2;
-    int bid = blockIdx.x;
-    {
-        const int nblk = ((M + T2 - 1) / T2) * tiles_n;     // effective tiles (device-side row count), <= gridDim.x
-        const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-        if (slot >= q + (xcd < r ? 1 : 0)) return;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int bid = xcd_tile(blockIdx.x, ((M + T2 - 1) / T2) * tiles_n);    // effective tiles (device-side row count), <= gridDim.x
+    if (bid < 0) return;
     const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
     const int m0 = tm * T2, n0 = tn * T2;
     if (m0 >= M) return;
@@ -324,12 +282,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt256_kernel(GemmBf16Args g)
         if (kb >= ke) return;
     }
     f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     uint4 ra[4], rb[4];
     load_panel256(ra, g.A, g.lda, m0, M, kb, ke, tid);
@@ -372,8 +325,8 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt256_kernel(GemmBf16Args g)
     const bool add_bias = g.bias != nullptr && (!atomic || blockIdx.z == 0);
     if (m0 + T2 <= M && n0 + T2 <= g.N && !atomic) {
         // a tile wholly inside the matrix: straight-line stores, one address computation per 32x32 tile (the per-element
-        // form below -- row predicate, three-way mode branch -- is ~40 instructions x 128 elements per lane: longer than the
-        // K = 512 main loop, and with one workgroup per CU nothing runs beside it)
+        // form, epilogue_generic -- row predicate, three-way mode branch -- is ~40 instructions x 128 elements per lane: longer
+        // than the K = 512 main loop, and with one workgroup per CU nothing runs beside it)
         const size_t ldc = (size_t)g.ldc;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -384,34 +337,17 @@ __global__ __launch_bounds__(512) void gemm_bf16_nt256_kernel(GemmBf16Args g)
                 float* c0 = g.C + (size_t)(m0 + 128 * wm + 32 * i + 4 * h) * ldc + col;
                 if (g.accumulate) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) { float* c = c0 + (size_t)((r & 3) + 8 * (r >> 2)) * ldc; *c += g.alpha * acc[i][j][r] + bv; }
+                    for (int r = 0; r < 16; ++r) { float* c = c0 + (size_t)mfma32_row(r, 0) * ldc; *c += g.alpha * acc[i][j][r] + bv; }
                 } else {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) c0[(size_t)((r & 3) + 8 * (r >> 2)) * ldc] = g.alpha * acc[i][j][r] + bv;
+                    for (int r = 0; r < 16; ++r) c0[(size_t)mfma32_row(r, 0) * ldc] = g.alpha * acc[i][j][r] + bv;
                 }
             }
         }
         return;
     }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + 64 * wn + 32 * j + l31;
-        if (col >= g.N) continue;
-        const float bv = add_bias ? g.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 128 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row >= M) continue;
-                const float v = g.alpha * acc[i][j][r] + bv;
-                float* c = g.C + (size_t)row * g.ldc + col;
-                if (atomic) atomicAdd(c, v);
-                else if (g.accumulate) *c += v;
-                else *c = v;
-            }
-        }
-    }
+    epilogue_generic(acc, g.C, g.ldc, M, g.N, m0 + 128 * wm, n0 + 64 * wn, h, l31, g.alpha, add_bias ? g.bias : nullptr,
+                     atomic ? kEpiAtomic : (g.accumulate ? kEpiAccumulate : kEpiStore));
 }
 
 // ---------------------------------------------------------------- the TN form: both operands stored [k][x]
@@ -478,12 +414,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn256_kernel(GemmBf16Args g)
         if (kb >= ke) return;                       // (uniform over the workgroup: EXEC stays full for the transposing reads)
     }
     f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // this lane's place in the 4 x 16 blocks of a transposing read: group gq = lane / 16 -> k half (gq >> 1) and x half (gq & 1)
     const int gq = lane >> 4, li = lane & 15;
@@ -524,25 +455,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn256_kernel(GemmBf16Args g)
         }
         __syncthreads();
     }
-    const bool atomic = g.split_k > 1;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + 64 * wn + 32 * j + l31;
-        if (col >= g.N) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 128 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row >= M) continue;
-                const float v = g.alpha * acc[i][j][r];
-                float* c = g.C + (size_t)row * g.ldc + col;
-                if (atomic) atomicAdd(c, v);
-                else if (g.accumulate) *c += v;
-                else *c = v;
-            }
-        }
-    }
+    // (no bias in this form: gemm_bf16_tn refuses one)
+    epilogue_generic<4, 2, false>(acc, g.C, g.ldc, M, g.N, m0 + 128 * wm, n0 + 64 * wn, h, l31, g.alpha, nullptr,
+                     g.split_k > 1 ? kEpiAtomic : (g.accumulate ? kEpiAccumulate : kEpiStore));
 }
 
 static int big_tile_count(const GemmArgs& g) { return ((g.M + T2 - 1) / T2) * ((g.N + T2 - 1) / T2); }

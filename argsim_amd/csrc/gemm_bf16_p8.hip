@@ -41,11 +41,9 @@
 #include <type_traits>
 #include <utility>
 #include "kernels.h"
+#include "mfma_tile.h"
 
 namespace avae {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kP8Tile = 256, kP8K = 64, kP8Piece = 16384, kP8Ring = 8 * kP8Piece, kP8Lds = kP8Ring + 8 * 256, kP8Group = 8;
 constexpr int kP8Stores = 32;                            // stores per wave of a whole-tile epilogue
@@ -75,14 +73,13 @@ __device__ __forceinline__ void dma4(const float* g, unsigned char* l)
 // behind the intrinsic hipcc (ROCm 7.2) waits vmcnt(0) before every such read while an LDS-DMA is in flight (it cannot tell the
 // read from the DMA's target), which drains the ring each phase.  The caller waits lgkmcnt(0) itself before the first use.
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 template <int OFF>
 __device__ __forceinline__ bf16x8 frag_tr(unsigned lds_addr)
 {
     u32x2 lo, hi;
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(lds_addr), "n"(OFF));
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(lds_addr), "n"(OFF + 1024));
-    return __builtin_bit_cast(bf16x8, u32x4v{lo[0], lo[1], hi[0], hi[1]});
+    return __builtin_bit_cast(bf16x8, u32x4{lo[0], lo[1], hi[0], hi[1]});
 }
 template <class F, int... I> __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
@@ -147,11 +144,9 @@ __global__ __launch_bounds__(512) void gemm_bf16_p8_kernel(P8Args g)
     const int nkt_all = TN ? max((K + kP8K - 1) / kP8K, 2) : K / kP8K, nslice = TN ? max(min(g.split_k, nkt_all >> 1), 1) : max(g.split_k, 1);
     const int work = tiles * nslice, G = gridDim.x;
     // this workgroup's place in a round of G work items: the (up to) 32 workgroups of an XCD take consecutive items
-    int place;
-    {
-        const int q = G >> 3, r = G & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-        place = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    int run0, run_n;
+    xcd_run(blockIdx.x & 7, G, run0, run_n);
+    const int place = run0 + (blockIdx.x >> 3);          // (blockIdx.x < G: the slot lies inside the run)
     if (place >= work) return;
     // item v -> K slice v / tiles, tile v % tiles in groups of kP8Group tile rows walked column by column: the ~32 tiles an
     // XCD works on at a time are an 8 x 4 block (12 operand panels through its L2 per K tile) instead of a tile row (33)
@@ -351,7 +346,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_p8_kernel(P8Args g)
                     const f32x4 x = g.alpha * acc[i][2 * jp], y = g.alpha * acc[i][2 * jp + 1];
                     const auto r0 = __builtin_amdgcn_permlane16_swap(p8_pk_f16(x[0], x[1]), p8_pk_f16(y[0], y[1]), false, false);
                     const auto r1 = __builtin_amdgcn_permlane16_swap(p8_pk_f16(x[2], x[3]), p8_pk_f16(y[2], y[3]), false, false);
-                    *reinterpret_cast<u32x4v*>(h0 + (size_t)((i >> 2) * 128 + (i & 3) * 16) * g.ldc + jp * 128) = u32x4v{r0[0], r1[0], r0[1], r1[1]};
+                    *reinterpret_cast<u32x4*>(h0 + (size_t)((i >> 2) * 128 + (i & 3) * 16) * g.ldc + jp * 128) = u32x4{r0[0], r1[0], r0[1], r1[1]};
                 }
         } else if (H16) {
 #pragma unroll

@@ -11,53 +11,19 @@
 // Within a 32-deep K tile, MFMA step j (0..15) of lane-half h consumes k = 8*(j>>2) + 4*h + (j&3):
 // a k-contiguous operand row then feeds four consecutive steps from ONE ds_read_b128.
 #include "kernels.h"
+#include "mfma_tile.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 namespace avae {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BK = 32;
-constexpr int LDK = BK + 4;     // k-contiguous tile row stride (floats): conflict-free b128 reads
-
-// stage one operand tile (ROWS x 32) global -> ROWS/32 float4 registers per thread
-template <bool XC, int ROWS>   // XC: x(m or n)-contiguous storage [k][x];  else k-contiguous [x][k]
-__device__ __forceinline__ void load_tile(float4 (&r)[ROWS / 32], const float* __restrict__ P, int ld,
-                                          int x0, int X, int k0, int K1, int tid)
-{
-#pragma unroll
-    for (int rep = 0; rep < ROWS / 32; ++rep) {
-        int f = tid + 256 * rep;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (XC) {
-            int k = k0 + f / (ROWS / 4), x = x0 + ((f % (ROWS / 4)) << 2);
-            if (k < K1 && x < X) v = *reinterpret_cast<const float4*>(P + (size_t)k * ld + x);
-        } else {
-            int x = x0 + (f >> 3), k = k0 + ((f & 7) << 2);
-            if (x < X && k < K1) v = *reinterpret_cast<const float4*>(P + (size_t)x * ld + k);
-        }
-        r[rep] = v;
-    }
-}
-
-template <bool XC, int ROWS>
-__device__ __forceinline__ void store_tile(float* __restrict__ s, const float4 (&r)[ROWS / 32], int tid)
-{
-#pragma unroll
-    for (int rep = 0; rep < ROWS / 32; ++rep) {
-        int f = tid + 256 * rep;
-        if (XC) *reinterpret_cast<float4*>(s + (f / (ROWS / 4)) * ROWS + ((f % (ROWS / 4)) << 2)) = r[rep];
-        else    *reinterpret_cast<float4*>(s + (f >> 3) * LDK + ((f & 7) << 2)) = r[rep];
-    }
-}
+constexpr int BK = kTileBK, LDK = kTileLDK;     // (mfma_tile.h; the predicated staging load_tile / store_tile lives there too)
 
 // Fast staging (shapes whose tiles need no per-element predicate, see gemm_f32()): raw buffer loads with per-thread
 // byte offsets computed once and a uniform (SGPR) base that advances per K tile; rows beyond the valid region read
-// as zero through the buffer's num_records.  The predicated path above spends ~650 vector instructions per wave
+// as zero through the buffer's num_records.  The predicated path (load_tile) spends ~650 vector instructions per wave
 // and K tile on exec-mask branches and 64-bit address arithmetic; this one ~20.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 template <bool XC, int ROWS>
 struct FastTile {
     const float* base; long long step, valid; unsigned voff[ROWS / 32];
@@ -86,11 +52,10 @@ struct FastTile {
     }
 };
 
-// Epilogue of a (32 WM TM) x (32 WN TN) block tile.  C/D map of a 32x32 MFMA tile: col = lane&31,
-// row = (r&3) + 8*(r>>2) + 4*(lane>>5).  MODE 0 store, 1 accumulate (+=), 2 float atomics (split-K).  A tile that lies
-// wholly inside the matrix takes the straight-line form (one address computation per 32x32 tile, no per-element
-// predicate or mode branch): the branchy generic form below costs ~40 instructions per element, which was ~15 % of
-// a K = 512 output tile.
+// Epilogue of a (32 WM TM) x (32 WN TN) block tile (C/D map: mfma32_row).  MODE 0 store, 1 accumulate (+=), 2 float atomics
+// (split-K).  A tile that lies wholly inside the matrix takes the straight-line form (one address computation per 32x32 tile, no
+// per-element predicate or mode branch): the branchy generic form (epilogue_generic, mfma_tile.h) costs ~40 instructions per
+// element, which was ~15 % of a K = 512 output tile.
 template <int MODE>
 __device__ __forceinline__ void put(float* c, float v)
 {
@@ -114,7 +79,7 @@ __device__ __forceinline__ void epilogue_full(const GemmArgs& g, const f32x16 (&
             float* c = g.C + (size_t)(m0 + 32 * (wm * TM + i) + 4 * h) * g.ldc + col;
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                put<MODE>(c + (size_t)((r & 3) + 8 * (r >> 2)) * g.ldc, g.alpha * acc[i][j][r] + bv[j]);
+                put<MODE>(c + (size_t)mfma32_row(r, 0) * g.ldc, g.alpha * acc[i][j][r] + bv[j]);
         }
     }
 }
@@ -129,25 +94,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x16 (&acc)[
         else epilogue_full<TM, TN, WN, 0>(g, acc, m0, n0, wm, wn, h, l31, add_bias);
         return;
     }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        int col = n0 + 32 * (wn * TN + j) + l31;
-        if (col >= g.N) continue;
-        float bv = add_bias ? g.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int row = m0 + 32 * (wm * TM + i) + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row >= M) continue;
-                float v = g.alpha * acc[i][j][r] + bv;
-                float* c = g.C + (size_t)row * g.ldc + col;
-                if (atomic) atomicAdd(c, v);
-                else if (g.accumulate) *c += v;
-                else *c = v;
-            }
-        }
-    }
+    epilogue_generic<TM, TN>(acc, g.C, g.ldc, M, g.N, m0 + 32 * wm * TM, n0 + 32 * wn * TN, h, l31, g.alpha, add_bias ? g.bias : nullptr,
+                             atomic ? kEpiAtomic : (g.accumulate ? kEpiAccumulate : kEpiStore));
 }
 
 // WM x WN waves (WM*WN = 4), each TM x TN MFMA tiles of 32x32: block tile BM = 32 WM TM, BN = 32 WN TN.
@@ -172,18 +120,13 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(GemmArgs g)
     if (g.dyn_kind == 1) M = min(M, *g.dyn);
     if (g.dyn_kind == 2) K = min(K, *g.dyn);
 
-    // XCD-aware tile order: blocks b, b+8, b+16.. share an XCD (round-robin dispatch), give each
-    // XCD a contiguous run of tiles; tiles advance along N fastest so a run shares A panels.
+    // XCD-aware tile order (xcd_tile): each XCD a contiguous run of tiles; tiles advance along N fastest so a run shares A panels.
     // The runs are cut over the EFFECTIVE tile count (device-side row count of a ragged batch): cut over the grid,
     // the XCDs whose runs lie beyond the real rows would idle while the others carry the whole GEMM.
     const int tiles_n = (g.N + BN - 1) / BN;
     const int nblk = ((M + BM - 1) / BM) * tiles_n;          // <= gridDim.x
-    int bid = blockIdx.x;
-    {
-        int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-        if (slot >= q + (xcd < r ? 1 : 0)) return;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int bid = xcd_tile(blockIdx.x, nblk);
+    if (bid < 0) return;
     const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
     if (m0 >= M) return;
@@ -199,12 +142,7 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(GemmArgs g)
     }
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     float4 ra[BM / 32], rb[BN / 32];
     FastTile<A_MC, BM> fa; FastTile<B_NC, BN> fb;
@@ -243,6 +181,9 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(GemmArgs g)
         // the waves inside their MFMA burst issue ahead of the co-resident workgroups' staging phases (address arithmetic, LDS writes, the
         // loads' issue): +1-3 % on every shape of the step (gpurun_out/s2_f32_prio2.log); a static priority per workgroup measured nothing
         __builtin_amdgcn_s_setprio(1);
+        // (mfma_ktile, written out: with the call in its place three shapes of scripts/gemm_bench.py measured 0.4-0.8 % slower than the parent's
+        //  spread, two of them on the double-buffered form -- same registers, two LDS address adds of the K loop and the basic-block order
+        //  moved; the persistent kernel below, knn.hip and probe.hip take the call; profiles/mfma_tile_ab.txt)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             float a[TM][4], b[TN][4];
@@ -314,10 +255,10 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_persist_kernel(GemmArgs g)
     if (g.dyn_kind == 1) M = min(M, *g.dyn);
     const int tiles_n = (g.N + BN - 1) / BN;
     const int nblk = ((M + BM - 1) / BM) * tiles_n;
-    // XCD-aware order (see gemm_f32_kernel): workgroups g, g + 8, ... share an XCD and walk its contiguous run of tiles
-    const int xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int run0 = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, run_n = q + (xcd < r ? 1 : 0);
+    // XCD-aware order (xcd_run): workgroups g, g + 8, ... share an XCD and walk its contiguous run of tiles
+    const int per_xcd = gridDim.x >> 3;
+    int run0, run_n;
+    xcd_run(blockIdx.x & 7, nblk, run0, run_n);
     int local = blockIdx.x >> 3;
     if (local >= run_n) return;
 
@@ -340,12 +281,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_persist_kernel(GemmArgs g)
         const int m0 = tm * BM, n0 = tn * BN;
         const bool more = local + per_xcd < run_n;
         f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+        zero_acc(acc);
         for (int k0 = 0; k0 < K; k0 += BK) {
             store_tile<A_MC, BM>(As, ra, tid);
             store_tile<B_NC, BN>(Bs, rb, tid);
@@ -361,37 +297,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_persist_kernel(GemmArgs g)
             }
             __syncthreads();
             __builtin_amdgcn_s_setprio(1);                    // (see gemm_f32_kernel)
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                float a[TM][4], b[TN][4];
-#pragma unroll
-                for (int t = 0; t < TM; ++t) {
-                    if (A_MC) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) a[t][e] = As[(8 * qq + 4 * h + e) * BM + 32 * (wm * TM + t) + l31];
-                    } else {
-                        float4 v = *reinterpret_cast<const float4*>(As + (32 * (wm * TM + t) + l31) * LDK + 8 * qq + 4 * h);
-                        a[t][0] = v.x; a[t][1] = v.y; a[t][2] = v.z; a[t][3] = v.w;
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    if (B_NC) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) b[t][e] = Bs[(8 * qq + 4 * h + e) * BN + 32 * (wn * TN + t) + l31];
-                    } else {
-                        float4 v = *reinterpret_cast<const float4*>(Bs + (32 * (wn * TN + t) + l31) * LDK + 8 * qq + 4 * h);
-                        b[t][0] = v.x; b[t][1] = v.y; b[t][2] = v.z; b[t][3] = v.w;
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
-            }
+            mfma_ktile<A_MC, B_NC, TM, TN, BM, BN>(acc, As, Bs, wm, wn, h, l31);
             __builtin_amdgcn_s_setprio(0);
             __syncthreads();
         }
@@ -461,7 +367,7 @@ __global__ __launch_bounds__(512) void gemm_f32_skinny_kernel(GemmArgs g)
         float v = acc[r];
 #pragma unroll
         for (int w = 0; w < 7; ++w) v += red[w][r][lane];           // fixed order: the same bits every run
-        const int row = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = m0 + mfma32_row(r, h);
         if (row >= g.M) continue;
         float* c = g.C + (size_t)row * g.ldc + col;
         v = g.alpha * v + bv;

@@ -25,16 +25,11 @@
 // shapes).  s_setprio on either phase, deeper load prefetch and a hand-interleaved single-wave-per-SIMD form were
 // measured and brought nothing.
 #include "kernels.h"
+#include "mfma_tile.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace avae {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SBK = 32;               // K tile
 constexpr int SLD = 32;               // LDS row stride in bf16: 64-byte rows, no padding, XOR-swizzled (below)
@@ -220,16 +215,12 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void gemm_f32s_kernel(GemmArg
     if (g.dyn_kind == 1) M = min(M, *g.dyn);
     if (g.dyn_kind == 2) K = min(K, *g.dyn);
 
-    // XCD-aware tile order (as gemm_f32): blocks b, b+8, .. share an XCD; each XCD gets a contiguous run of tiles
+    // XCD-aware tile order (xcd_tile, mfma_tile.h): each XCD gets a contiguous run of tiles
     // (runs cut over the EFFECTIVE tile count -- the device-side row count of a ragged batch -- so that no XCD idles)
     const int tiles_n = (g.N + 127) / 128;
     const int tiles_m = (M + 127) / 128;
-    int bid = blockIdx.x;
-    {
-        const int nblk = tiles_m * tiles_n, q = nblk >> 3, r = nblk & 7, xcd = bid & 7, slot = bid >> 3;
-        if (slot >= q + (xcd < r ? 1 : 0)) return;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
+    const int bid = xcd_tile(blockIdx.x, tiles_m * tiles_n);
+    if (bid < 0) return;
     // grouped order inside the run: 8 row panels x all column panels, rows fastest, so that the ~64 tiles an XCD
     // works on at one time form an 8 x 8 block: 16 operand panels per K step instead of 3 + all of B
     // (the exact-fp32 kernel needs a quarter of this kernel's operand bandwidth and gets away without)
@@ -248,12 +239,7 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void gemm_f32s_kernel(GemmArg
     }
 
     f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     float4 ra[4], rb[4];
     FastSrc<A_MC> fsa; FastSrc<B_NC> fsb;
@@ -325,28 +311,10 @@ __global__ __launch_bounds__(256, NP == 1 ? 3 : 2) void gemm_f32s_kernel(GemmArg
     }
 #undef AVAE_STAMP
 
-    // epilogue.  C/D map of the 32x32 tile: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
     const bool atomic = g.split_k > 1;
     const bool add_bias = g.bias != nullptr && (!atomic || blockIdx.z == 0) && !(ABL & 16);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + 64 * wn + 32 * j + l31;
-        if (col >= g.N) continue;
-        const float bv = add_bias ? g.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (row >= M) continue;
-                const float v = g.alpha * acc[i][j][r] + bv;
-                float* c = g.C + (size_t)row * g.ldc + col;
-                if (atomic) atomicAdd(c, v);
-                else if (g.accumulate) *c += v;
-                else *c = v;
-            }
-        }
-    }
+    epilogue_generic(acc, g.C, g.ldc, M, g.N, m0 + 64 * wm, n0 + 64 * wn, h, l31, g.alpha, add_bias ? g.bias : nullptr,
+                     atomic ? kEpiAtomic : (g.accumulate ? kEpiAccumulate : kEpiStore));
 }
 
 // ---------------------------------------------------------------- wave-specialised form (fast-path shapes)
@@ -367,8 +335,9 @@ struct TileIter {
     __device__ __forceinline__ void seek()
     {
         for (ok = false; vb < nblk; vb += step) {
-            const int q = nblk >> 3, r = nblk & 7, xcd = vb & 7, slot = vb >> 3;
-            const int bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+            int run0, run_n;
+            xcd_run(vb & 7, nblk, run0, run_n);
+            const int bid = run0 + (vb >> 3);            // (vb < nblk: the slot lies inside the run)
             const int grp = bid / (8 * tiles_n), rem = bid - grp * 8 * tiles_n;
             const int gm = min(8, tiles_m - 8 * grp);
             const int tn = rem / gm, tm = 8 * grp + rem - tn * gm;
@@ -453,12 +422,7 @@ __global__ __launch_bounds__(768, 1) void gemm_f32s_ws_kernel(GemmArgs g, int nb
     __syncthreads();
     for (int G = 0; ti.ok; ti.next()) {
         f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        zero_acc(acc);
         for (int it = 0; it < nk; ++it, ++G) {
             const unsigned short* st = dsm + (G & 1) * 2 * NP * SPLANE;
             bf16x8 a[2][2][NP], b[2][2][NP];          // [step][tile][plane]
@@ -483,26 +447,8 @@ __global__ __launch_bounds__(768, 1) void gemm_f32s_ws_kernel(GemmArgs g, int nb
             }
             __syncthreads();
         }
-        const int m0 = ti.m0, n0 = ti.n0;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + 64 * wn + 32 * j + l31;
-            if (col >= g.N) continue;
-            const float bv = add_bias ? g.bias[col] : 0.f;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = m0 + 64 * wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (row >= M) continue;
-                    const float v = g.alpha * acc[i][j][r] + bv;
-                    float* c = g.C + (size_t)row * g.ldc + col;
-                    if (atomic) atomicAdd(c, v);
-                    else if (g.accumulate) *c += v;
-                    else *c = v;
-                }
-            }
-        }
+        epilogue_generic(acc, g.C, g.ldc, M, g.N, ti.m0 + 64 * wm, ti.n0 + 64 * wn, h, l31, g.alpha, add_bias ? g.bias : nullptr,
+                         atomic ? kEpiAtomic : (g.accumulate ? kEpiAccumulate : kEpiStore));
     }
 }
 

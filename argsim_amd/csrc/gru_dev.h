@@ -4,20 +4,10 @@
 #pragma once
 #include <type_traits>
 #include "kernels.h"
+#include "mfma_tile.h"      // the vector typedefs and pack_bf16
 
 namespace avae {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// two floats -> two bf16 (round to nearest even, v_cvt_pk_bf16_f32), `lo` in the low half
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 // 16-bit exchange (bf16 mode, backward team kernels): the exchanged operand itself is stored as bf16, eight k per 16-byte
 // chunk -- element (pos, row, k) at halfword
 //     X[(((pos * B/16 + row/16) * K/8 + k/8) * 16 + row%16) * 8 + k%8]

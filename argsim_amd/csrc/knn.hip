@@ -3,8 +3,8 @@
 //
 //   knn_norms  one wave per row of q and of the bank (metrics 1 and 2 only): the fixed-order sum of squares of that row
 //              alone, its square root for the cosine.  A second pass over the bank (DESIGN 4.3f states the cost).
-//   knn_tile   grid = (query tiles) x (bank parts).  A workgroup walks its part in 128-row bank tiles with the NT main loop of
-//              gemm_f32_kernel (k-contiguous operands, 32-deep K tiles, v_mfma_f32_32x32x2_f32, the next K tile's loads in
+//   knn_tile   grid = (query tiles) x (bank parts).  A workgroup walks its part in 128-row bank tiles with the NT K-tile step of
+//              mfma_tile.h (k-contiguous operands, 32-deep K tiles, v_mfma_f32_32x32x2_f32, the next K tile's loads in
 //              flight); the query tile is 128 rows (2 x 2 waves of 64 x 64) or 32 rows (1 x 4 waves of 32 x 32) where n is
 //              small.  The epilogue turns the accumulators into scores, drops what does not beat the query's current k-th best
 //              entry (kept per query in LDS) and appends the survivors to the query's LDS candidate list (integer LDS
@@ -18,6 +18,7 @@
 // MFMA step order whatever tile, part or launch shape it falls in (rows and K tails are zero filled, and x + 0 = x).  No
 // float atomics; the only atomics are integer LDS ones: the same arguments give the same bits.
 #include "kernels.h"
+#include "mfma_tile.h"
 #include "sample_dev.h"
 
 #include <algorithm>
@@ -27,11 +28,8 @@ namespace avae {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
-constexpr int kBK = 32;
-constexpr int kLDK = kBK + 4;      // k-contiguous tile row stride (floats): conflict-free b128 reads (gemm_f32.hip)
 constexpr int kBN = 128;           // bank rows per tile
 constexpr int kCap = 64;           // candidate slots per query in LDS: one wave ranks a full list with one entry per lane
 constexpr int kKnnMaxK = 32;
@@ -64,29 +62,6 @@ __global__ __launch_bounds__(256) void knn_norms_kernel(const float* __restrict_
     if (lane == 0) {
         const float v = metric == 1 ? __fsqrt_rn(s) : s;
         if (row < n) qn[row] = v; else bn[row - n] = v;
-    }
-}
-
-// stage one k-contiguous operand tile (ROWS x 32) global -> registers -> LDS; rows >= X and k >= K read as zero
-template <int ROWS>
-__device__ __forceinline__ void load_tile(float4 (&r)[ROWS / 32], const float* __restrict__ P, int ld, int x0, int X, int k0, int K, int tid)
-{
-#pragma unroll
-    for (int rep = 0; rep < ROWS / 32; ++rep) {
-        const int f = tid + 256 * rep;
-        const int x = x0 + (f >> 3), k = k0 + ((f & 7) << 2);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (x < X && k < K) v = *reinterpret_cast<const float4*>(P + (size_t)x * ld + k);
-        r[rep] = v;
-    }
-}
-template <int ROWS>
-__device__ __forceinline__ void store_tile(float* __restrict__ s, const float4 (&r)[ROWS / 32], int tid)
-{
-#pragma unroll
-    for (int rep = 0; rep < ROWS / 32; ++rep) {
-        const int f = tid + 256 * rep;
-        *reinterpret_cast<float4*>(s + (f >> 3) * kLDK + ((f & 7) << 2)) = r[rep];
     }
 }
 
@@ -127,13 +102,13 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnTileArgs a)
 {
     constexpr int BM = 32 * WM * TM;
     static_assert(32 * WN * TN == kBN && TN * 16 <= 32, "tile shape");
-    __shared__ __attribute__((aligned(16))) float s_tile[(BM + kBN) * kLDK];
+    __shared__ __attribute__((aligned(16))) float s_tile[(BM + kBN) * kTileLDK];
     __shared__ u64 s_list[BM * kCap];
     __shared__ u64 s_adm[BM];             // a candidate is admitted when its entry > s_adm: 0 until the list has been cut to k, then its k-th entry
     __shared__ int s_cnt[BM];
     __shared__ float s_qn[BM];
     float* As = s_tile;
-    float* Bs = s_tile + BM * kLDK;
+    float* Bs = s_tile + BM * kTileLDK;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, l31 = lane & 31;
@@ -154,52 +129,26 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnTileArgs a)
 
     for (int n0 = (int)c_begin; n0 < c_end; n0 += kBN) {
         f32x16 acc[TM][TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        zero_acc(acc);
 
         float4 ra[BM / 32], rb[kBN / 32];
-        load_tile<BM>(ra, a.q, dim, m0, a.n, 0, dim, tid);
-        load_tile<kBN>(rb, a.bank, dim, n0, c_end, 0, dim, tid);
-        for (int k0 = 0; k0 < dim; k0 += kBK) {
-            store_tile<BM>(As, ra, tid);
-            store_tile<kBN>(Bs, rb, tid);
-            if (k0 + kBK < dim) {         // the next K tile's loads go out before the barrier that publishes this one
-                load_tile<BM>(ra, a.q, dim, m0, a.n, k0 + kBK, dim, tid);
-                load_tile<kBN>(rb, a.bank, dim, n0, c_end, k0 + kBK, dim, tid);
+        load_tile<false, BM>(ra, a.q, dim, m0, a.n, 0, dim, tid);
+        load_tile<false, kBN>(rb, a.bank, dim, n0, c_end, 0, dim, tid);
+        for (int k0 = 0; k0 < dim; k0 += kTileBK) {
+            store_tile<false, BM>(As, ra, tid);
+            store_tile<false, kBN>(Bs, rb, tid);
+            if (k0 + kTileBK < dim) {         // the next K tile's loads go out before the barrier that publishes this one
+                load_tile<false, BM>(ra, a.q, dim, m0, a.n, k0 + kTileBK, dim, tid);
+                load_tile<false, kBN>(rb, a.bank, dim, n0, c_end, k0 + kTileBK, dim, tid);
             }
             __syncthreads();
             __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                float av[TM][4], bv[TN][4];
-#pragma unroll
-                for (int t = 0; t < TM; ++t) {
-                    const float4 v = *reinterpret_cast<const float4*>(As + (32 * (wm * TM + t) + l31) * kLDK + 8 * qq + 4 * h);
-                    av[t][0] = v.x; av[t][1] = v.y; av[t][2] = v.z; av[t][3] = v.w;
-                }
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    const float4 v = *reinterpret_cast<const float4*>(Bs + (32 * (wn * TN + t) + l31) * kLDK + 8 * qq + 4 * h);
-                    bv[t][0] = v.x; bv[t][1] = v.y; bv[t][2] = v.z; bv[t][3] = v.w;
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
-            }
+            mfma_ktile<false, false, TM, TN, BM, kBN>(acc, As, Bs, wm, wn, h, l31);
             __builtin_amdgcn_s_setprio(0);
             __syncthreads();
         }
 
-        // ---- epilogue: accumulators -> scores in place; `pend` marks the lane's elements that are not yet decided.
-        // C/D map of a 32x32 MFMA tile: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+        // ---- epilogue: accumulators -> scores in place; `pend` marks the lane's elements that are not yet decided (C/D map: mfma32_row)
         float bn[TN]; int colv[TN];
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -212,7 +161,7 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnTileArgs a)
             pend[i] = TN * 16 == 32 ? 0xFFFFFFFFu : (1u << (TN * 16)) - 1u;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float qn = s_qn[32 * (wm * TM + i) + (r & 3) + 8 * (r >> 2) + 4 * h];
+                const float qn = s_qn[32 * (wm * TM + i) + mfma32_row(r, h)];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j][r] = pair_score(METRIC, acc[i][j][r], qn, bn[j]);
             }
@@ -224,7 +173,7 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnTileArgs a)
                 if (!pend[i]) continue;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int rl = 32 * (wm * TM + i) + (r & 3) + 8 * (r >> 2) + 4 * h, row = m0 + rl;
+                    const int rl = 32 * (wm * TM + i) + mfma32_row(r, h), row = m0 + rl;
                     const u64 adm = row < a.n ? s_adm[rl] : ~0ull;                 // (no entry beats it: a row beyond n admits nothing)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {

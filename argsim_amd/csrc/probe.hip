@@ -2,7 +2,7 @@
 // in lockstep by a truncated Newton method (contract: include/argsim_vae.h, avae_probe_fit / avae_probe_decision).
 //
 //   probe_pass   grid = (row parts) x (problem tiles of 32).  A workgroup walks its part in tiles of 128 rows.  Per tile:
-//                  A  the 128 x 32 panel tile X V^T with the NT main loop of knn_tile (k-contiguous operands, 32-deep K tiles through
+//                  A  the 128 x 32 panel tile X V^T with the NT K-tile step of mfma_tile.h (k-contiguous operands, 32-deep K tiles through
 //                     LDS, v_mfma_f32_32x32x2_f32, the next K tile's loads in flight), one 32 x 32 MFMA tile per wave; the bias
 //                     column of x~ = (x, 1) is never materialised: the bias component of the vector is added in the epilogue;
 //                  E  the epilogue in registers: GRAD stores the decision z and the curvature D = |s| sigma(m) sigma(-m) and forms
@@ -22,6 +22,7 @@
 // row parts are a function of (N, probe_chunk) alone, so its bits do not depend on P, on its position or on its companions.  A
 // launch whose 32 problems are all idle returns at once; an idle problem in a busy tile is computed and ignored.  No float atomics.
 #include "kernels.h"
+#include "mfma_tile.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -30,10 +31,6 @@ namespace avae {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kBK = 32;
-constexpr int kLDK = kBK + 4;      // k-contiguous tile row stride (floats): conflict-free b128 reads (gemm_f32.hip)
 constexpr int kTR = 128;           // rows per tile
 constexpr int kTP = kProbeTile;    // problems per tile
 constexpr int kNA = kProbeAlphas;  // step lengths per probe_trial launch
@@ -42,29 +39,6 @@ constexpr int kNA = kProbeAlphas;  // step lengths per probe_trial launch
 enum { I_ITER = 0, I_STATUS = 1, I_FROZEN = 2, I_CG = 3, I_LS = 4, I_ALIVE = 5 };
 enum { F_F = 0, F_GNORM = 1, F_G0 = 2 };
 enum { D_RR = 0, D_GTP = 1, D_WTP = 2, D_PP = 3, D_PHI0 = 4 };
-
-// stage one k-contiguous operand tile (ROWS x 32) global -> registers -> LDS; rows >= X and k >= K read as zero
-template <int ROWS>
-__device__ __forceinline__ void load_tile(float4 (&r)[(ROWS + 31) / 32], const float* __restrict__ P, int ld, int x0, int X, int k0, int K, int tid)
-{
-#pragma unroll
-    for (int rep = 0; rep < (ROWS + 31) / 32; ++rep) {
-        const int f = tid + 256 * rep;
-        const int x = x0 + (f >> 3), k = k0 + ((f & 7) << 2);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (x < X && k < K) v = *reinterpret_cast<const float4*>(P + (size_t)x * ld + k);
-        r[rep] = v;
-    }
-}
-template <int ROWS>
-__device__ __forceinline__ void store_tile(float* __restrict__ s, const float4 (&r)[(ROWS + 31) / 32], int tid)
-{
-#pragma unroll
-    for (int rep = 0; rep < (ROWS + 31) / 32; ++rep) {
-        const int f = tid + 256 * rep;
-        *reinterpret_cast<float4*>(s + (f >> 3) * kLDK + ((f & 7) << 2)) = r[rep];
-    }
-}
 
 struct ProbePassArgs {
     const float* x;          // (N, dim)
@@ -83,11 +57,11 @@ template <int MODE, int DT>
 __global__ __launch_bounds__(256) void probe_pass_kernel(ProbePassArgs a)
 {
     constexpr int VW = DT >= 4 ? 4 : DT;          // floats a lane loads per row in step B
-    __shared__ __attribute__((aligned(16))) float s_tile[(kTR + kTP) * kLDK];
+    __shared__ __attribute__((aligned(16))) float s_tile[(kTR + kTP) * kTileLDK];
     __shared__ float s_R[kTR * kTP];
     __shared__ float s_red[2][8][kTP];
     float* As = s_tile;
-    float* Bs = s_tile + kTR * kLDK;
+    float* Bs = s_tile + kTR * kTileLDK;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, l31 = lane & 31;
@@ -113,49 +87,40 @@ __global__ __launch_bounds__(256) void probe_pass_kernel(ProbePassArgs a)
 
     for (int row0 = (int)c_begin; row0 < c_end; row0 += kTR) {
         // ---- A: acc = X[row0 + 32 wave ..][:] . V[p0 ..][:]^T
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        float4 ra[kTR / 32], rb[1];
-        load_tile<kTR>(ra, a.x, dim, row0, c_end, 0, dim, tid);
-        load_tile<kTP>(rb, a.v, a.LD, p0, Ppad, 0, dim, tid);
-        for (int k0 = 0; k0 < dim; k0 += kBK) {
-            store_tile<kTR>(As, ra, tid);
-            store_tile<kTP>(Bs, rb, tid);
-            if (k0 + kBK < dim) {         // the next K tile's loads go out before the barrier that publishes this one
-                load_tile<kTR>(ra, a.x, dim, row0, c_end, k0 + kBK, dim, tid);
-                load_tile<kTP>(rb, a.v, a.LD, p0, Ppad, k0 + kBK, dim, tid);
+        f32x16 acc[1][1];
+        zero_acc(acc);
+        float4 ra[kTR / 32], rb[kTP / 32];
+        load_tile<false, kTR>(ra, a.x, dim, row0, c_end, 0, dim, tid);
+        load_tile<false, kTP>(rb, a.v, a.LD, p0, Ppad, 0, dim, tid);
+        for (int k0 = 0; k0 < dim; k0 += kTileBK) {
+            store_tile<false, kTR>(As, ra, tid);
+            store_tile<false, kTP>(Bs, rb, tid);
+            if (k0 + kTileBK < dim) {         // the next K tile's loads go out before the barrier that publishes this one
+                load_tile<false, kTR>(ra, a.x, dim, row0, c_end, k0 + kTileBK, dim, tid);
+                load_tile<false, kTP>(rb, a.v, a.LD, p0, Ppad, k0 + kTileBK, dim, tid);
             }
             __syncthreads();
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                const float4 av = *reinterpret_cast<const float4*>(As + (32 * wave + l31) * kLDK + 8 * qq + 4 * h);
-                const float4 bv = *reinterpret_cast<const float4*>(Bs + l31 * kLDK + 8 * qq + 4 * h);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc, 0, 0, 0);
-            }
+            mfma_ktile<false, false, 1, 1, kTR, kTP>(acc, As, Bs, wave, 0, h, l31);      // (no s_setprio here: not measured in this kernel)
             __syncthreads();
         }
 
-        // ---- E: C/D map of a 32x32 MFMA tile: col (problem) = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+        // ---- E: the wave's 32 x 32 tile (C/D map: mfma32_row; col = problem)
         float pv[16];             // the tile's costs (GRAD) or curvature (HV): unconditional loads, all in flight at once
         if (MODE != 2) {
             const float* panel = MODE == 0 ? a.sT : a.D;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = row0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = row0 + 32 * wave + mfma32_row(r, h);
                 const float v = panel[(size_t)min(row, c_end - 1) * Ppad + prob];
                 pv[r] = row < c_end ? v : 0.f;
             }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rl = 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * h, row = row0 + rl;
+            const int rl = 32 * wave + mfma32_row(r, h), row = row0 + rl;
             const bool valid = row < c_end;
             const size_t at = (size_t)row * Ppad + prob;
-            const float zz = acc[r] + vb;
+            const float zz = acc[0][0][r] + vb;
             if (MODE == 2) {
                 if (valid && prob < a.pout) a.out[(size_t)row * a.ldo + prob] = zz;
             } else {
@@ -230,7 +195,7 @@ __global__ __launch_bounds__(256) void probe_pass_kernel(ProbePassArgs a)
         const int blk = t / VW, e = t % VW;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int j = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int j = mfma32_row(r, h);
             const int d = d0 + blk * 32 * VW + VW * j + e;
             if (d < dim) gp[(size_t)d * Ppad + prob] = g[t][r];
         }
