@@ -1,0 +1,106 @@
+// clustering.cpp -- Ward clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
+// (contract: include/argsim_vae.h; kernels: ward.hip).
+#include "ctx.h"
+
+using namespace avae;
+using namespace avae::host;
+
+namespace {
+
+// Workspace of a call, every buffer on a 256-byte boundary: G descriptors, then per group of n rows
+//   4 n^2 bytes     the square of stored pair values (its upper triangle is used)
+//   8 n dim bytes   the double sums of member rows
+//   12 n + 16 bytes counts, nearest-neighbour cache words, the last merge
+void ward_layout(Bump& b, std::vector<WardGroup>& gs, WardGroup** dev, const int32_t* off, int G, int dim)
+{
+    *dev = b.take<WardGroup>((size_t)G);
+    for (int g = 0; g < G; ++g) {
+        WardGroup& w = gs[g];
+        const size_t n = (size_t)(off[g + 1] - off[g]);
+        w.off = off[g]; w.n = (int)n; w.mrg = off[g] - g; w.pad = 0;
+        w.D = b.take<float>(n * n);
+        w.S = b.take<double>(n * dim);
+        w.nn = b.take<unsigned long long>(n);
+        w.cnt = b.take<int>(n);
+        w.st = b.take<int>(4);
+    }
+}
+
+// group_off as the header states it; *nmax <- the largest group
+int check_groups(avae_ctx* h, const char* what, const int32_t* off, int G, int* nmax)
+{
+    const std::string w(what);
+    if (G < 1 || G > (1 << 16)) return fail(h, w + ": G must be in [1, 2^16]");
+    if (off[0] != 0) return fail(h, w + ": group_off[0] must be 0");
+    *nmax = 0;
+    for (int g = 0; g < G; ++g) {
+        if (off[g + 1] <= off[g]) return fail(h, w + ": group_off must ascend, with at least one row per group");
+        if (off[g + 1] - off[g] > (1 << 15)) return fail(h, w + ": at most 2^15 rows per group");
+        *nmax = std::max(*nmax, off[g + 1] - off[g]);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int avae_ward(avae_handle h, const float* x, int32_t dim, const int32_t* group_off, int32_t G, const avae_ward_config* wc,
+              int32_t* pair, float* delta, int32_t* size)
+{
+    if (!h) return 1;
+    if (!wc) return fail(h, "ward config is null");
+    if (!x || !group_off || !pair || !delta) return fail(h, "ward: x, group_off, pair and delta must be given");
+    int nmax = 0;
+    AV_TRY(check_groups(h, "ward", group_off, G, &nmax));
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "ward: dim must be a multiple of 4 in [4, 1024]");
+    if ((uintptr_t)x & 15) return fail(h, "ward: x must be 16-byte aligned");
+    if (wc->reserved[0] != 0 || wc->reserved[1] != 0) return fail(h, "ward: the reserved fields must be 0");
+    if (nmax < 2) return 0;                                     // every group a single row: no merge, nothing written
+    AV_CHECK(hipSetDevice(h->device));
+    std::vector<WardGroup> gs((size_t)G);
+    WardGroup* dev = nullptr;
+    Bump probe{nullptr};
+    ward_layout(probe, gs, &dev, group_off, G, dim);
+    AV_TRY(reserve_named(h, probe.off + 4096, "ward"));         // sized once per call; nothing is allocated between the launches
+    Bump real{h->ws};
+    ward_layout(real, gs, &dev, group_off, G, dim);
+    AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardGroup), hipMemcpyHostToDevice, h->stream));
+    AV_CHECK(ward_init(h->stream, dev, G, nmax, x, dim));
+    const int form = h->ward_form ? h->ward_form : (nmax <= kWardOneWgMax ? 1 : 2);
+    if (form == 1) {
+        AV_CHECK(ward_tree(h->stream, dev, G, nmax, dim, pair, delta, size));
+    } else {
+        // the same two launches for every merge; a group with fewer merges returns at once.  Never a synchronisation: what a round
+        // merges is decided on the device
+        for (int t = 0; t < nmax - 1; ++t) AV_CHECK(ward_round(h->stream, dev, G, nmax, dim, t, pair, delta, size));
+    }
+    return 0;
+}
+
+int avae_ward_cut(avae_handle h, const int32_t* pair, const int32_t* group_off, int32_t G, const int32_t* k, int32_t* label)
+{
+    if (!h) return 1;
+    if (!pair || !group_off || !k || !label) return fail(h, "ward cut: pair, group_off, k and label must be given");
+    int nmax = 0;
+    AV_TRY(check_groups(h, "ward cut", group_off, G, &nmax));
+    std::vector<WardCutGroup> gs((size_t)G);
+    for (int g = 0; g < G; ++g) {
+        const int n = group_off[g + 1] - group_off[g];
+        if (k[g] < 1 || k[g] > n) return fail(h, "ward cut: k[g] must be in [1, n_g]");
+        gs[g] = WardCutGroup{group_off[g], n, group_off[g] - g, n - k[g]};
+    }
+    AV_CHECK(hipSetDevice(h->device));
+    WardCutGroup* dev = nullptr; int32_t* parent = nullptr;
+    auto lay = [&](Bump& b) { dev = b.take<WardCutGroup>((size_t)G); parent = b.take<int32_t>((size_t)group_off[G]); };
+    Bump probe{nullptr};
+    lay(probe);
+    AV_TRY(reserve_named(h, probe.off + 4096, "ward cut"));
+    Bump real{h->ws};
+    lay(real);
+    AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardCutGroup), hipMemcpyHostToDevice, h->stream));
+    AV_CHECK(ward_cut(h->stream, dev, G, nmax, pair, parent, label));
+    return 0;
+}
+
+}  // extern "C"

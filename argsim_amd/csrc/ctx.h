@@ -73,6 +73,7 @@ struct avae_ctx {
                           // exchange): 0 never, 1 wherever the geometry allows, 2 auto -- where few rows are alive per step (rs_pick)
     int knn_chunk = 0;    // avae_knn test aid: caps the bank rows one workgroup walks (small tests run many parts and the merge); 0: knn_plan decides
     int agg_chunk = 0;    // avae_agg_logq test aid: caps the bank rows of a part (small tests run several parts and the merge); 0: agg_plan decides
+    int ward_form = 0;    // avae_ward test aid: 0 the planner picks the kernel form from the largest group, 1 one-workgroup, 2 launch-per-merge (same bits)
     int probe_chunk = 0;  // avae_probe_fit / avae_probe_decision test aid: caps the rows of a part (small tests run several parts and the merge); 0: probe_plan decides
     int gru_bf16 = 1;     // compute_dtype 1 only: the recurrent product of the team kernels takes bf16 operands too (0: fp32 recurrence)
     // offsets
@@ -263,6 +264,17 @@ inline GemmCall tn_grad(const float* A, int lda, const float* B, int ldb, float*
 bool use_table(const avae_ctx* h, int rows, int B);
 void layout(avae_ctx* h, Bump& b, Ws& w, int B, int Ss, int St, bool train);
 int reserve_ws(avae_ctx* h, size_t need);
+// reserve_ws for a call that sizes its workspace once: a refusal names the call and the byte count
+inline int reserve_named(avae_ctx* h, size_t need, const char* what)
+{
+    if (reserve_ws(h, need)) {
+        (void)hipGetLastError();                                   // (the refused allocation is reported here, not by a later launch check)
+        char b[256]; snprintf(b, sizeof b, "%s: the device cannot give the workspace of %zu bytes this call needs", what, need);
+        h->err = b;
+        return 1;
+    }
+    return 0;
+}
 int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train);
 int gemm(avae_ctx* h, const GemmCall& c);
 int gemm_tn16(avae_ctx* h, const GemmCall& c);

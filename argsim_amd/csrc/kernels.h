@@ -396,6 +396,24 @@ hipError_t probe_finish(hipStream_t st, const ProbeWs& b, int P, float* w, float
 // out (n, P) = x~ w^T; W: (Ppad, LD) floats of workspace
 hipError_t probe_decision(hipStream_t st, const ProbePlan& p, const float* x, int n, int dim, const float* w, int P, float* W, float* out);
 
+// ---------------------------------------------------------------- Ward clustering of latent rows (ward.hip)
+// G independent groups per call (contract: include/argsim_vae.h, avae_ward).  A group's buffers are workspace laid out by the caller
+// (clustering.cpp); the descriptors themselves live in device memory.
+constexpr int kWardOneWgMax = 128;    // planner: the one-workgroup form up to this many rows in the largest group (where the two forms were measured to cross)
+struct WardGroup {
+    int off, n, mrg, pad;             // first row of x, rows, first merge row of pair / delta / size (= off - g)
+    float* D;                         // (n, n): [i][j], i < j, the stored pair values
+    double* S;                        // (n, dim) sums of member rows
+    int* cnt;                         // (n) member counts, 0 = retired
+    unsigned long long* nn;           // (n) nearest-neighbour cache words (ward.hip)
+    int* st;                          // (4) the last merge (a, b)
+};
+struct WardCutGroup { int off, n, mrg, m; };      // m: merges to replay (n - k)
+hipError_t ward_init(hipStream_t st, const WardGroup* gs, int G, int nmax, const float* x, int dim);      // sums, counts, every pair value, the row caches
+hipError_t ward_tree(hipStream_t st, const WardGroup* gs, int G, int nmax, int dim, int32_t* pair, float* delta, int32_t* size);      // one-workgroup form: all merges
+hipError_t ward_round(hipStream_t st, const WardGroup* gs, int G, int nmax, int dim, int t, int32_t* pair, float* delta, int32_t* size);      // launch-per-merge form: merge t of every group
+hipError_t ward_cut(hipStream_t st, const WardCutGroup* gs, int G, int nmax, const int32_t* pair, int32_t* p /* (N) workspace */, int32_t* label);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

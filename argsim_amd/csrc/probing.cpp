@@ -25,16 +25,6 @@ void probe_layout(Bump& b, ProbeWs& w, const ProbePlan& p, int N, int dim)
     w.N = N; w.dim = dim; w.LD = p.LD; w.Ppad = p.Ppad; w.parts = p.parts; w.chunk = p.chunk;
 }
 
-int probe_reserve(avae_ctx* h, size_t need, const char* what)
-{
-    if (reserve_ws(h, need)) {
-        (void)hipGetLastError();                                   // (the refused allocation is reported here, not by a later launch check)
-        char b[256]; snprintf(b, sizeof b, "%s: the device cannot give the workspace of %zu bytes this call needs", what, need);
-        return fail(h, b);
-    }
-    return 0;
-}
-
 // the trial rounds of the Armijo search: step length 0 (the loss at w from the same panels) and 1, 1/2, .. 2^-20
 void probe_rounds(ProbeAlphas (&r)[4])
 {
@@ -73,7 +63,7 @@ int avae_probe_fit(avae_handle h, const float* x, int32_t N, int32_t dim, const 
     ProbeWs b{};
     Bump probe{nullptr};
     probe_layout(probe, b, p, N, dim);
-    AV_TRY(probe_reserve(h, probe.off + 4096, "probe"));        // sized once per call; nothing is allocated between the launches
+    AV_TRY(reserve_named(h, probe.off + 4096, "probe"));        // sized once per call; nothing is allocated between the launches
     Bump real{h->ws};
     probe_layout(real, b, p, N, dim);
     ProbeAlphas rounds[4];
@@ -117,7 +107,7 @@ int avae_probe_decision(avae_handle h, const float* x, int32_t n, int32_t dim, c
     AV_CHECK(hipSetDevice(h->device));
     const ProbePlan p = probe_plan(n, P, dim, h->probe_chunk);
     if ((long long)p.parts * p.ptiles > 0x7fffffffLL ) return fail(h, "probe decision: too many (row part, problem tile) workgroups for one launch");
-    AV_TRY(probe_reserve(h, (size_t)p.Ppad * p.LD * sizeof(float) + 4096, "probe decision"));
+    AV_TRY(reserve_named(h, (size_t)p.Ppad * p.LD * sizeof(float) + 4096, "probe decision"));
     AV_CHECK(probe_decision(h->stream, p, x, n, dim, w, P, reinterpret_cast<float*>(h->ws), out));
     return 0;
 }

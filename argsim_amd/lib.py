@@ -65,6 +65,10 @@ class AvaeProbeConfig(C.Structure):
     _fields_ = [('max_newton', C.c_int32), ('max_cg', C.c_int32), ('tol', C.c_float), ('reserved', C.c_int32)]
 
 
+class AvaeWardConfig(C.Structure):
+    _fields_ = [('reserved', C.c_int32 * 2)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -103,6 +107,8 @@ SIGNATURES = {
     'avae_latent_moments': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P]),
     'avae_probe_fit': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(AvaeProbeConfig), _P, _P]),
     'avae_probe_decision': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    'avae_ward': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(AvaeWardConfig), _P, _P, _P]),
+    'avae_ward_cut': (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),

@@ -16,6 +16,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) nearest neighbours among latent rows         -> VAE.neighbors(queries, bank, k, metric) / neighbors(vae, ...)
     (new) aggregate-posterior diagnostics (MI, AU)     -> VAE.posterior_stats(src) / VAE.log_q(z, mu, lv) / VAE.latent_moments(mu, lv)
     (new) linear probes of latent rows (liblinear CV)  -> VAE.probe_fit(z, labels) / VAE.probe_cv(z, labels, folds, groups)
+    (new) Ward clustering of latent rows (ARS, V_MSR)  -> VAE.ward(z, groups) / VAE.ward_cut(res, k) / VAE.cluster_eval(z, gold, groups)
 """
 import ctypes as C
 
@@ -598,6 +599,25 @@ class VAE:
         from . import probe
         return probe.cross_validate(self, z, labels, folds, groups, C, class_weight, **solver)
 
+    def ward(self, z, groups=None):
+        """the Ward tree (sklearn's AgglomerativeClustering default, scipy's linkage(x, 'ward')) of every group of rows of z, all groups
+        in ONE device call (include/argsim_vae.h, avae_ward).  groups: None, an (N,) array of group labels or {key: row numbers}
+        -> dict(keys, group_off, groups {key: dict(rows, pair, delta, size, Z)}) (argsim_amd/cluster.py)"""
+        from . import cluster
+        return cluster.ward(self, z, groups)
+
+    def ward_cut(self, res, k):
+        """the clusters of ward's result cut at k clusters per group (avae_ward_cut) -> {key: labels 0 .. k - 1 aligned with the
+        group's rows}"""
+        from . import cluster
+        return cluster.ward_cut(self, res, k)
+
+    def cluster_eval(self, z, gold, groups=None):
+        """the reference's clustering evaluation (src/eval_clustering.py:95-102) for every group at once -> {key: (ARS, V_MSR)}: as
+        many Ward clusters as the group has distinct gold labels, scored by the adjusted Rand score and the V-measure"""
+        from . import cluster
+        return cluster.cluster_eval(self, z, gold, groups)
+
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
 
@@ -789,3 +809,18 @@ def probe_fit(vae, z, labels, C=0.001, class_weight='balanced', train=None, **so
 def probe_cv(vae, z, labels, folds, groups=None, C=0.001, class_weight='balanced', **solver):
     """functional form of VAE.probe_cv"""
     return vae.probe_cv(z, labels, folds, groups, C, class_weight, **solver)
+
+
+def ward(vae, z, groups=None):
+    """functional form of VAE.ward"""
+    return vae.ward(z, groups)
+
+
+def ward_cut(vae, res, k):
+    """functional form of VAE.ward_cut"""
+    return vae.ward_cut(res, k)
+
+
+def cluster_eval(vae, z, gold, groups=None):
+    """functional form of VAE.cluster_eval"""
+    return vae.cluster_eval(z, gold, groups)

@@ -11,7 +11,8 @@
  *   - every tensor pointer is a DEVICE pointer owned by the caller (e.g. a PyTorch-ROCm
  *     tensor's data_ptr()); the library never frees caller memory.  It owns only its
  *     workspace.  Parameters, gradients and Adam slots live in four caller-allocated flat
- *     float32 buffers bound with avae_bind_state().
+ *     float32 buffers bound with avae_bind_state().  (One exception: group_off and k of avae_ward /
+ *     avae_ward_cut are host arrays, as their section says.)
  *   - int return: 0 = ok, non-zero = error, text via avae_last_error().  No C++ exception
  *     crosses the ABI.
  *   - all work is enqueued on the stream given to avae_set_stream() (default: the null
@@ -402,6 +403,46 @@ int  avae_probe_fit(avae_handle h, const float* x /* (N, dim) */, int32_t N, int
                     float* w /* (P, dim + 1) out */, float* stats /* (P, 4) optional */);
 int  avae_probe_decision(avae_handle h, const float* x /* (n, dim) */, int32_t n, int32_t dim,
                          const float* w /* (P, dim + 1) */, int32_t P, float* out /* (n, P) */);
+
+/* ---- hierarchical clustering of latent rows -------------------------------------------------- */
+/* The clustering evaluation of the reference (src/eval_clustering.py:82-103, src/eval_clustering_explorative.py:138-176:
+ * AgglomerativeClustering, Ward linkage, per selection of rows) as ONE call over G independent groups of rows.  x (N, dim) is a
+ * row-major float32 device array, 16-byte aligned, dim a multiple of 4 in [4, 1024] and independent of the handle's dim_rep.
+ * group_off (G + 1) and k (G) are HOST arrays -- the one exception to "every tensor pointer is a device pointer": the host sizes the
+ * workspace and the launches from them.  Group g is rows group_off[g] .. group_off[g + 1] of x, n_g >= 1 of them (n_g <= 2^15,
+ * 1 <= G <= 2^16); its n_g - 1 merges are rows group_off[g] - g .. of pair (N - G, 2), delta (N - G) and size (N - G, optional).
+ *   identity   a cluster lives in the SLOT of its smallest member row (group-local index).  Merge t joins the slots a < b into slot
+ *              a: pair[t] = (a, b), size[t] the member count afterwards.
+ *   value      Delta(A, B) = |A||B| / (|A| + |B|) |c_A - c_B|^2, the increase of the within-cluster sum of squares (scipy's Ward
+ *              height is sqrt(2 Delta)).  Evaluated in double: per-cluster sums of member rows kept in double, c = sum / count, the
+ *              difference first and then its square (never |a|^2 - 2 a.b + |b|^2, which cancels exactly where Ward decides its first
+ *              merges), accumulated in a fixed order, times the size factor in double and rounded ONCE to fp32.  That fp32 value is
+ *              what is stored, compared and returned in delta.  It depends on the two clusters alone -- not on n_g, G, the group's
+ *              position or the kernel form -- and is symmetric by construction.
+ *   order      every step merges the alive pair with the smallest stored value; ties go to the lowest a, then the lowest b.  Values
+ *              compare through an order key in which a NaN is the largest value, so some alive pair always wins.
+ *   not finite inputs are NOT checked.  A row that is not finite gives an unspecified but complete tree: exactly n_g - 1 merges, every
+ *              slot b merged away exactly once, every loop bounded by n_g, never a hang.
+ *   bits       no float atomics, fixed-order reductions: the same arguments give the same bits, and a group's result does not depend
+ *              on its companions, on its position or on the kernel form.
+ *   forms      one workgroup per group runs all merges of the call in ONE launch (largest group <= 128 rows), or two launches
+ *              per merge over (groups, row tiles) with max n_g - 1 rounds enqueued without a synchronisation.  No kernel waits on
+ *              another workgroup.  Option ward_form (avae_set_option; a test aid): 0 the planner, 1 one-workgroup, 2 launch-per-merge.
+ *   workspace  per group 4 n_g^2 + 8 n_g dim + 12 n_g bytes (+ 256-byte rounding) and 56 G bytes, reserved once per call
+ *              (DESIGN.md 4.3i).
+ * N = G (every group a single row) is legal: no merge, the outputs are not touched.
+ * avae_ward_cut: label[i] = the slot (smallest member row, group-local) of row i's cluster after its group's first n_g - k[g]
+ * merges: p[b_t] = a_t, followed downwards from every leaf (slots only decrease: at most n_g steps).  Enqueued only; nothing is
+ * synchronised.
+ * Errors (text through avae_last_error): a null wc, x, group_off, pair or delta; G < 1 or G > 2^16; a group_off that does not ascend
+ * from 0 or has an empty group; n_g > 2^15; dim not a multiple of 4 in [4, 1024]; x not 16-byte aligned; reserved != 0; a workspace
+ * the device cannot give (the text names its size); for the cut a null pair, group_off, k or label, or k[g] outside [1, n_g].      */
+typedef struct avae_ward_config { int32_t reserved[2]; } avae_ward_config;
+int  avae_ward(avae_handle h, const float* x /* (N, dim) device */, int32_t dim,
+               const int32_t* group_off /* HOST (G + 1) */, int32_t G, const avae_ward_config* wc,
+               int32_t* pair /* (N - G, 2) */, float* delta /* (N - G) */, int32_t* size /* (N - G), optional */);
+int  avae_ward_cut(avae_handle h, const int32_t* pair /* device, as returned */, const int32_t* group_off /* HOST */, int32_t G,
+                   const int32_t* k /* HOST (G) */, int32_t* label /* (N) */);
 
 #ifdef __cplusplus
 }
