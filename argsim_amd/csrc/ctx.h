@@ -278,6 +278,8 @@ inline int reserve_named(avae_ctx* h, size_t need, const char* what)
 int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train);
 int gemm(avae_ctx* h, const GemmCall& c);
 int gemm_tn16(avae_ctx* h, const GemmCall& c);
+// batch groups per job and rows per group (a multiple of 16) of a GRU launch over B rows: at most 512 workgroups, at most 16 groups
+void gru_geometry(int D, int njobs, int B, int* G, int* rpg);
 void gru_common(avae_ctx* h, const Ws& w, GruArgs& a, int njobs, int S, int B, int ldg, int ldh, const int32_t* lens, int Bx);
 int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec, bool with_enc = true);
 int build_compact_dec(avae_ctx* h, Ws& w, int B, int T);

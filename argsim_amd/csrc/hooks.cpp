@@ -226,6 +226,7 @@ int avae_debug_op_layout(int64_t n, int64_t V, int64_t out[6])
 // non-zero return with the hipError_t text in avae_last_error.  Nothing else happens here.
 //   row_order: p = (lens, perm, slens) per order, then steps_sum; i = n, Breal, B, S, sum_rows, then (add, T, cpj) per order (n <= 4 read)
 //   id_groups_build / rows_group_sum: the scratch is p's last entry
+//   gru_first_step_fwd: p = gi, bR, h_out, sv, lens; i = ldo, B, D     gru_first_step_bwd: p = dh, sv, dgi, dgh, lens; i = ldd, B, D
 int avae_debug_op(avae_handle h, const char* op, void* const* p, const int64_t* i, const float* f)
 {
     if (!h || !op || !p || !i || !f) return 1;
@@ -270,8 +271,71 @@ int avae_debug_op(avae_handle h, const char* op, void* const* p, const int64_t* 
         const AdamArgs a{F(0), F(1), F(2), F(3), i[0], f[0], f[1], f[2], f[3], static_cast<const int*>(p[4])};
         AV_CHECK(adam_tf(st, a));
     } else if (o == "g16_permute") AV_CHECK(g16_permute(st, F(0), F(1), (int)i[0], (int)i[1], i[2] != 0));
+    else if (o == "gru_first_step_fwd") AV_CHECK(gru_first_step_fwd(st, F(0), F(1), F(2), (int)i[0], F(3), (int)i[1], (int)i[2], I(4)));
+    else if (o == "gru_first_step_bwd") AV_CHECK(gru_first_step_bwd(st, F(0), (int)i[0], F(1), F(2), F(3), (int)i[1], (int)i[2], I(4)));
     else return fail(h, "avae_debug_op: no such launcher: " + o);
     return 0;
+}
+
+// The shape half of a GRU launch as both GRU hooks take it: i = njobs, S, B, D, ldg, ldh, Bx, G, rows_per_group, p_begin, p_end, item_pipeline,
+// bf16, bwd_rs, xbuf_floats.  G = 0: the groups and rows per group the model gives the shape (gru_geometry).
+static void gru_shape(const int64_t* i, GruArgs& a)
+{
+    a.njobs = (int)i[0]; a.S = (int)i[1]; a.B = (int)i[2]; a.D = (int)i[3]; a.ldg = (int)i[4]; a.ldh = (int)i[5]; a.Bx = (int)i[6];
+    a.G = (int)i[7]; a.rows_per_group = (int)i[8]; a.p_begin = (int)i[9]; a.p_end = (int)i[10]; a.item_pipeline = (int)i[11];
+    a.bf16 = (int)i[12]; a.bwd_rs = (int)i[13]; a.xbuf_floats = (size_t)std::max<int64_t>(i[14], 0);
+    if (a.G == 0 && a.D >= 16 && a.njobs >= 1 && a.B >= 1) gru_geometry(a.D, a.njobs, a.B, &a.G, &a.rows_per_group);
+}
+static void gru_plan_out(const GruArgs& a, const GruPlan& p, int64_t out[10])
+{
+    const int64_t v[10] = {(int64_t)p.form, p.T, p.C, p.cpj, p.Bg, p.pipe, a.G, a.rows_per_group, (int64_t)gru_bwd_rs_xbuf_floats(a.njobs, p.Bg), 0};
+    std::copy(v, v + 10, out);
+}
+// test hook: gru_plan() for one launch shape (i: gru_shape above; a static aligned dummy stands in for the exchange scratch where xbuf_floats > 0).
+// out = form (GruForm: 0 stepwise, 1 persistent, 2 item, 3 team, 4 team_rs), T, C, cpj, Bg, pipe, the G and rows_per_group used, the floats of
+// exchange scratch the reduce-scatter backward needs for the shape (gru_bwd_rs_xbuf_floats), 0.  Host arithmetic only: callable without a GPU.
+int avae_debug_gru_plan(const int64_t* i, int fwd, int persistent, int64_t out[10])
+{
+    if (!i || !out) return 1;
+    alignas(16) static float dummy[4] = {0.f, 0.f, 0.f, 0.f};
+    GruArgs a{};
+    gru_shape(i, a);
+    a.xbuf = a.xbuf_floats > 0 ? dummy : nullptr;
+    gru_plan_out(a, gru_plan(a, fwd != 0, persistent != 0), out);
+    return 0;
+}
+// test hook: ONE gru_forward / gru_backward call on caller-owned device buffers, on the handle's stream -- plan, operand check, residency check and
+// exchange preparation as in the product.  i: gru_shape above, then stagger, force_slow, sv16, spec, then (reverse, dgi_by_pos) per job; jobs: 19
+// pointers per job, GruJob's pointer fields in their order (gi, gi_rows, R, bR, h0, hs, sv, hp, hs16, hp16, dh_out, dgi, dgh, dgi16, dgh16, dh0,
+// carry, dbW, dbR); shared: lens, slens, perm, rowmap, xbuf.  counters, err and stamps are the handle's, ablate is 0, and only whole-sequence launches
+// (p_begin = 0, p_end = S: all the product launches) are taken.  A launcher's refusal comes back as a non-zero return with the hipError_t text in
+// avae_last_error.  Synchronises, then reads (and clears) the device error word: an exchange time-out is a non-zero return too.  plan_out: as
+// avae_debug_gru_plan's out, the plan that ran.
+int avae_debug_gru(avae_handle h, int fwd, int persistent, const int64_t* i, void* const* jobs, void* const* shared, int64_t plan_out[10])
+{
+    if (!h || !i || !jobs || !shared || !plan_out) return 1;
+    GruArgs a{};
+    gru_shape(i, a);
+    if (a.njobs < 1 || a.njobs > kMaxGruJobs) return fail(h, "avae_debug_gru: njobs in 1..3");
+    if (a.p_begin != 0 || a.p_end != a.S) return fail(h, "avae_debug_gru: whole-sequence launches only (p_begin = 0, p_end = S)");
+    a.stagger = (int)i[15]; a.force_slow = (int)i[16]; a.sv16 = (int)i[17]; a.spec = (int)i[18];
+    for (int k = 0; k < a.njobs; ++k) {
+        void* const* p = jobs + 19 * k;
+        auto F = [&](int q) { return static_cast<float*>(p[q]); };
+        auto H = [&](int q) { return static_cast<unsigned short*>(p[q]); };
+        GruJob& j = a.job[k];
+        j.gi = F(0); j.gi_rows = static_cast<const int32_t*>(p[1]); j.R = F(2); j.bR = F(3); j.h0 = F(4); j.hs = F(5); j.sv = F(6); j.hp = F(7);
+        j.hs16 = H(8); j.hp16 = H(9); j.dh_out = F(10); j.dgi = F(11); j.dgh = F(12); j.dgi16 = H(13); j.dgh16 = H(14); j.dh0 = F(15);
+        j.carry = F(16); j.dbW = F(17); j.dbR = F(18);
+        j.reverse = (int)i[19 + 2 * k]; j.dgi_by_pos = (int)i[20 + 2 * k];
+    }
+    a.lens = static_cast<const int*>(shared[0]); a.slens = static_cast<const int*>(shared[1]); a.perm = static_cast<const int*>(shared[2]);
+    a.rowmap = static_cast<const int*>(shared[3]); a.xbuf = static_cast<float*>(shared[4]);
+    a.counters = h->counters; a.err = h->errw; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.ablate = 0;
+    gru_plan_out(a, gru_plan(a, fwd != 0, persistent != 0), plan_out);
+    AV_CHECK(hipSetDevice(h->device));
+    AV_GRU(fwd ? gru_forward(h->stream, a, persistent != 0) : gru_backward(h->stream, a, persistent != 0));
+    return check_gru_err(h);
 }
 
 // test hook: sample_rows (ops.hip, the launch-per-token sampler) on caller buffers at step t0, row index = batch row

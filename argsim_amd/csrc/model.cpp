@@ -291,7 +291,7 @@ int gemm_tn16(avae_ctx* h, const GemmCall& c)
 }
 static bool tn16_ok(const avae_ctx* h, int M, int N) { return h->cfg.compute_dtype == 1 && h->bf16_tn && gemm_tn16_shape(M, N); }
 
-static void gru_geometry(int D, int njobs, int B, int* G, int* rpg)
+void gru_geometry(int D, int njobs, int B, int* G, int* rpg)
 {
     int HT = D / 16;
     int gmax = 512 / (njobs * HT); if (gmax < 1) gmax = 1; if (gmax > 16) gmax = 16;

@@ -134,6 +134,8 @@ SIGNATURES = {
     'avae_debug_gemm_forced': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                                          _P, _P, _P, _P]),
     'avae_debug_gemm_f32_form': (C.c_int, [C.c_int] * 14 + [C.POINTER(C.c_int32)]),
+    'avae_debug_gru_plan': (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    'avae_debug_gru': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     'avae_bucket_count': (C.c_int, [_P]),
     'avae_bucket_info': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
