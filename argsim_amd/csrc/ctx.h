@@ -69,6 +69,8 @@ struct avae_ctx {
     //  compute_dtype 1: GEMMs read their fp32 operands directly and round to bf16 while staging (0: conversion passes + NT kernel)
     int gru_spec = 2;     // team kernels load a consumer's operand at once, without a probe round trip in front of it: 0 never, 1 always, 2 where few rows are alive per
                           // step (spec_pick: RAGGED 256 x 64 10.41 -> 10.23 ms; always-on costs a FULL 100 x 512 batch 1 %, 71.5 -> 72.3 ms, and a FULL 256 x 64 nothing)
+    int gru_ring = 1;     // fp32 team kernels with one row block per workgroup exchange through a 4-slot ring the producers re-arm themselves (GruPlan::ring): the launcher
+                          // fills min(S, 4) slots per job instead of S; 0: one slot per position (in-process A/B runs)
     int bwd_rs = 2;       // fp32 BPTT team kernels in the reduce-scatter form (gru_rs.hip: own gate columns x resident R slice, partial dH summed through the
                           // exchange): 0 never, 1 wherever the geometry allows, 2 auto -- where few rows are alive per step (rs_pick)
     int knn_chunk = 0;    // avae_knn test aid: caps the bank rows one workgroup walks (small tests run many parts and the merge); 0: knn_plan decides

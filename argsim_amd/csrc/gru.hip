@@ -442,9 +442,10 @@ __global__ __launch_bounds__(256, 2) void gru_fwd_item_kernel(GruArgs a)
 // the h_{t-1} of its (row, unit) in a register (one per row block) instead of picking it out of the exchanged operand; the
 // gate math and everything saved stay fp32.
 constexpr int kFwdTeamLdsBytes = (96 * 256 + 48 * 256 + 4 * 256) * 4 + 128;      // dynamic LDS of gru_fwd_team_kernel: Wl | part | hps | sync
-template <bool DIAG, bool PIPE, int T, bool BF = false, bool CMP = false>      // CMP: compact external arrays / phantom rows (GruArgs::rowmap, Bx)
+template <bool DIAG, bool PIPE, int T, bool BF = false, bool CMP = false, bool RING = false>      // CMP: compact external arrays / phantom rows (GruArgs::rowmap, Bx); RING: exchange ring (GruPlan::ring)
 __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
 {
+    static_assert(!RING || (!PIPE && !BF && !DIAG), "the exchange ring: fp32, one row block per workgroup");
     const int ab = DIAG ? a.ablate : 0;                     // timing experiments / stamps: diagnostic instantiation only
     constexpr int D = 512, HT = 32, KS = 16 / T, WK = D / KS, NQ = WK / 16, RB = 16 * T;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -504,7 +505,9 @@ __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
     float* __restrict__ p_hpw = J.hp;
     float* __restrict__ p_hsw = J.hs;
     // this job's exchange buffer (tiled, sentinel-filled; BF: S + 1 positions of 16-bit values)
-    float* const xh = BF ? a.xbuf + (size_t)tm.jb * (a.S + 1) * B * D / 2 : a.xbuf + (size_t)tm.jb * a.S * B * D;
+    // exchange ring (gru_dev.h): the value of iteration p (= the step: team launches begin at step 0) in slot p % kGruRing of min(S, kGruRing)
+    constexpr bool ring = RING;
+    float* const xh = BF ? a.xbuf + (size_t)tm.jb * (a.S + 1) * B * D / 2 : a.xbuf + (size_t)tm.jb * (ring ? min(a.S, kGruRing) : a.S) * B * D;
     const __amdgpu_buffer_rsrc_t rs_hs = make_rsrc(xh), rs_h0 = make_rsrc(J.h0 ? J.h0 : xh);
     const __amdgpu_buffer_rsrc_t rs_gi = make_rsrc(p_gi), rs_hsw = make_rsrc(p_hsw);
     const __amdgpu_buffer_rsrc_t rs_svw = make_rsrc(p_svw ? p_svw : p_hsw), rs_hpw = make_rsrc(p_hpw ? p_hpw : p_hsw);
@@ -551,7 +554,7 @@ __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
     auto a_offset = [&](int p, int row0, int len_a) -> unsigned {
         if constexpr (BF) return xch_lane_offset(p == 0 ? 0 : pos_map(p - 1, len_a, J.reverse) + 1, row0, wk * (WK / 8), n, kh, B, D / 2);
         if (p == 0) return (unsigned)((size_t)(CMP ? min(perm ? perm[row0 + n] : row0 + n, Bs - 1) : (perm ? perm[row0 + n] : row0 + n)) * D * 4) + (wk * WK + 4 * kh) * 4;      // (row-major h0: an external array; a phantom row reads the last real one's)
-        return xch_lane_offset(pos_map(p - 1, len_a, J.reverse), row0, wk * (WK / 4), n, kh, B, D);
+        return xch_lane_offset(ring ? ((p - 1) & (kGruRing - 1)) : pos_map(p - 1, len_a, J.reverse), row0, wk * (WK / 4), n, kh, B, D);
     };
     auto q_stride = [&](int p) -> unsigned { return (p == 0 && !BF) ? 64u : 1024u; };
     auto next_frag = [&](int p2, int r2, int len2) __attribute__((always_inline)) {   // PIPE: issue (or zero) the fragment of item (p2, r2)
@@ -651,7 +654,7 @@ __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
                         const int prow = row0 + 15;
                         const int plen = len_p0;                     // (!PIPE: one row block, fetched once before the loop)
                         const float* pp = BF ? xh + (xch16_index(pos_map(p - 1, plen, J.reverse) + 1, prow, (lane & 31) * 16 + 15, B, D) >> 1)      // (the high half of its dword)
-                                             : xh + xch_index(pos_map(p - 1, plen, J.reverse), prow, (lane & 31) * 16 + 15, B, D);
+                                             : xh + xch_index(ring ? ((p - 1) & (kGruRing - 1)) : pos_map(p - 1, plen, J.reverse), prow, (lane & 31) * 16 + 15, B, D);
                         SpinGuard sg;
                         while (__any(BF ? (load4_sc1(pp) >> 16) == 0xffffu : load4_sc1(pp) == kSentinel) && !sg.expired(a.err)) { }
                         }
@@ -762,7 +765,7 @@ __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
                 if constexpr (PIPE) { if (r == 0) hc0 = hnew; else if (r == 1) hc1 = hnew; else if (r == 2) hc2 = hnew; else hc3 = hnew; }
                 else hc = hnew;
             } else {
-                const unsigned xo = xch_index(gpos, grow, j, B, D) * 4u;      // exchanged store first
+                const unsigned xo = xch_index(ring ? (p & (kGruRing - 1)) : gpos, grow, j, B, D) * 4u;      // exchanged store first
                 if (fast) bstore1(not_sentinel(hnew), rs_hs, xo); else bstore1_sc1(not_sentinel(hnew), rs_hs, xo);
             }
             if (real) {
@@ -778,6 +781,12 @@ __global__ __launch_bounds__(1024, 4) void gru_fwd_team_kernel(GruArgs a)
             if (BF && p_hp16) __builtin_amdgcn_raw_buffer_store_b16(to_bf16(hprev), rs_hp16, (int)((rix * D + j) * 2u), 0, 0);
             else if (p_hpw) bstore1(hprev, rs_hpw, (rix * D + j) * 4u);
             }
+        }
+        // exchange ring: the slot that held iteration p - 2 is dead behind the team barrier above; the team's last K-split wave (T = 2: one
+        // that sits out the gate math) re-arms this workgroup's slice of it for iteration p + 2 (gru_dev.h xch_rearm).  The first two
+        // re-arms would hit slots the launcher armed.
+        if constexpr (RING) {
+            if (wk == KS - 1 && p >= 2 && p + 2 < p_stop) xch_rearm<1>(rs_hs, (p + 2) & (kGruRing - 1), row0, ht * 4, lane, B, D, fast);
         }
         len_a = len2; len_g = len2g; ge_cur = ge2;
         TSTAMP(3);
@@ -1067,9 +1076,10 @@ __global__ __launch_bounds__(256, 2) void gru_bwd_kernel(GruArgs a)
 // per SIMD) whose first NB pieces are in flight before the MFMAs start.  A job with dh0 (decoder layers) gets the
 // tail item p = -1: dh0 = carry + dgh_0 R.  Teams synchronise through monotonic LDS counters, never s_barrier.
 constexpr int kBwdTeamLdsBytes = (4 * 24 * 256 + 16 * 256 + 64) * 4 + 64;      // dynamic LDS of gru_bwd_team_kernel: Wl | part | red | sync
-template <int NB, bool PIPE, int T, bool DIAG = false, bool BF = false, bool CMP = false>   // CMP: compact external arrays / phantom rows (GruArgs::rowmap, Bx); PIPE: several row blocks per workgroup; T teams of 16 / T waves; BF: bf16 operands (see the forward)
+template <int NB, bool PIPE, int T, bool DIAG = false, bool BF = false, bool CMP = false, bool RING = false>   // CMP: compact external arrays / phantom rows (GruArgs::rowmap, Bx); PIPE: several row blocks per workgroup; T teams of 16 / T waves; BF: bf16 operands (see the forward); RING: exchange ring (GruPlan::ring)
 __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
 {
+    static_assert(!RING || (!PIPE && !BF && !DIAG), "the exchange ring: fp32, one row block per workgroup");
     // diagnostic phase stamps (DIAG instantiation only): [0] top loads [1] probe + first pieces [2] operand stream + MFMAs
     // [3] barrier 1 [4] partial write + prefetch [5] barrier 2 [6] gate derivatives + stores
     unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = DIAG ? __builtin_amdgcn_s_memrealtime() : 0ULL;
@@ -1159,7 +1169,9 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
     const int* const perm = a.perm;                           // slot -> batch row of every external array (nullptr: identity)
     int* p_err = a.err;
     const int j_rev = J.reverse, ldg = a.ldg, ldh = a.ldh;
-    float* const xg = a.xbuf + (size_t)tm.jb * S * B * (3 * D) / (BF ? 2 : 1);       // this job's exchange buffer (tiled, sentinel-filled)
+    // exchange ring (gru_dev.h): the value of iteration `done` (steps run downwards; the count runs up) in slot done % kGruRing of min(S, kGruRing)
+    constexpr bool ring = RING;
+    float* const xg = a.xbuf + (size_t)tm.jb * (ring ? min(S, kGruRing) : S) * B * (3 * D) / (BF ? 2 : 1);       // this job's exchange buffer (tiled, sentinel-filled)
     const unsigned long long pa = (unsigned long long)xg;
     const i32x4 srd = {(int)(unsigned)(pa & 0xffffffffULL), (int)(unsigned)((pa >> 32) & 0xffffULL), -1, 0x00020000};
     float sb_r = 0.f, sb_u = 0.f, sb_n = 0.f, sb_nr = 0.f;
@@ -1179,7 +1191,7 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
     const __amdgpu_buffer_rsrc_t rs_dgh16 = make_rsrc(reinterpret_cast<const float*>(p_dgh16 ? p_dgh16 : reinterpret_cast<unsigned short*>(p_dghw)));
     auto a_offset = [&](int p, int row0, int len_a) -> unsigned {      // byte offset of this lane's first piece of dgh_{p+1}
         if constexpr (BF) return xch_lane_offset(pos_map(p + 1, len_a, j_rev), row0, wk * (WKB / 8), n, kh, B, 3 * D / 2);
-        return xch_lane_offset(pos_map(p + 1, len_a, j_rev), row0, wk * (WKB / 4), n, kh, B, 3 * D);
+        return xch_lane_offset(ring ? ((done - 1) & (kGruRing - 1)) : pos_map(p + 1, len_a, j_rev), row0, wk * (WKB / 4), n, kh, B, 3 * D);
     };
     auto issue_piece = [&](int piece, u32x4 (&dst)[PQ], unsigned vo) __attribute__((always_inline)) {
         asm_issue6x(dst, vo, srd, 6144 * piece, 6144 * piece + 4096);       // a piece = 96 floats (BF: 192 bf16) of K = 24 chunks of 256 B
@@ -1348,7 +1360,7 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
                 // start signal (heuristic): lane l reads the last element producer l&31 stores for the team's last row
                 const int len_p = PIPE ? (j_rev ? p_lens[row0 + 15] : 0) : len_p0;      // (one row block: fetched once, before the loop)
                 const float* pp = BF ? xg + (xch16_index(pos_map(p + 1, len_p, j_rev), row0 + 15, (ln_l & 31) * 48 + 47, B, 3 * D) >> 1)      // (the high half of its dword)
-                                     : xg + xch_index(pos_map(p + 1, len_p, j_rev), row0 + 15, (ln_l & 31) * 48 + 47, B, 3 * D);
+                                     : xg + xch_index(ring ? ((done - 1) & (kGruRing - 1)) : pos_map(p + 1, len_p, j_rev), row0 + 15, (ln_l & 31) * 48 + 47, B, 3 * D);
                 for (;;) {
                     unsigned v = 0u;
                     if (ln_l < 32) v = load4_sc1(pp);              // 32 cache lines per poll: half the wave stays out of it
@@ -1419,7 +1431,7 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
                 }
             } else {   // exchanged stores first (tiled buffer, gate-major: gate g of this unit sits 4 chunks = 1 KB after gate g - 1)
                 const float x0 = not_sentinel(dr), x1 = not_sentinel(du), x2 = not_sentinel(dn * r_);
-                const unsigned o0 = xch_index(gpos, grow, ht * 48 + gn_l, B, 3 * D) * 4u;
+                const unsigned o0 = xch_index(ring ? (done & (kGruRing - 1)) : gpos, grow, ht * 48 + gn_l, B, 3 * D) * 4u;
                 if (fast) { bstore1(x0, rs_dgh, o0); bstore1(x1, rs_dgh, o0 + 1024u); bstore1(x2, rs_dgh, o0 + 2048u); }
                 else { bstore1_sc1(x0, rs_dgh, o0); bstore1_sc1(x1, rs_dgh, o0 + 1024u); bstore1_sc1(x2, rs_dgh, o0 + 2048u); }
             }
@@ -1449,6 +1461,12 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_team_kernel(GruArgs a)
             if (real || (dgi_by_pos && inb)) bstore3(dr, du, dn, rs_dgi, orow_i);
             }
             sb_r += dr; sb_u += du; sb_n += dn; sb_nr += dn * r_;
+        }
+        // exchange ring: the slot that held iteration done - 2 is dead behind the team barrier above; the team's last K-split wave (T = 2: one
+        // that sits out the gate math) re-arms this workgroup's slice of it for iteration done + 2, i.e. step p - 2 (gru_dev.h xch_rearm).
+        // Issued here, outside the hand-counted piece stream; the next pass's counted waits cover it (it is older than every piece).
+        if constexpr (RING) {
+            if (wk == KS - 1 && done >= 2 && p >= 2) xch_rearm<3>(rs_dgh, (done + 2) & (kGruRing - 1), row0, ht * 12, lane, B, 3 * D, fast);
         }
         len_a = len2; len_g = len2g; ge_cur = ge2;
         BSTAMP(6);
@@ -1636,9 +1654,13 @@ static hipError_t prepare_exchange(hipStream_t st, const GruArgs& a, bool fwd, c
         return hipGetLastError();
     }
     if (team) {       // team kernels exchange through the tiled scratch buffer: one linear fill over every job's part
-        const size_t n16 = (size_t)a.njobs * rows * width / 4;             // (bf16 mode, backward: the exchange holds 16-bit values)
-        hipLaunchKernelGGL(gru_prepare_kernel, dim3(2048), dim3(256), 0, st, a.counters, kGruSyncWords,
-                           reinterpret_cast<uint4*>(a.xbuf), bf ? n16 / 2 : n16);
+        // (exchange ring: min(S, ring) slots per job at the front of the scratch, which the producers re-arm themselves -- a fill of a few MB)
+        const size_t slots = p.ring ? (size_t)std::min(a.S, p.ring) : (size_t)a.S;
+        size_t n16 = (size_t)a.njobs * slots * Bg * width / 4;             // (bf16 mode, backward: the exchange holds 16-bit values)
+        if (bf) n16 /= 2;
+        const size_t blocks = (std::max(n16, (size_t)kGruSyncWords) + 255) / 256;
+        hipLaunchKernelGGL(gru_prepare_kernel, dim3((unsigned)std::min<size_t>(blocks, 2048)), dim3(256), 0, st, a.counters, kGruSyncWords,
+                           reinterpret_cast<uint4*>(a.xbuf), n16);
         return hipGetLastError();
     }
     float* base0 = fwd ? a.job[0].hs : a.job[0].dgh;
@@ -1727,6 +1749,8 @@ GruPlan gru_plan(const GruArgs& a, bool fwd, bool persistent)
     p.T = T; p.C = C; p.cpj = C / a.njobs;
     p.pipe = a.njobs * (p.Bg / (16 * T)) > C;
     p.diag = kDiagBuild && (fwd ? a.ablate != 0 : (a.ablate & 128) != 0);
+    // the exchange ring: the fp32 kernels with one row block per workgroup (the pipelined and the bf16 forms keep one slot per position)
+    p.ring = (a.ring && p.form == GruForm::team && !p.pipe && !a.bf16 && !p.diag) ? kGruRing : 0;
     return p;
 }
 
@@ -1760,10 +1784,13 @@ hipError_t gru_forward(hipStream_t st, const GruArgs& a, bool persistent)
     case GruForm::team: {
         // D = 512: independent 16-row teams sharing one LDS-resident weight slice per CU, the row blocks of a workgroup
         // interleaved item by item (team_geometry picks 4 teams x 4 waves or 2 teams x 8 waves)
-        return team_dispatch(p.T, [&](auto T, auto PIPE, auto BF, auto CMP) {
-            if constexpr (kDiagBuild && T == 4 && !BF && !CMP) if (p.diag) return launch_team(st, gru_fwd_team_kernel<true, PIPE, 4>, a, kFwdTeamLdsBytes, p.C);
-            return launch_team(st, gru_fwd_team_kernel<false, PIPE, T, BF, CMP>, a, kFwdTeamLdsBytes, p.C);
-        }, p.pipe, a.bf16 && !p.diag, a.rowmap != nullptr);
+        return team_dispatch(p.T, [&](auto T, auto PIPE, auto BF, auto CMP, auto RING) {
+            if constexpr (RING && (PIPE || BF)) return hipErrorInvalidValue;      // (gru_plan gives these forms no ring)
+            else {
+            if constexpr (kDiagBuild && T == 4 && !BF && !CMP && !RING) if (p.diag) return launch_team(st, gru_fwd_team_kernel<true, PIPE, 4>, a, kFwdTeamLdsBytes, p.C);
+            return launch_team(st, gru_fwd_team_kernel<false, PIPE, T, BF, CMP, RING>, a, kFwdTeamLdsBytes, p.C);
+            }
+        }, p.pipe, a.bf16 && !p.diag, a.rowmap != nullptr, p.ring != 0);
     }
     case GruForm::item:
         e = resident(gru_fwd_item_kernel, 256, 0, grid); if (e != hipSuccess) return e;
@@ -1789,10 +1816,13 @@ hipError_t gru_backward(hipStream_t st, const GruArgs& a, bool persistent)
         return gru_bwd_rs_launch(st, a, p);
     case GruForm::team: {
         e = prepare_exchange(st, a, false, p); if (e != hipSuccess) return e;
-        return team_dispatch(p.T, [&](auto T, auto PIPE, auto BF, auto CMP) {
-            if constexpr (kDiagBuild && !BF && !CMP) if (p.diag) return launch_team(st, gru_bwd_team_kernel<2, PIPE, T, true>, a, kBwdTeamLdsBytes, p.C);
-            return launch_team(st, gru_bwd_team_kernel<2, PIPE, T, false, BF, CMP>, a, kBwdTeamLdsBytes, p.C);
-        }, p.pipe, a.bf16 && !p.diag, a.rowmap != nullptr);
+        return team_dispatch(p.T, [&](auto T, auto PIPE, auto BF, auto CMP, auto RING) {
+            if constexpr (RING && (PIPE || BF)) return hipErrorInvalidValue;      // (gru_plan gives these forms no ring)
+            else {
+            if constexpr (kDiagBuild && !BF && !CMP && !RING) if (p.diag) return launch_team(st, gru_bwd_team_kernel<2, PIPE, T, true>, a, kBwdTeamLdsBytes, p.C);
+            return launch_team(st, gru_bwd_team_kernel<2, PIPE, T, false, BF, CMP, RING>, a, kBwdTeamLdsBytes, p.C);
+            }
+        }, p.pipe, a.bf16 && !p.diag, a.rowmap != nullptr, p.ring != 0);
     }
     case GruForm::persistent:
         e = prepare_exchange(st, a, false, p); if (e != hipSuccess) return e;

@@ -369,6 +369,37 @@ __device__ __forceinline__ unsigned xch_lane_offset(int pos, int row0, int kc0, 
     return ((((unsigned)pos * (unsigned)(B >> 4) + (unsigned)(row0 >> 4)) * (unsigned)(K >> 2) + (unsigned)(kc0 + kh)) * 16u + (unsigned)n) * 16u;
 }
 
+// ---- exchange ring (fp32 team kernels with one row block per workgroup; GruPlan::ring = kGruRing slots).  A consumer of iteration q
+// reads only what iteration q - 1 produced, so the scratch need not be as long as the sequence: the value a team produces in its
+// iteration q (its running step count -- NOT pos_map(...), which differs per row in a reversed ragged job; producer and consumer of a
+// value agree on the iteration) lives in slot q % 4, the layout inside a slot as above with `pos` = the slot.  Data stays the flag
+// (sentinel, probe, running-max check, bounded spins: all unchanged); the launcher arms min(S, 4) slots and the producers re-arm
+// them: in iteration p, behind the team barrier that follows the MFMA pass, ONE wave of the team stores the sentinel over the
+// workgroup's own slice (its 16 or 48 columns x the team's 16 rows: 1 or 3 KB, contiguous) of slot (p + 2) % 4, the slot that held
+// iteration p - 2, unless the row block has no iteration p + 2 that stores.
+//   Dead: at that barrier every wave of this team holds its whole operand of iteration p, i.e. the iteration p - 1 values of all 32
+// producers; a producer stores those only behind its own team barrier of iteration p - 1, where all its waves' loads of iteration
+// p - 2 have returned.  Nobody reads slot (p - 2) % 4 any more.
+//   Armed in time: the slot next takes data in iteration p + 2 and is polled from p + 3 on.  The re-arming wave waits for its operand
+// loads of iteration p + 1 -- vmcnt counts stores too and retires in issue order, so the re-arm is acknowledged by L2 by then --
+// before the team barrier of p + 1, behind which the gate threads store the iteration p + 1 values; a consumer that has seen those
+// (it cannot poll the slot earlier) therefore sees the re-arm, and this workgroup's own data stores of p + 2 come after it.  With 3
+// slots the re-armed slot would take data one iteration later, ordered against nothing but a new vmcnt(0) on the gate path.
+// N16 stores of 16 bytes per lane, 1 KB apart, from chunk kc0 of the team's rows at row0; sc1 off the same-XCD fast path like the data.
+template <int N16>
+__device__ __forceinline__ void xch_rearm(__amdgpu_buffer_rsrc_t rs, int slot, int row0, int kc0, int lane, int B, int K, bool fast)
+{
+    const unsigned off = ((((unsigned)slot * (unsigned)(B >> 4) + (unsigned)(row0 >> 4)) * (unsigned)(K >> 2) + (unsigned)kc0) * 16u + (unsigned)lane) * 16u;
+    const u32x4 s4 = {kSentinel, kSentinel, kSentinel, kSentinel};
+    if (fast) {
+#pragma unroll
+        for (int i = 0; i < N16; ++i) __builtin_amdgcn_raw_buffer_store_b128(s4, rs, (int)(off + 1024u * i), 0, 0);
+    } else {
+#pragma unroll
+        for (int i = 0; i < N16; ++i) __builtin_amdgcn_raw_buffer_store_b128(s4, rs, (int)(off + 1024u * i), 0, 16);
+    }
+}
+
 __device__ __forceinline__ void team_barrier(unsigned* word, unsigned target)
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                       // this wave's LDS traffic is done

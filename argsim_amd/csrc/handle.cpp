@@ -253,6 +253,7 @@ int avae_set_option(avae_handle h, const char* key, int value)
     if (!strcmp(key, "dyn_split")) { h->dyn_split = value != 0; return 0; }
     if (!strcmp(key, "shared_device")) { h->shared_device = value != 0; return 0; }
     if (!strcmp(key, "gru_spec")) { h->gru_spec = value; return 0; }
+    if (!strcmp(key, "gru_ring")) { h->gru_ring = value != 0; return 0; }
     if (!strcmp(key, "bf16_nt8")) { h->bf16_nt8 = value != 0; return 0; }
     if (!strcmp(key, "logits16")) { h->logits16 = value != 0; return 0; }
     if (!strcmp(key, "bf16_direct")) { h->bf16_direct = value != 0; return 0; }

@@ -288,26 +288,27 @@ static void gru_shape(const int64_t* i, GruArgs& a)
 }
 static void gru_plan_out(const GruArgs& a, const GruPlan& p, int64_t out[10])
 {
-    const int64_t v[10] = {(int64_t)p.form, p.T, p.C, p.cpj, p.Bg, p.pipe, a.G, a.rows_per_group, (int64_t)gru_bwd_rs_xbuf_floats(a.njobs, p.Bg), 0};
+    const int64_t v[10] = {(int64_t)p.form, p.T, p.C, p.cpj, p.Bg, p.pipe, a.G, a.rows_per_group, (int64_t)gru_bwd_rs_xbuf_floats(a.njobs, p.Bg), p.ring};
     std::copy(v, v + 10, out);
 }
 // test hook: gru_plan() for one launch shape (i: gru_shape above; a static aligned dummy stands in for the exchange scratch where xbuf_floats > 0).
 // out = form (GruForm: 0 stepwise, 1 persistent, 2 item, 3 team, 4 team_rs), T, C, cpj, Bg, pipe, the G and rows_per_group used, the floats of
-// exchange scratch the reduce-scatter backward needs for the shape (gru_bwd_rs_xbuf_floats), 0.  Host arithmetic only: callable without a GPU.
+// exchange scratch the reduce-scatter backward needs for the shape (gru_bwd_rs_xbuf_floats), the depth of the exchange ring (GruPlan::ring, planned with
+// GruArgs::ring = 1; 0: one slot per position).  Host arithmetic only: callable without a GPU.
 int avae_debug_gru_plan(const int64_t* i, int fwd, int persistent, int64_t out[10])
 {
     if (!i || !out) return 1;
     alignas(16) static float dummy[4] = {0.f, 0.f, 0.f, 0.f};
     GruArgs a{};
     gru_shape(i, a);
-    a.xbuf = a.xbuf_floats > 0 ? dummy : nullptr;
+    a.xbuf = a.xbuf_floats > 0 ? dummy : nullptr; a.ring = 1;
     gru_plan_out(a, gru_plan(a, fwd != 0, persistent != 0), out);
     return 0;
 }
 // test hook: ONE gru_forward / gru_backward call on caller-owned device buffers, on the handle's stream -- plan, operand check, residency check and
 // exchange preparation as in the product.  i: gru_shape above, then stagger, force_slow, sv16, spec, then (reverse, dgi_by_pos) per job; jobs: 19
 // pointers per job, GruJob's pointer fields in their order (gi, gi_rows, R, bR, h0, hs, sv, hp, hs16, hp16, dh_out, dgi, dgh, dgi16, dgh16, dh0,
-// carry, dbW, dbR); shared: lens, slens, perm, rowmap, xbuf.  counters, err and stamps are the handle's, ablate is 0, and only whole-sequence launches
+// carry, dbW, dbR); shared: lens, slens, perm, rowmap, xbuf.  counters, err and stamps are the handle's, ring is the handle's option gru_ring, ablate is 0, and only whole-sequence launches
 // (p_begin = 0, p_end = S: all the product launches) are taken.  A launcher's refusal comes back as a non-zero return with the hipError_t text in
 // avae_last_error.  Synchronises, then reads (and clears) the device error word: an exchange time-out is a non-zero return too.  plan_out: as
 // avae_debug_gru_plan's out, the plan that ran.
@@ -332,6 +333,7 @@ int avae_debug_gru(avae_handle h, int fwd, int persistent, const int64_t* i, voi
     a.lens = static_cast<const int*>(shared[0]); a.slens = static_cast<const int*>(shared[1]); a.perm = static_cast<const int*>(shared[2]);
     a.rowmap = static_cast<const int*>(shared[3]); a.xbuf = static_cast<float*>(shared[4]);
     a.counters = h->counters; a.err = h->errw; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.ablate = 0;
+    a.ring = h->gru_ring;
     gru_plan_out(a, gru_plan(a, fwd != 0, persistent != 0), plan_out);
     AV_CHECK(hipSetDevice(h->device));
     AV_GRU(fwd ? gru_forward(h->stream, a, persistent != 0) : gru_backward(h->stream, a, persistent != 0));

@@ -139,15 +139,18 @@ struct GruArgs {
     int bf16;             // 1 (compute_dtype 1): the team kernels round both operands of the recurrent product to bf16
     int spec;             // 1 (team kernels, one row block per workgroup): few rows are alive per step -- a consumer loads its operand at once, without a probe round trip in front (speed only)
     int bwd_rs;           // 1: the backward runs the reduce-scatter team kernel (gru_rs.hip) where the team geometry applies and xbuf holds its ring
+    int ring;             // 1: the team kernels exchange through a ring of slots where the plan allows it (GruPlan::ring; gru_dev.h "exchange ring"), 0: one slot per position
     int ablate;           // timing experiments only: 1 no MFMA/A loads, 2 no gate-phase loads, 4 no saves, 8 cheap activations, 16 no sync
 };
 // The kernel form of a launch, from its shape alone (geometry, Bx, xbuf / xbuf_floats, p_begin / p_end, bf16, bwd_rs, ablate,
 // item_pipeline): callers plan before they attach slens / perm / rowmap and the job pointers.  gi_rows, slens / perm: team forms only.
+constexpr int kGruRing = 4;       // depth of the team kernels' exchange ring (gru_dev.h "exchange ring": why not 3)
 enum class GruForm { stepwise, persistent, item, team, team_rs };     // item: forward only (gru_fwd_item_kernel); team_rs: backward only (gru_rs.hip)
 struct GruPlan {
     GruForm form;
     int T, C, cpj, Bg;      // team forms: T teams of 16 rows per 16 T-row block, C workgroups per hidden tile (cpj per job); Bg = max(B, Bx)
     bool pipe, diag;        // pipe: several row blocks per workgroup; diag: the DIAG build's timing instantiation (fp32, padded layout)
+    int ring;               // slots of the exchange ring (kGruRing; the slot of a value = the iteration that made it, mod ring), 0: one slot per position
     bool team() const { return form == GruForm::team || form == GruForm::team_rs; }
     bool full() const { return team() && !diag; }      // a team form that honours the 16-bit operands, rowmap and phantom rows too
 };

@@ -365,6 +365,7 @@ void gru_common(avae_ctx* h, const Ws& w, GruArgs& a, int njobs, int S, int B, i
     a.p_begin = 0; a.p_end = S; a.counters = h->counters; a.err = h->errw; a.ablate = h->gru_ablate; a.force_slow = h->gru_force_slow;
     a.bf16 = h->cfg.compute_dtype == 1 && h->gru_bf16; a.stagger = h->gru_stagger; a.item_pipeline = h->gru_item;
     a.xbuf = w.xbuf; a.xbuf_floats = w.xbuf_floats; a.stamps = reinterpret_cast<unsigned long long*>(h->errw + 16); a.bwd_rs = h->bwd_rs != 0;
+    a.ring = h->gru_ring;
 }
 // Row orders of this call (one launch, after prep_ids has the lengths): for every GRU launch shape of the step whose team
 // kernels can skip padding, the batch rows sorted by length and dealt over the workgroups.  with_dec: the decoder runs too.
