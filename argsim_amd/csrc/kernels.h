@@ -372,8 +372,8 @@ size_t moments_ws_bytes(int N, int dim);
 hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, void* ws);
 
 // ---------------------------------------------------------------- linear probes of latent rows (probe.hip)
-// P independent L2 logistic regressions over x (N, dim) in lockstep (contract: include/argsim_vae.h, avae_probe_fit).  The host loop
-// (probing.cpp) strings these launches together; every buffer is workspace laid out by the caller.
+// P independent L2 (avae_probe_fit) or L1 (avae_probe_fit_l1) logistic regressions over x (N, dim) in lockstep (contract:
+// include/argsim_vae.h).  The host loops (probing.cpp) string these launches together; every buffer is workspace laid out by the caller.
 constexpr int kProbeTile = 32;        // problems per tile: P is padded to it with zero-cost problems
 constexpr int kProbeAlphas = 7;       // step lengths one probe_trial launch evaluates
 constexpr int kProbeMaxParts = 256;
@@ -389,6 +389,9 @@ struct ProbeWs {
     double* tp;                       // (parts, kProbeAlphas, Ppad): the parts' trial loss sums
     int* is; float* fs; double* ds;   // (Ppad, 8) each: per-problem state words (probe.hip)
     int N, dim, LD, Ppad, parts, chunk;
+    // the L1 fit alone (null in the L2 fit):
+    float *Yv, *Hd, *Hy;              // (Ppad, LD), one run: the FISTA point y, H d of the last accepted d, H y
+    float* xs;                        // (N, dim): x with the rows that are not finite zeroed
 };
 struct ProbeAlphas { int n, last; float a[kProbeAlphas]; };      // a trial round: its step lengths; last: no round follows
 hipError_t probe_prepare(hipStream_t st, const ProbeWs& b, const float* s, int P);                 // state of a fresh fit, s (P, N) -> sT
@@ -396,6 +399,12 @@ hipError_t probe_pass(hipStream_t st, const ProbeWs& b, const float* x, int mode
 hipError_t probe_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_cg, float tol, const ProbeAlphas& al);
 hipError_t probe_trial(hipStream_t st, const ProbeWs& b, const ProbeAlphas& al);
 hipError_t probe_finish(hipStream_t st, const ProbeWs& b, int P, float* w, float* stats);
+// the L1 fit (avae_probe_fit_l1) runs probe_pass, probe_trial and probe_finish as they are, on b.xs, with Dv the FISTA candidate and Pv
+// the accepted step; its own launches: the state of a fresh fit (probe_prepare + xs), the curvature column sums into gp, and the
+// per-problem vector kernel (phase 0 after GRAD, 3 after probe_l1_curv, 1 after the k-th HV pass, 2 after trial round k)
+hipError_t probe_l1_prepare(hipStream_t st, const ProbeWs& b, const float* x, const float* s, int P);
+hipError_t probe_l1_curv(hipStream_t st, const ProbeWs& b);
+hipError_t probe_l1_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_inner, float tol, const ProbeAlphas& al);
 // out (n, P) = x~ w^T; W: (Ppad, LD) floats of workspace
 hipError_t probe_decision(hipStream_t st, const ProbePlan& p, const float* x, int n, int dim, const float* w, int P, float* W, float* out);
 

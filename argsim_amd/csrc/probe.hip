@@ -21,6 +21,8 @@
 // A problem is one column of every MFMA tile and one column of every panel: its arithmetic does not see the other columns, and the
 // row parts are a function of (N, probe_chunk) alone, so its bits do not depend on P, on its position or on its companions.  A
 // launch whose 32 problems are all idle returns at once; an idle problem in a busy tile is computed and ignored.  No float atomics.
+// The L1 fit (avae_probe_fit_l1: proximal Newton, the inner problem by FISTA) runs the same passes and trial kernel with its own
+// per-problem kernel probe_l1_vec, the curvature column sums probe_l1_curv and the row check probe_l1_rows, at the end of this file's kernels.
 #include "kernels.h"
 #include "mfma_tile.h"
 
@@ -446,6 +448,340 @@ __global__ __launch_bounds__(256) void probe_trial_kernel(ProbeTrialArgs a)
         }
 }
 
+// ---------------------------------------------------------------- the L1 probes (avae_probe_fit_l1)
+// The same passes, another per-problem method: proximal Newton, the inner problem by FISTA.  Of the L2 fit's vectors Dv holds the
+// FISTA candidate d+ (what the HV pass multiplies), Pv the last accepted d (what the PANEL pass multiplies), Rv is unused.
+enum { F_L = 3, F_T = 4, F_RHO = 5, F_MX = 6 };      // fs: L, the momentum t, L / (largest curvature column sum) of the last inner solve, that sum
+enum { D_W1 = 0, D_DELTA = 1 };                      // ds: |w|_1, g.d + |w + d|_1 - |w|_1 (D_PHI0 as in the L2 fit)
+
+// sgn(a) max(|a| - t, 0); what it cuts off is an exact +0.0f
+__device__ __forceinline__ float soft_thr(float a, float t)
+{
+    const float m = fabsf(a) - t;
+    return m > 0.f ? copysignf(m, a) : 0.f;
+}
+
+// |v_j| of the minimum-norm subgradient: |g + sgn(w)| where w != 0, max(|g| - 1, 0) where w = 0 (a NaN stays a NaN)
+__device__ __forceinline__ float subgrad_abs(float g, float w)
+{
+    if (w != 0.f) return fabsf(g + (w > 0.f ? 1.f : -1.f));
+    const float e = fabsf(g) - 1.f;
+    return e <= 0.f ? 0.f : e;
+}
+
+// the largest of one float per thread over the 256 threads (values >= 0, fmaxf: a NaN is dropped); every thread gets it
+__device__ __forceinline__ float block_max(float v, double* s)
+{
+    const int tid = threadIdx.x;
+    s[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s[tid] = fmax(s[tid], s[tid + o]);
+        __syncthreads();
+    }
+    const float r = (float)s[0];
+    __syncthreads();
+    return r;
+}
+
+// block_sum of three values behind one set of barriers (the same tree for each)
+__device__ __forceinline__ void block_sum3(double& a, double& b, double& c, double (*s)[256])
+{
+    const int tid = threadIdx.x;
+    s[0][tid] = a; s[1][tid] = b; s[2][tid] = c;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { s[0][tid] += s[0][tid + o]; s[1][tid] += s[1][tid + o]; s[2][tid] += s[2][tid + o]; }
+        __syncthreads();
+    }
+    a = s[0][0]; b = s[1][0]; c = s[2][0];
+    __syncthreads();
+}
+
+// merge_parts with 16 parts' loads in flight at once: the same additions in the same order, so the same bits (the strided loads of
+// one element are independent, only the additions form a chain; the L2 fit's kernel keeps its own merge)
+__device__ __forceinline__ float merge_parts_deep(const ProbeWs& b, int p, int d)
+{
+    const float* src = b.gp + (size_t)d * b.Ppad + p;
+    const size_t step = (size_t)b.LD * b.Ppad;
+    float s = 0.f;
+    int q = 0;
+    for (; q + 16 <= b.parts; q += 16) {
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = src[(size_t)(q + i) * step];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s += v[i];
+    }
+    if (q < b.parts) {
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = q + i < b.parts ? src[(size_t)(q + i) * step] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (q + i < b.parts) s += v[i];
+    }
+    return s;
+}
+
+// xs (N, dim) <- x with every row that holds a value that is not finite replaced by zeros, and every problem with a nonzero cost on
+// such a row ended with status 2 before the first pass: x~^T (tile) would carry the row's NaN into every problem of the call, 0 cost
+// or not.  One wave per row.
+__global__ __launch_bounds__(256) void probe_l1_rows_kernel(const float* __restrict__ x, float* __restrict__ xs, const float* __restrict__ sT,
+                                                            int* __restrict__ is, int N, int dim, int Ppad)
+{
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const float4* src = reinterpret_cast<const float4*>(x + (size_t)row * dim);
+    float4* dst = reinterpret_cast<float4*>(xs + (size_t)row * dim);
+    const int nv = dim >> 2;                  // <= 256: 4 float4 per lane
+    float4 v[4];
+    int bad = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        v[j] = i < nv ? src[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float t = (v[j].x - v[j].x) + (v[j].y - v[j].y) + (v[j].z - v[j].z) + (v[j].w - v[j].w);
+        bad |= !(t == 0.f);
+    }
+    const bool any = __ballot(bad) != 0ull;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = lane + 64 * j;
+        if (i < nv) dst[i] = any ? make_float4(0.f, 0.f, 0.f, 0.f) : v[j];
+    }
+    if (any)
+        for (int p = lane; p < Ppad; p += 64)
+            if (sT[(size_t)row * Ppad + p] != 0.f) {          // (every writer stores the same words)
+                is[(size_t)p * 8 + I_STATUS] = 2; is[(size_t)p * 8 + I_FROZEN] = 1; is[(size_t)p * 8 + I_ALIVE] = 0;
+            }
+}
+
+struct ProbeCurvArgs {
+    const float* x; const float* D;      // (N, dim), (N, Ppad)
+    float* gp;                           // (parts, LD, Ppad)
+    const int* flags;
+    int N, dim, LD, Ppad, parts, chunk;
+};
+
+// the diagonal of H = X~^T D X~ per part: gp[part][j][p] = sum over the part's rows of D_ip x_ij^2, row j = dim the sum of D alone.
+// grid = (parts x problem tiles, dim / 32 rounded up); thread (jg, pl) owns dims 32 blockIdx.y + 4 jg .. + 3 of problem p0 + pl and
+// adds the rows in row order.
+__global__ __launch_bounds__(256) void probe_l1_curv_kernel(ProbeCurvArgs a)
+{
+    const int tid = threadIdx.x, pl = tid & 31, jg = tid >> 5;
+    const int part = blockIdx.x % a.parts, p0 = (blockIdx.x / a.parts) * kTP, prob = p0 + pl;
+    const int busy = tid < kTP ? a.flags[(size_t)(p0 + tid) * 8 + I_CG] : 0;
+    if (!__syncthreads_or(busy)) return;
+    const long long c_begin = (long long)part * a.chunk;
+    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    const int j = blockIdx.y * 32 + jg * 4;
+    const bool jok = j < a.dim, bias = blockIdx.y == 0 && jg == 0;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f}, accb = 0.f;
+    const float* xj = a.x + (jok ? j : 0);
+#pragma unroll 4
+    for (int row = (int)c_begin; row < c_end; ++row) {
+        const float Dv = a.D[(size_t)row * a.Ppad + prob];
+        const float4 xv = *reinterpret_cast<const float4*>(xj + (size_t)row * a.dim);
+        acc[0] = fmaf(Dv * xv.x, xv.x, acc[0]); acc[1] = fmaf(Dv * xv.y, xv.y, acc[1]);
+        acc[2] = fmaf(Dv * xv.z, xv.z, acc[2]); acc[3] = fmaf(Dv * xv.w, xv.w, acc[3]);
+        accb += Dv;
+    }
+    float* gp = a.gp + (size_t)part * a.LD * a.Ppad;
+    if (jok)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gp[(size_t)(j + e) * a.Ppad + prob] = acc[e];
+    if (bias) gp[(size_t)a.dim * a.Ppad + prob] = accb;
+}
+
+// PHASE 0: after a GRAD pass -- F, g, v, the stop rule.  PHASE 3: after the curvature reduction -- L and the first FISTA candidate.
+// PHASE 1: after the k-th HV pass -- the accept / reject of L, the momentum with restart, v_q, the next candidate.  PHASE 2: after
+// trial round k -- the composite Armijo test of its step lengths.
+template <int PHASE>
+__global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int max_newton, int max_inner, float tol, ProbeAlphas al)
+{
+    __shared__ double s_sum3[3][256];
+    double* s_sum = s_sum3[0];
+    __shared__ float s_alpha;
+    const int p = blockIdx.x, tid = threadIdx.x, n = b.dim + 1;
+    int* is = b.is + (size_t)p * 8;
+    float* fs = b.fs + (size_t)p * 8;
+    double* ds = b.ds + (size_t)p * 8;
+    float* W = b.W + (size_t)p * b.LD;
+    float* G = b.G + (size_t)p * b.LD;
+    float* Dv = b.Dv + (size_t)p * b.LD;
+    float* Pv = b.Pv + (size_t)p * b.LD;
+    float* Yv = b.Yv + (size_t)p * b.LD;
+    float* Hd = b.Hd + (size_t)p * b.LD;
+    float* Hy = b.Hy + (size_t)p * b.LD;
+
+    if (PHASE == 0) {
+        if (is[I_FROZEN]) return;
+        const int it = is[I_ITER];
+        const float v0_kept = fs[F_G0];
+        double w1 = 0.0, vn = 0.0;
+        for (int d = tid; d < n; d += 256) {
+            const float w = W[d], gv = merge_parts_deep(b, p, d);
+            G[d] = gv;
+            w1 += (double)fabsf(w); vn += (double)subgrad_abs(gv, w);
+        }
+        w1 = block_sum(w1, s_sum); vn = block_sum(vn, s_sum);
+        float loss = 0.f;
+        for (int q = 0; q < b.parts; ++q) loss += b.lp[(size_t)q * b.Ppad + p];
+        const float f = (float)w1 + loss, vnorm = (float)vn;
+        const float v0 = it == 0 ? vnorm : v0_kept;
+        int status = -1;
+        if (!(f - f == 0.f) || !(vnorm - vnorm == 0.f)) status = 2;
+        else if (vnorm <= tol * v0) status = 0;
+        else if (it >= max_newton) status = 1;
+        if (tid == 0) {
+            fs[F_F] = f; fs[F_GNORM] = vnorm; fs[F_G0] = v0;
+            if (status >= 0) { is[I_STATUS] = status; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            else { ds[D_W1] = w1; is[I_CG] = 1; }
+        }
+    } else if (PHASE == 3) {
+        if (!is[I_CG]) return;
+        const float rho = fs[F_RHO];
+        float mx = 0.f;
+        for (int d = tid; d < n; d += 256) mx = fmaxf(mx, merge_parts_deep(b, p, d));
+        mx = block_max(mx, s_sum);
+        // L starts at the largest diagonal entry of H (a lower bound of its largest eigenvalue; the backtracking doubles it), from the
+        // second inner solve on at half of what the last one ended with, relative to that entry
+        float L = mx;
+        if (rho > 2.f && rho - rho == 0.f) L = mx * (0.5f * rho);
+        if (!(L > 0.f) || !(L - L == 0.f)) {
+            if (tid == 0) { is[I_CG] = 0; is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            return;
+        }
+        const float iL = 1.f / L;
+        for (int d = tid; d < n; d += 256) {
+            const float w = W[d];
+            Pv[d] = 0.f; Yv[d] = 0.f; Hd[d] = 0.f; Hy[d] = 0.f;
+            Dv[d] = soft_thr(fmaf(-G[d], iL, w), iL) - w;
+        }
+        if (tid == 0) { fs[F_L] = L; fs[F_T] = 1.f; fs[F_MX] = mx; }
+    } else if (PHASE == 1) {
+        if (!is[I_CG]) return;
+        const float L = fs[F_L], t = fs[F_T], vnorm = fs[F_GNORM];
+        float hp[kVecPer];
+        double dHd = 0.0, dd = 0.0, rs = 0.0;
+#pragma unroll
+        for (int j = 0; j < kVecPer; ++j) {          // (a loop of loads alone: nothing stored between them, every element's in flight)
+            const int d = tid + 256 * j;
+            hp[j] = d < n ? merge_parts_deep(b, p, d) : 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < kVecPer; ++j) {
+            const int d = tid + 256 * j;
+            if (d < n) {
+                const float c = Dv[d], yv = Yv[d], del = c - yv;
+                dHd += (double)del * (double)(hp[j] - Hy[d]); dd += (double)del * del; rs += (double)(yv - c) * (double)(c - Pv[d]);
+            }
+        }
+        block_sum3(dHd, dd, rs, s_sum3);
+        bool bad = !finite_d(dHd) || !finite_d(dd);
+        // the backtracking test on the quadratic: q_s(d+) - q_s(y) - grad q_s(y).(d+ - y) = 1/2 (d+ - y).H (d+ - y) <= L/2 |d+ - y|^2
+        const bool accept = !bad && dHd <= (double)L * dd;
+        const bool last = k + 1 >= max_inner;
+        bool stop = last;
+        float Ln = L, tn = 1.f;
+        if (accept) {
+            double vq = 0.0;
+#pragma unroll
+            for (int j = 0; j < kVecPer; ++j) {
+                const int d = tid + 256 * j;
+                if (d < n) vq += (double)subgrad_abs(G[d] + hp[j], W[d] + Dv[d]);
+            }
+            vq = block_sum(vq, s_sum);
+            bad = !finite_d(vq);
+            stop = last || vq <= 0.1 * (double)vnorm;
+            const bool restart = rs > 0.0;          // the momentum points against the step just taken
+            tn = restart ? 1.f : 0.5f * (1.f + sqrtf(fmaf(4.f * t, t, 1.f)));
+            const float beta = restart ? 0.f : (t - 1.f) / tn, iL = 1.f / L;
+#pragma unroll
+            for (int j = 0; j < kVecPer; ++j) {
+                const int d = tid + 256 * j;
+                if (d < n) {
+                    const float c = Dv[d], w = W[d];
+                    const float yn = fmaf(beta, c - Pv[d], c), hyn = fmaf(beta, hp[j] - Hd[d], hp[j]);
+                    Pv[d] = c; Hd[d] = hp[j]; Yv[d] = yn; Hy[d] = hyn;
+                    if (!stop) Dv[d] = soft_thr(fmaf(-(G[d] + hyn), iL, w + yn), iL) - w;
+                }
+            }
+        } else if (!bad) {
+            // L doubles, the momentum falls back to the last accepted d; this launch was spent
+            Ln = 2.f * L;
+            const float iL = 1.f / Ln;
+#pragma unroll
+            for (int j = 0; j < kVecPer; ++j) {
+                const int d = tid + 256 * j;
+                if (d < n) {
+                    const float pd = Pv[d], hd = Hd[d], w = W[d];
+                    Yv[d] = pd; Hy[d] = hd;
+                    if (!stop) Dv[d] = soft_thr(fmaf(-(G[d] + hd), iL, w + pd), iL) - w;
+                }
+            }
+        }
+        if (bad) {
+            if (tid == 0) { is[I_CG] = 0; is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            return;
+        }
+        if (!stop) {
+            if (tid == 0) { fs[F_L] = Ln; fs[F_T] = tn; }
+            return;
+        }
+        // the step is Pv: what the Armijo test needs of it
+        double gtd = 0.0, w1d = 0.0;
+        for (int d = tid; d < n; d += 256) { const float pv = Pv[d]; gtd += (double)G[d] * pv; w1d += fabs((double)W[d] + (double)pv); }
+        gtd = block_sum(gtd, s_sum); w1d = block_sum(w1d, s_sum);
+        if (tid == 0) {
+            const double delta = gtd + (w1d - ds[D_W1]);
+            is[I_CG] = 0;
+            if (!finite_d(delta)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            else { ds[D_DELTA] = delta; is[I_LS] = 1; fs[F_RHO] = Ln / fs[F_MX]; }
+        }
+    } else {
+        if (!is[I_LS]) return;
+        double l1[kNA];
+#pragma unroll
+        for (int j = 0; j < kNA; ++j) {
+            l1[j] = 0.0;
+            if (j < al.n) {
+                const double a = al.a[j];
+                double part = 0.0;
+                for (int d = tid; d < n; d += 256) part += fabs((double)W[d] + a * (double)Pv[d]);
+                l1[j] = block_sum(part, s_sum);
+            }
+        }
+        if (tid == 0) {
+            // trial slot j of round k: its loss sum, the parts added in part order; slot 0 of round 0 is the step length 0
+            float take = -1.f; bool bad = false;
+#pragma unroll
+            for (int j = 0; j < kNA; ++j) {
+                if (j >= al.n || take >= 0.f || bad) break;
+                double Ls = 0.0;
+                for (int q = 0; q < b.parts; ++q) Ls += b.tp[((size_t)q * kNA + j) * b.Ppad + p];
+                if (k == 0 && j == 0) { ds[D_PHI0] = Ls; if (!finite_d(Ls)) bad = true; continue; }
+                if (!finite_d(Ls) || !finite_d(l1[j])) { bad = true; break; }
+                const double a = al.a[j];
+                const double lhs = (Ls - ds[D_PHI0]) + (l1[j] - ds[D_W1]);
+                if (lhs <= 0.01 * a * ds[D_DELTA]) take = al.a[j];
+            }
+            if (bad || (take < 0.f && al.last)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; is[I_LS] = 0; }
+            else if (take >= 0.f) { is[I_LS] = 0; is[I_ITER] += 1; }
+            s_alpha = bad ? -1.f : take;
+        }
+        __syncthreads();
+        const float a = s_alpha;
+        if (a > 0.f)
+            for (int d = tid; d < n; d += 256) {
+                const float nw = fmaf(a, Pv[d], W[d]);          // at a = 1 and d = 0 - w (the soft-threshold cut it off): exactly 0
+                W[d] = nw == 0.f ? 0.f : nw;
+            }
+    }
+}
+
 int pick_dt(int dim) { return dim <= 128 ? 1 : dim <= 256 ? 2 : dim <= 512 ? 4 : 8; }
 
 }  // namespace
@@ -532,6 +868,35 @@ hipError_t probe_trial(hipStream_t st, const ProbeWs& b, const ProbeAlphas& al)
 hipError_t probe_finish(hipStream_t st, const ProbeWs& b, int P, float* w, float* stats)
 {
     hipLaunchKernelGGL(probe_finish_kernel, dim3((unsigned)P), dim3(256), 0, st, b, w, stats);
+    return hipGetLastError();
+}
+
+// the state of a fresh L1 fit: that of the L2 fit, then b.xs <- x without the rows that are not finite
+hipError_t probe_l1_prepare(hipStream_t st, const ProbeWs& b, const float* x, const float* s, int P)
+{
+    const hipError_t e = probe_prepare(st, b, s, P);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(probe_l1_rows_kernel, dim3((unsigned)(((long long)b.N + 3) / 4)), dim3(256), 0, st, x, b.xs, b.sT, b.is, b.N, b.dim, b.Ppad);
+    return hipGetLastError();
+}
+
+hipError_t probe_l1_curv(hipStream_t st, const ProbeWs& b)
+{
+    ProbeCurvArgs a{};
+    a.x = b.xs; a.D = b.D; a.gp = b.gp; a.flags = b.is;
+    a.N = b.N; a.dim = b.dim; a.LD = b.LD; a.Ppad = b.Ppad; a.parts = b.parts; a.chunk = b.chunk;
+    const dim3 grid((unsigned)(b.parts * (b.Ppad / kTP)), (unsigned)((b.dim + 31) / 32));
+    hipLaunchKernelGGL(probe_l1_curv_kernel, grid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t probe_l1_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_inner, float tol, const ProbeAlphas& al)
+{
+    const dim3 grid((unsigned)P);
+    if (phase == 0) hipLaunchKernelGGL(probe_l1_vec_kernel<0>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
+    else if (phase == 1) hipLaunchKernelGGL(probe_l1_vec_kernel<1>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
+    else if (phase == 2) hipLaunchKernelGGL(probe_l1_vec_kernel<2>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
+    else hipLaunchKernelGGL(probe_l1_vec_kernel<3>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-// probing.cpp -- linear probes of latent rows: the lockstep truncated-Newton loop of avae_probe_fit and avae_probe_decision (contract:
-// include/argsim_vae.h; kernels: probe.hip).
+// probing.cpp -- linear probes of latent rows: the lockstep truncated-Newton loop of avae_probe_fit, the lockstep proximal-Newton loop
+// of avae_probe_fit_l1, and avae_probe_decision (contract: include/argsim_vae.h; kernels: probe.hip).
 #include "ctx.h"
 
 using namespace avae;
@@ -23,6 +23,18 @@ void probe_layout(Bump& b, ProbeWs& w, const ProbePlan& p, int N, int dim)
     w.tp = b.take<double>((size_t)p.parts * kProbeAlphas * p.Ppad);
     w.is = b.take<int>((size_t)p.Ppad * 8); w.fs = b.take<float>((size_t)p.Ppad * 8); w.ds = b.take<double>((size_t)p.Ppad * 8);
     w.N = N; w.dim = dim; w.LD = p.LD; w.Ppad = p.Ppad; w.parts = p.parts; w.chunk = p.chunk;
+}
+
+// Workspace of an L1 fit: that of the L2 fit, then
+//   3 Ppad LD floats           the FISTA point y, H d of the accepted d, H y
+//   N dim floats               x with the rows that are not finite zeroed
+void probe_l1_layout(Bump& b, ProbeWs& w, const ProbePlan& p, int N, int dim)
+{
+    probe_layout(b, w, p, N, dim);
+    const size_t vec = (size_t)p.Ppad * p.LD;
+    w.Yv = b.take<float>(3 * vec);
+    if (w.Yv) { w.Hd = w.Yv + vec; w.Hy = w.Hd + vec; }
+    w.xs = b.take<float>((size_t)N * dim);
 }
 
 // the trial rounds of the Armijo search: step length 0 (the loss at w from the same panels) and 1, 1/2, .. 2^-20
@@ -89,6 +101,60 @@ int avae_probe_fit(avae_handle h, const float* x, int32_t N, int32_t dim, const 
         for (int r = 0; r < 4; ++r) {
             AV_CHECK(probe_trial(h->stream, b, rounds[r]));
             AV_CHECK(probe_vec(h->stream, b, P, 2, r, pc->max_newton, pc->max_cg, pc->tol, rounds[r]));
+        }
+    }
+    AV_CHECK(probe_finish(h->stream, b, P, w, stats));
+    return 0;
+}
+
+// The L1 fit: the workspace of the L2 fit, 3 more vectors per problem and the copy of x (probe_l1_layout), and per proximal Newton
+// iteration GRAD + vec, the synchronisation, the curvature sums + vec, max_inner x (HV + vec), PANEL, 4 x (trial + vec).
+int avae_probe_fit_l1(avae_handle h, const float* x, int32_t N, int32_t dim, const float* s, int32_t P, const avae_probe_l1_config* pc, float* w, float* stats)
+{
+    if (!h) return 1;
+    if (!pc) return fail(h, "probe l1 config is null");
+    if (!x || !s || !w) return fail(h, "probe l1: x, s and w must be given");
+    if (N < 1 || P < 1) return fail(h, "probe l1: N and P must be >= 1");
+    if (P > (1 << 20)) return fail(h, "probe l1: at most 2^20 problems per call");
+    if (N > 0x7fffffff - 255) return fail(h, "probe l1: at most 2^31 - 256 rows per call");
+    if (pc->max_newton < 1 || pc->max_inner < 1) return fail(h, "probe l1: max_newton and max_inner must be >= 1");
+    if (!(pc->tol >= 0.f)) return fail(h, "probe l1: tol must be >= 0 (and not NaN)");
+    if (pc->reserved != 0) return fail(h, "probe l1: the reserved field must be 0");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "probe l1: dim must be a multiple of 4 in [4, 1024]");
+    if (((uintptr_t)x | (uintptr_t)w) & 15) return fail(h, "probe l1: x and w must be 16-byte aligned");
+    AV_CHECK(hipSetDevice(h->device));
+    const ProbePlan p = probe_plan(N, P, dim, h->probe_chunk);
+    if ((long long)p.parts * p.ptiles > 0x7fffffffLL ) return fail(h, "probe l1: too many (row part, problem tile) workgroups for one launch");
+    ProbeWs b{};
+    Bump probe{nullptr};
+    probe_l1_layout(probe, b, p, N, dim);
+    AV_TRY(reserve_named(h, probe.off + 4096, "probe l1"));     // sized once per call; nothing is allocated between the launches
+    Bump real{h->ws};
+    probe_l1_layout(real, b, p, N, dim);
+    ProbeAlphas rounds[4];
+    probe_rounds(rounds);
+    const ProbeAlphas none{};
+    std::vector<int> state((size_t)p.Ppad * 8);
+    AV_CHECK(probe_l1_prepare(h->stream, b, x, s, P));
+    for (int it = 0; it <= pc->max_newton; ++it) {
+        AV_CHECK(probe_pass(h->stream, b, b.xs, 0));
+        AV_CHECK(probe_l1_vec(h->stream, b, P, 0, it, pc->max_newton, pc->max_inner, pc->tol, none));
+        // the one synchronisation of an iteration, as in avae_probe_fit
+        AV_CHECK(hipMemcpyAsync(state.data(), b.is, state.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        AV_CHECK(hipStreamSynchronize(h->stream));
+        bool alive = false;
+        for (int q = 0; q < P; ++q) alive = alive || state[(size_t)q * 8 + 2] == 0;
+        if (!alive) break;
+        AV_CHECK(probe_l1_curv(h->stream, b));
+        AV_CHECK(probe_l1_vec(h->stream, b, P, 3, it, pc->max_newton, pc->max_inner, pc->tol, none));
+        for (int k = 0; k < pc->max_inner; ++k) {
+            AV_CHECK(probe_pass(h->stream, b, b.xs, 1));
+            AV_CHECK(probe_l1_vec(h->stream, b, P, 1, k, pc->max_newton, pc->max_inner, pc->tol, none));
+        }
+        AV_CHECK(probe_pass(h->stream, b, b.xs, 2));
+        for (int r = 0; r < 4; ++r) {
+            AV_CHECK(probe_trial(h->stream, b, rounds[r]));
+            AV_CHECK(probe_l1_vec(h->stream, b, P, 2, r, pc->max_newton, pc->max_inner, pc->tol, rounds[r]));
         }
     }
     AV_CHECK(probe_finish(h->stream, b, P, w, stats));

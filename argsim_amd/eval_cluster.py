@@ -9,7 +9,10 @@ group of ONE device call (VAE.cluster_eval).  Prints the reference's lines.
 --by topic | stance | reason: one selection per topic, per (topic, stance) or per (topic, reason), in sorted order
 (eval_clustering.py:86-92, where the partition picked at its line 35 decides).  --by all: the whole set cut at the number of topics
 and at the number of labels, then every topic's rows against their labels.  --dims: an .npy of column numbers to keep (the
-useful_dimension.npy that eval_clustering.py:57-58 writes)."""
+useful_dimension.npy that eval_clustering.py:57-58 writes).  --select topic | stance | reason | labels: pick those columns here instead,
+as eval_clustering.py:46-58 does -- the L1 logistic model (C = 0.1) of that partition of the labels, fitted on the device
+(VAE.select_dims; the reference's line 35 picks stance), keeping the columns with a nonzero coefficient in any class -- print how many
+were kept, write them with --save-dims PATH, and cluster on them."""
 import argparse
 
 import numpy as np
@@ -67,19 +70,54 @@ def evaluate(vae, z, labels, by):
     return scores, report_all(scores, order)
 
 
-def main(argv=None):
+def partition(parts, which):
+    """the gold partition of eval_clustering.py:16-35 -> (n,) strings: the topic, (topic, stance), (topic, reason) or the whole label"""
+    pick = {'topic': lambda p: p[0], 'stance': lambda p: p[0] + '-' + p[1], 'reason': lambda p: p[0] + '-' + p[2], 'labels': "-".join}[which]
+    return np.array([pick(p) for p in parts])
+
+
+def select(vae, z, labels, which, C=0.1):
+    """eval_clustering.py:46-58 on the device: the columns of z that the L1 model of that partition uses -> dims (int64, sorted)"""
+    dims, probe = vae.select_dims(z, partition(split_labels(labels), which), C=C)
+    if probe.stats.shape[0] and (probe.stats[:, 3] != 0).any():
+        raise RuntimeError("the L1 fit of the selection did not converge: status %s per class" % (probe.stats[:, 3].astype(int).tolist(),))
+    if dims.shape[0] == 0:
+        raise RuntimeError("the selection keeps no column: every coefficient of the L1 model at C = %g is zero" % C)
+    return dims
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--inputs', required=True, help=".npy (n, dim) float32 embeddings (eval_embed's output)")
     ap.add_argument('--labels', required=True, help=".npy (n,) strings topic-stance-reason")
     ap.add_argument('--by', choices=('topic', 'stance', 'reason', 'all'), default='stance')
-    ap.add_argument('--dims', default=None, help=".npy of the column numbers to cluster on (useful_dimension.npy)")
+    which = ap.add_mutually_exclusive_group()
+    which.add_argument('--dims', default=None, help=".npy of the column numbers to cluster on (useful_dimension.npy)")
+    which.add_argument('--select', choices=('topic', 'stance', 'reason', 'labels'), default=None,
+                       help="pick the columns on the device: those the L1 model (C = 0.1) of this partition of the labels uses")
+    ap.add_argument('--save-dims', default=None, help="with --select: write the kept column numbers to this .npy (int64)")
     ap.add_argument('--device', type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     A = ap.parse_args(argv)
+    if A.save_dims is not None and A.select is None:
+        ap.error("--save-dims needs --select")
     z = np.load(A.inputs)
+    labels = np.load(A.labels)
+    vae = make_vae(A.device)
     if A.dims is not None:
         z = z[:, np.load(A.dims)]
+    elif A.select is not None:
+        dims = select(vae, np.ascontiguousarray(z, dtype=np.float32), labels, A.select)
+        print("useful dimensions: %d of %d" % (dims.shape[0], z.shape[1]))
+        if A.save_dims is not None:
+            np.save(A.save_dims, dims)
+        z = z[:, dims]
     z = np.ascontiguousarray(z, dtype=np.float32)
-    scores, lines = evaluate(make_vae(A.device), z, np.load(A.labels), A.by)
+    scores, lines = evaluate(vae, z, labels, A.by)
     for line in lines:
         print(line)
     return scores

@@ -65,6 +65,10 @@ class AvaeProbeConfig(C.Structure):
     _fields_ = [('max_newton', C.c_int32), ('max_cg', C.c_int32), ('tol', C.c_float), ('reserved', C.c_int32)]
 
 
+class AvaeProbeL1Config(C.Structure):
+    _fields_ = [('max_newton', C.c_int32), ('max_inner', C.c_int32), ('tol', C.c_float), ('reserved', C.c_int32)]
+
+
 class AvaeWardConfig(C.Structure):
     _fields_ = [('reserved', C.c_int32 * 2)]
 
@@ -107,6 +111,7 @@ SIGNATURES = {
     'avae_latent_moments': (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P]),
     'avae_probe_fit': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(AvaeProbeConfig), _P, _P]),
     'avae_probe_decision': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P]),
+    'avae_probe_fit_l1': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(AvaeProbeL1Config), _P, _P]),
     'avae_ward': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(AvaeWardConfig), _P, _P, _P]),
     'avae_ward_cut': (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)

@@ -16,6 +16,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) nearest neighbours among latent rows         -> VAE.neighbors(queries, bank, k, metric) / neighbors(vae, ...)
     (new) aggregate-posterior diagnostics (MI, AU)     -> VAE.posterior_stats(src) / VAE.log_q(z, mu, lv) / VAE.latent_moments(mu, lv)
     (new) linear probes of latent rows (liblinear CV)  -> VAE.probe_fit(z, labels) / VAE.probe_cv(z, labels, folds, groups)
+    (new) L1 probes: the useful dimensions (liblinear) -> VAE.probe_fit_l1(z, labels) / VAE.select_dims(z, labels)
     (new) Ward clustering of latent rows (ARS, V_MSR)  -> VAE.ward(z, groups) / VAE.ward_cut(res, k) / VAE.cluster_eval(z, gold, groups)
 """
 import ctypes as C
@@ -599,6 +600,19 @@ class VAE:
         from . import probe
         return probe.cross_validate(self, z, labels, folds, groups, C, class_weight, **solver)
 
+    def probe_fit_l1(self, z, labels, C=0.1, class_weight=None, train=None, **solver):
+        """the one-vs-rest L1 logistic regression of the reference's src/eval_clustering.py:46, LogisticRegression(penalty='l1', C,
+        solver='liblinear'), fitted on the device (include/argsim_vae.h, avae_probe_fit_l1) -> the object probe_fit returns; a zero
+        coefficient is an exact 0.  solver: tol, max_newton, max_inner."""
+        from . import probe
+        return probe.fit_l1(self, z, labels, C, class_weight, train, **solver)
+
+    def select_dims(self, z, labels, C=0.1, class_weight=None, train=None, **solver):
+        """the useful dimensions of src/eval_clustering.py:57 -> (dims, probe): the sorted columns of z with a nonzero coefficient in
+        any class of that L1 model (int64, as useful_dimension.npy), and the model"""
+        from . import probe
+        return probe.select_dims(self, z, labels, C, class_weight, train, **solver)
+
     def ward(self, z, groups=None):
         """the Ward tree (sklearn's AgglomerativeClustering default, scipy's linkage(x, 'ward')) of every group of rows of z, all groups
         in ONE device call (include/argsim_vae.h, avae_ward).  groups: None, an (N,) array of group labels or {key: row numbers}
@@ -809,6 +823,16 @@ def probe_fit(vae, z, labels, C=0.001, class_weight='balanced', train=None, **so
 def probe_cv(vae, z, labels, folds, groups=None, C=0.001, class_weight='balanced', **solver):
     """functional form of VAE.probe_cv"""
     return vae.probe_cv(z, labels, folds, groups, C, class_weight, **solver)
+
+
+def probe_fit_l1(vae, z, labels, C=0.1, class_weight=None, train=None, **solver):
+    """functional form of VAE.probe_fit_l1"""
+    return vae.probe_fit_l1(z, labels, C, class_weight, train, **solver)
+
+
+def select_dims(vae, z, labels, C=0.1, class_weight=None, train=None, **solver):
+    """functional form of VAE.select_dims"""
+    return vae.select_dims(z, labels, C, class_weight, train, **solver)
 
 
 def ward(vae, z, groups=None):

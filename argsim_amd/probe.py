@@ -4,6 +4,7 @@ logistic regression per topic, scored by cross-validation) as ONE batched fit on
     probe_costs(labels, train_idx, C, class_weight)  liblinear's weighting as signed per-row costs: pure numpy
     fit(vae, z, labels, ...)                         -> Probe (classes_, coef_, intercept_, stats, decision, predict)
     cross_validate(vae, z, labels, folds, groups)    every group x fold x class in one avae_probe_fit -> held-out predictions, scores
+    l1_costs / fit_l1 / select_dims(vae, z, labels)  the L1 model of src/eval_clustering.py:46-58 (avae_probe_fit_l1) and the columns it keeps
 """
 import ctypes as C
 
@@ -12,6 +13,7 @@ import numpy as np
 DEFAULT_TOL = 1e-4          # scikit-learn's; DESIGN 4.3h records the smallest tol at which every test case still converges
 DEFAULT_MAX_NEWTON = 50
 DEFAULT_MAX_CG = 30
+DEFAULT_MAX_INNER = 50      # the L1 fit: Hessian products per proximal Newton iteration
 STATUS = {0: 'converged', 1: 'max_newton reached', 2: 'line search exhausted or a value that is not finite'}
 
 
@@ -55,14 +57,22 @@ def probe_costs(labels, train_idx=None, C=0.001, class_weight='balanced'):
     return classes, costs.astype(np.float32)
 
 
-def _check_fit_args(z, costs, tol, max_newton, max_cg):
-    """the argument rules of avae_probe_fit, checked before anything touches the device"""
+def l1_costs(labels, train_idx=None, C=0.1, class_weight=None):
+    """the signed costs of the reference's dimension selection, LogisticRegression(penalty='l1', C=0.1, solver='liblinear') of
+    src/eval_clustering.py:46: the one-vs-rest layout of probe_costs (K >= 3: K problems, K = 2: one, K = 1: none) with that
+    call's defaults, C = 0.1 and no class weights -> (classes, costs (P, N) float32) for avae_probe_fit_l1"""
+    return probe_costs(labels, train_idx, C, class_weight)
+
+
+def _check_fit_args(z, costs, tol, max_newton, max_cg, inner='max_cg'):
+    """the argument rules of avae_probe_fit (and, with inner='max_inner', of avae_probe_fit_l1), checked before anything touches
+    the device"""
     _check_rows('z', z)
     if not isinstance(costs, np.ndarray) or costs.dtype != np.float32 or costs.ndim != 2:
         raise ValueError("costs must be a (P, N) float32 numpy array")
     if costs.shape[0] < 1 or costs.shape[1] != z.shape[0]:
         raise ValueError("costs must be (P, N) with P >= 1 and N = %d rows of z, got %s" % (z.shape[0], costs.shape))
-    for name, v in (('max_newton', max_newton), ('max_cg', max_cg)):
+    for name, v in (('max_newton', max_newton), (inner, max_cg)):
         if isinstance(v, bool) or int(v) != v or not 1 <= v < (1 << 31):
             raise ValueError("%s must be an integer >= 1, got %r" % (name, v))
     if isinstance(tol, bool) or not (tol >= 0) or not np.isfinite(tol):
@@ -89,19 +99,31 @@ def _check_rows(name, x):
 
 def fit_raw(vae, z, costs, tol=DEFAULT_TOL, max_newton=DEFAULT_MAX_NEWTON, max_cg=DEFAULT_MAX_CG):
     """avae_probe_fit as it stands: z (N, dim) float32 numpy or torch, costs (P, N) float32 numpy -> (w (P, dim + 1), stats (P, 4)) numpy"""
-    import torch
     from . import lib as _lib
     tol, max_newton, max_cg = _check_fit_args(z, costs, tol, max_newton, max_cg)
+    return _fit_call(vae, z, costs, vae._l.avae_probe_fit, _lib.AvaeProbeConfig(max_newton, max_cg, tol, 0))
+
+
+def _fit_call(vae, z, costs, entry, pc):
+    """one of the two fit entries (same arguments but for the config) on checked arguments"""
+    import torch
     x = vae._dev_f32(z)
     s = torch.as_tensor(np.ascontiguousarray(costs)).to(vae.device)
     N, dim, P = x.shape[0], x.shape[1], costs.shape[0]
     w = torch.empty((P, dim + 1), dtype=torch.float32, device=vae.device)
     stats = torch.empty((P, 4), dtype=torch.float32, device=vae.device)
-    pc = _lib.AvaeProbeConfig(max_newton, max_cg, tol, 0)
     vae._stream()
-    vae._ck(vae._l.avae_probe_fit(vae._h, C.c_void_p(x.data_ptr()), N, dim, C.c_void_p(s.data_ptr()), P, C.byref(pc),
-                                  C.c_void_p(w.data_ptr()), C.c_void_p(stats.data_ptr())))
+    vae._ck(entry(vae._h, C.c_void_p(x.data_ptr()), N, dim, C.c_void_p(s.data_ptr()), P, C.byref(pc),
+                  C.c_void_p(w.data_ptr()), C.c_void_p(stats.data_ptr())))
     return w.cpu().numpy(), stats.cpu().numpy()
+
+
+def fit_l1_raw(vae, z, costs, tol=DEFAULT_TOL, max_newton=DEFAULT_MAX_NEWTON, max_inner=DEFAULT_MAX_INNER):
+    """avae_probe_fit_l1 as it stands: z (N, dim) float32 numpy or torch, costs (P, N) float32 numpy -> (w (P, dim + 1), stats (P, 4))
+    numpy; a zero of w is an exact +0.0"""
+    from . import lib as _lib
+    tol, max_newton, max_inner = _check_fit_args(z, costs, tol, max_newton, max_inner, 'max_inner')
+    return _fit_call(vae, z, costs, vae._l.avae_probe_fit_l1, _lib.AvaeProbeL1Config(max_newton, max_inner, tol, 0))
 
 
 def decision_raw(vae, z, w):
@@ -132,7 +154,7 @@ def labels_from_decision(classes, dec):
 
 class Probe:
     """a fitted one-vs-rest model: classes_ (K,), coef_ (P, dim), intercept_ (P,), stats (P, 4) = f, |grad f|, Newton iterations,
-    status per problem (P = K, or 1 for K = 2, or 0 for K = 1)"""
+    status per problem (P = K, or 1 for K = 2, or 0 for K = 1); of an L1 fit: F, |v|_1, outer iterations, status"""
 
     def __init__(self, vae, classes, w, stats):
         self._vae, self.classes_, self._w, self.stats = vae, classes, w, stats
@@ -165,6 +187,35 @@ def fit(vae, z, labels, C=0.001, class_weight='balanced', train=None, tol=DEFAUL
         return Probe(vae, classes, np.zeros((0, dim + 1), np.float32), np.zeros((0, 4), np.float32))
     w, stats = fit_raw(vae, z, costs, tol, max_newton, max_cg)
     return Probe(vae, classes, w, stats)
+
+
+def fit_l1(vae, z, labels, C=0.1, class_weight=None, train=None, tol=DEFAULT_TOL, max_newton=DEFAULT_MAX_NEWTON, max_inner=DEFAULT_MAX_INNER):
+    """the one-vs-rest L1 model of the labels (l1_costs) fitted by avae_probe_fit_l1 -> Probe; its stats are F, |v|_1, the outer
+    iterations and the status per problem"""
+    labels = _check_labels(z, labels)
+    classes, costs = l1_costs(labels, train, C, class_weight)
+    dim = z.shape[1]
+    if costs.shape[0] == 0:
+        _check_fit_args(z, np.zeros((1, z.shape[0]), np.float32), tol, max_newton, max_inner, 'max_inner')
+        return Probe(vae, classes, np.zeros((0, dim + 1), np.float32), np.zeros((0, 4), np.float32))
+    w, stats = fit_l1_raw(vae, z, costs, tol, max_newton, max_inner)
+    return Probe(vae, classes, w, stats)
+
+
+def useful_dims(coef):
+    """the rule of the reference's src/eval_clustering.py:57 on coef (P, dim): the sorted numbers of the columns with a nonzero
+    coefficient in any class (int64, as useful_dimension.npy).  The device returns exact zeros, so no threshold is used."""
+    coef = np.asarray(coef)
+    if coef.ndim != 2:
+        raise ValueError("coef must be (P, dim), got %s" % (coef.shape,))
+    return np.flatnonzero((coef != 0).any(axis=0)).astype(np.int64)
+
+
+def select_dims(vae, z, labels, C=0.1, class_weight=None, train=None, **solver):
+    """the dimension selection of src/eval_clustering.py:46-58 -> (dims, probe): the L1 model of the labels and the columns of z it
+    uses.  solver: tol, max_newton, max_inner."""
+    probe = fit_l1(vae, z, labels, C, class_weight, train, **solver)
+    return useful_dims(probe.coef_), probe
 
 
 def cv_problems(labels, folds, groups=None, C=0.001, class_weight='balanced'):

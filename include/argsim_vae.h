@@ -404,6 +404,48 @@ int  avae_probe_fit(avae_handle h, const float* x /* (N, dim) */, int32_t N, int
 int  avae_probe_decision(avae_handle h, const float* x /* (n, dim) */, int32_t n, int32_t dim,
                          const float* w /* (P, dim + 1) */, int32_t P, float* out /* (n, P) */);
 
+/* ---- L1 probes: sparse logistic fits and the selection of useful dimensions ------------------ */
+/* The dimension selection of the reference (src/eval_clustering.py:46-60: LogisticRegression(penalty='l1', C=0.1,
+ * solver='liblinear'), then the columns whose coefficients are not all zero): P independent L1-regularised logistic regressions over
+ * ONE matrix of latent rows, fitted in lockstep on the device.  Arrays, alignment and the ranges of N, P and dim as for
+ * avae_probe_fit; avae_probe_decision evaluates the fitted w.
+ *   objective  problem p minimises F_p(w) = |w|_1 + sum_i |s_pi| softplus(-sgn(s_pi) w . x~_i), x~_i = (x_i, 1).  The bias is the
+ *              last component and IS inside the 1-norm (liblinear with intercept_scaling = 1).  The costs mean what they mean in
+ *              avae_probe_fit: the sign is the label, the magnitude C times the weight, and 0 leaves the row out.
+ *   optimality with g = X~^T r the gradient of the smooth part, the minimum-norm subgradient of F_p is v(w), v_j = g_j + sgn(w_j)
+ *              where w_j != 0 and v_j = sgn(g_j) max(|g_j| - 1, 0) where w_j = 0; w is optimal iff v(w) = 0.  F_p is not smooth and
+ *              not strongly convex: there is NO certificate |w - w*| <= |grad f| here; |v(w)|_1 is what a caller can check.
+ *   method     proximal Newton from w = 0 (the structure of liblinear's newGLMNET).  Per iteration the inner problem
+ *              min_d g.d + 1/2 d.Hd + |w + d|_1, H = X~^T D X~, is solved by FISTA with adaptive restart: the candidate
+ *              d+ = soft(w + y - (g + Hy) / L, 1 / L) - w, ONE Hessian product per inner iteration (H y follows by linearity); L
+ *              starts at the largest diagonal entry of H (from the second iteration on at half of what the last inner solve ended
+ *              with, relative to that entry) and doubles whenever (d+ - y).H(d+ - y) > L |d+ - y|^2, which spends that product and
+ *              resets the momentum; the inner solve ends at |v_q(d)|_1 <= 0.1 |v(w)|_1, v_q the minimum-norm subgradient of the inner
+ *              problem, or after max_inner products.  The step is taken with the first alpha in 1, 1/2, .. 2^-20 for which
+ *              F(w + alpha d) <= F(w) + 0.01 alpha (g.d + |w + d|_1 - |w|_1) (liblinear's sufficient decrease); the smooth sums come
+ *              from the kept panels in double, the 1-norms are summed in double.  Every loop is bounded.
+ *   stop       a problem stops, and is frozen, at the first iteration where |v(w)|_1 <= tol |v(0)|_1.  This is liblinear's own
+ *              measure (Gnorm1) WITHOUT its min(#pos, #neg) / l scaling of tol.  A problem with v(0) = 0 -- every |g_j(0)| <= 1:
+ *              tiny costs, all costs 0 -- converges at iteration 0 with w exactly 0.
+ *   zeros      a returned zero is an exact +0.0f, produced by the soft-threshold: the selection reads w != 0, no threshold.
+ *   stats      stats[p] = F_p(w), |v(w)|_1 as the device evaluated it at the returned w, the outer iterations taken, and a status:
+ *              0 converged, 1 max_newton reached, 2 the line search was exhausted or a value that is not finite was met.
+ *              Inputs are NOT checked for finiteness: such a value ends the affected problem with status 2, never a hang.  A row
+ *              of x that holds such a value ends, before the first pass, the problems whose cost on it is not 0, and only those:
+ *              the fit runs on a copy of x with that row zeroed, so the others keep their bits.
+ *   bits       w[p] and stats[p] depend on x, on row p of s, on the config and on option probe_chunk alone -- not on P, on p or on
+ *              the other problems of the call.  No float atomics, fixed-order reductions: the same arguments give the same bits.
+ *   launches   per iteration 13 + 2 max_inner, whatever the problems need, and ONE stream synchronisation, after the gradient.
+ *   workspace  that of avae_probe_fit + 12 Pp (dim + 4) + 4 N dim bytes (three more vectors per problem and the copy of x), reserved
+ *              once per call.
+ * Errors (text through avae_last_error): a null pc, x, s or w; N or P < 1; N > 2^31 - 256; P > 2^20; max_newton < 1, max_inner < 1;
+ * a tol that is negative or NaN; reserved != 0; dim not a multiple of 4 in [4, 1024]; x or w not 16-byte aligned; a workspace the
+ * device cannot give (the text names its size).  Option probe_chunk applies as in avae_probe_fit. */
+typedef struct avae_probe_l1_config { int32_t max_newton; int32_t max_inner; float tol; int32_t reserved; } avae_probe_l1_config;
+int  avae_probe_fit_l1(avae_handle h, const float* x /* (N, dim) */, int32_t N, int32_t dim,
+                       const float* s /* (P, N) signed costs */, int32_t P, const avae_probe_l1_config* pc,
+                       float* w /* (P, dim + 1) out */, float* stats /* (P, 4) optional */);
+
 /* ---- hierarchical clustering of latent rows -------------------------------------------------- */
 /* The clustering evaluation of the reference (src/eval_clustering.py:82-103, src/eval_clustering_explorative.py:138-176:
  * AgglomerativeClustering, Ward linkage, per selection of rows) as ONE call over G independent groups of rows.  x (N, dim) is a
