@@ -16,6 +16,7 @@
 // Reductions run in a fixed order (a thread's terms in index order, a wave by shuffles, the workgroup through LDS); the
 // only atomics are integer ones (LDS histograms, list slots, the live-slot counter): the same arguments give the same bits.
 #include "kernels.h"
+#include "reduce_dev.h"
 #include "sample_dev.h"
 
 #include <algorithm>
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void beam_rows_kernel(const float* __restrict_
     const float* x = logits + (size_t)row * V;
     float m = -INFINITY, s = 0.f;
     for (int c = tid; c < V; c += 256) { const float l = x[c]; if (l == l) lse_add(m, s, l); }
-    for (int o = 32; o > 0; o >>= 1) { const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64); lse_merge(m, s, om, os); }
+    lse_wave_merge(m, s);
     if (tid == 0) s_n = 0;
     if (lane == 0) { s_m[wave] = m; s_s[wave] = s; }
     __syncthreads();

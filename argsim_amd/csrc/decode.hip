@@ -36,6 +36,7 @@
 // The greedy instantiation's device code is the parent's instruction for instruction (one kernel-argument offset moved).
 #include "kernels.h"
 #include "mfma_tile.h"
+#include "reduce_dev.h"
 #include "sample_dev.h"
 
 namespace avae {
@@ -60,7 +61,7 @@ __device__ __forceinline__ void st4i_sc1(int32_t* p, int v) { __hip_atomic_store
 
 // sum over the 64 lanes, returned in every lane: DPP adds inside the 16-lane rows, row broadcasts across them, one
 // readlane (vector ALU only -- the shuffle form goes through the LDS pipe, which the weight reads already load)
-__device__ __forceinline__ float wave_sum(float v)
+__device__ __forceinline__ float wave_sum_dpp(float v)
 {
 #define AVAE_DPP_ADD(ctrl, rows) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, rows, 0xf, false))
     AVAE_DPP_ADD(0xB1, 0xf);        // quad_perm [1,0,3,2]
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
                         const int u = w + s * G;
                         float gsum[6];
 #pragma unroll
-                        for (int g = 0; g < 6; ++g) gsum[g] = wave_sum(acc[i][s][g]);
+                        for (int g = 0; g < 6; ++g) gsum[g] = wave_sum_dpp(acc[i][s][g]);
                         if (lane == 0 && u < D && bb < b) {
                             const int c = (u / 16) * 48 + (u % 16) * 3;
                             const float gi_r = gsum[0] + a.bW[l][c], gi_u = gsum[1] + a.bW[l][c + 1], gi_n = gsum[2] + a.bW[l][c + 2];
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
                 for (int s = 0; s < 2; ++s) {
                     if (s >= nu) break;
                     const int u = w + s * G;
-                    const float v = wave_sum(acc[s]);
+                    const float v = wave_sum_dpp(acc[s]);
                     if (lane == 0 && u < D) st4_sc1(a.o + (size_t)bb * D + u, v + a.bout[u]);
                 }
             }
@@ -243,8 +244,11 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
         }
         // ---- tied logits (model.py:166) over this workgroup's vocabulary rows, partial argmax (first maximum)
         for (int bb0 = wave; bb0 < b; bb0 += kDecWaves * kRows) {
+            // greedy: the wave's first maximum; sampled: lanes 0..7 each keep the candidate and the (max, sum exp) of the ids = lane mod 8.
+            // (The fields of an ArgFirst / a Pick per row as plain scalars: with the structs here hipcc pairs the products of dot4 the other
+            //  way round in the GRU phase of kMode 3, and its logits change in the last bit.)
             float best[kRows]; int besti[kRows];
-            float bx[kRows], lm[kRows], ls[kRows];              // sampled: lanes 0..7 each keep the candidate and the (max, sum exp) of the ids = lane mod 8
+            float bx[kRows], lm[kRows], ls[kRows];
             float4 ov[kRows][2];                                  // this lane's slice of the `out` rows (D <= 512: two pieces)
 #pragma unroll
             for (int r = 0; r < kRows; ++r) {
@@ -282,7 +286,7 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         if (vb + j >= v1) break;
-                        const float v = wave_sum(p[r][j]) * a.isd;
+                        const float v = wave_sum_dpp(p[r][j]) * a.isd;
                         if constexpr (kMode == 0) { if (v > best[r]) { best[r] = v; besti[r] = vb + j; } }      // ascending v: the first maximum stays
                         else if (lane == j) mine = v;
                     }
@@ -304,15 +308,11 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
             for (int r = 0; r < kRows; ++r) {
                 const int bb = bb0 + r * kDecWaves;
                 if constexpr (kMode == 1) {
-#pragma unroll
-                    for (int o = 4; o > 0; o >>= 1) {            // lanes 8.. hold the neutral element
-                        const float ob = __shfl_xor(best[r], o, 64), ox = __shfl_xor(bx[r], o, 64), om = __shfl_xor(lm[r], o, 64), os = __shfl_xor(ls[r], o, 64);
-                        const int oi = __shfl_xor(besti[r], o, 64);
-                        if (cand_better(ob, oi, best[r], besti[r])) { best[r] = ob; besti[r] = oi; bx[r] = ox; }
-                        lse_merge(lm[r], ls[r], om, os);
-                    }
+                    Pick p{best[r], bx[r], lm[r], ls[r], besti[r]};
+                    p.wave_merge<8>();                            // lanes 8.. hold the neutral element
+                    best[r] = p.best; besti[r] = p.besti;
                     if (lane == 0 && bb < b) {
-                        st4_sc1(a.part_x + (size_t)w * b + bb, bx[r]); st4_sc1(a.part_m + (size_t)w * b + bb, lm[r]); st4_sc1(a.part_s + (size_t)w * b + bb, ls[r]);
+                        st4_sc1(a.part_x + (size_t)w * b + bb, p.bx); st4_sc1(a.part_m + (size_t)w * b + bb, p.m); st4_sc1(a.part_s + (size_t)w * b + bb, p.s);
                     }
                 }
                 if constexpr (kMode < 2)
@@ -325,41 +325,25 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
         if constexpr (kMode == 0) {
         if (wave == 0)
             for (int bb = w; bb < b; bb += G) {
-                float best = -INFINITY; int besti = 0x7fffffff;
-                for (int g = lane; g < G; g += 64) {
-                    const float v = ld4_sc1(a.part_val + (size_t)g * b + bb);
-                    const int vi = ld4i_sc1(a.part_idx + (size_t)g * b + bb);
-                    if (v > best || (v == best && vi < besti)) { best = v; besti = vi; }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(besti, o, 64);
-                    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-                }
-                if (lane == 0) st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, besti);
+                ArgFirst am;
+                for (int g = lane; g < G; g += 64) am.merge(ArgFirst{ld4_sc1(a.part_val + (size_t)g * b + bb), ld4i_sc1(a.part_idx + (size_t)g * b + bb)});
+                am.wave_merge();
+                if (lane == 0) st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, am.i);
             }
         } else if constexpr (kMode == 1) {
         // sampled: the same merge over (score, id), with the candidate's l inv_t and the (max, sum exp) pairs for its logp
         if (wave == 0)
             for (int bb = w; bb < b; bb += G) {
-                float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
+                Pick p;
                 for (int g = lane; g < G; g += 64) {
-                    const float v = ld4_sc1(a.part_val + (size_t)g * b + bb);
-                    const int vi = ld4i_sc1(a.part_idx + (size_t)g * b + bb);
-                    if (cand_better(v, vi, best, besti)) { best = v; besti = vi; bx = ld4_sc1(a.part_x + (size_t)g * b + bb); }
-                    lse_merge(m, s, ld4_sc1(a.part_m + (size_t)g * b + bb), ld4_sc1(a.part_s + (size_t)g * b + bb));
+                    const size_t at = (size_t)g * b + bb;
+                    p.merge(Pick{ld4_sc1(a.part_val + at), ld4_sc1(a.part_x + at), ld4_sc1(a.part_m + at), ld4_sc1(a.part_s + at), ld4i_sc1(a.part_idx + at)});
                 }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-                    const int oi = __shfl_xor(besti, o, 64);
-                    if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
-                    lse_merge(m, s, om, os);
-                }
+                p.wave_merge();
                 if (lane == 0) {
                     const bool fin = t > 0 && ld4i_sc1(lead + bb) == a.eos;       // a row fed eos has finished: eos again, logp 0
-                    st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, fin ? a.eos : (besti == 0x7fffffff ? 0 : besti));
-                    if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, fin ? 0.f : lse_logp(bx, m, s));
+                    st4i_sc1(a.ids_tm + (size_t)(t + 1) * b + bb, fin ? a.eos : p.token());
+                    if (a.logp_tm) st4_sc1(a.logp_tm + (size_t)t * b + bb, fin ? 0.f : p.logp());
                 }
             }
         } else {
@@ -411,6 +395,8 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
                     for (int i = 0; i < kSelMax; ++i) if (tid + i * kDecThreads < V && lv[i] == lv[i] && key[i] >= thr) f(key[i], wt[i]);
                 }, a.top_p, msh, &nkept);
             }
+            // (pick_kept and Pick's wave_merge / block_merge of sample_dev.h, written out, in Pick's LDS layout: with the shared forms here
+            //  these two instantiations lose the parent's bits in the GRU phase, see the logits phase)
             float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
             const uint64_t base = sample_base(bb, t);
 #pragma unroll

@@ -3,6 +3,8 @@
 // column sums, TF-style Adam, layout permutation.  Each cites the reference lines it replaces.
 #include <algorithm>
 #include "kernels.h"
+#include "mfma_tile.h"      // pack_bf16
+#include "reduce_dev.h"
 #include "sample_dev.h"
 
 namespace avae {
@@ -27,8 +29,7 @@ __device__ __forceinline__ bool prep_kept(const PrepArgs& p, int i)     // decod
 }
 __device__ __forceinline__ int block_sum256(int v, int* red)            // sum over the 256 threads, returned to all
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     const int s = red[0] + red[1] + red[2] + red[3];
@@ -46,8 +47,9 @@ __global__ __launch_bounds__(256) void prep_ids_kernel(PrepArgs p, int per, int 
         // (source: the reference's length = the COUNT of non-eos ids, model.py:84; target: the decoder mask is per position, so the
         //  steps that can reach the loss end one behind the LAST non-eos id, wherever other eos ids sit)
         for (int s = lane; s < p.St; s += 64) if (p.tgt[(size_t)b * p.St + s] != p.eos) lt = s + 1;
+        ls = wave_sum(ls);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { ls += __shfl_xor(ls, o); lt = max(lt, __shfl_xor(lt, o)); }
+        for (int o = 32; o > 0; o >>= 1) lt = max(lt, __shfl_xor(lt, o));
         if (lane == 0) { p.lens_src[b] = ls; p.lens_tgt[b] = lt; }
     }
     for (int i = gid; i < p.Ss * B; i += nthr) {
@@ -684,7 +686,7 @@ hipError_t pick_last_bwd(hipStream_t st, float* dhs, const float* dh, const int3
 // ---------------------------------------------------------------- latent (model.py:151-155,183-184)
 __device__ __forceinline__ float block_sum(float v, float* sh)
 {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    v = wave_sum(v);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     __syncthreads();
     if (lane == 0) sh[wave] = v;
@@ -782,25 +784,18 @@ __global__ __launch_bounds__(256) void softmax_ce_reg_kernel(CeArgs a)
         }
         const float xl = a.logits16 ? (float)x16[label] : x[label];                       // (before anything overwrites the row)
         // pass A: maximum and its first position
-        float bv = -INFINITY; int bi = 0x7fffffff;
+        ArgFirst am;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const int c = tid * 4 + 1024 * q;
             const float e[4] = {keep[q].x, keep[q].y, keep[q].z, keep[q].w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) if (e[k] > bv) { bv = e[k]; bi = c + k; }
+            for (int k = 0; k < 4; ++k) am.take(e[k], c + k);
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_down(bv, o, 64); const int oi = __shfl_down(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
+        am.wave_merge();
         __syncthreads();                                 // (s_* of the previous row have been read)
-        if (lane == 0) { s_m[wave] = bv; s_bi[wave] = bi; }
-        __syncthreads();
-        bv = s_m[0]; bi = s_bi[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) if (s_m[w] > bv || (s_m[w] == bv && s_bi[w] < bi)) { bv = s_m[w]; bi = s_bi[w]; }
-        const float m = bv;
+        am.block_merge<4, true>(s_m, s_bi);
+        const float m = am.v; const int bi = am.i;
         // pass B: one exponential per element, kept
         float s = 0.f;
 #pragma unroll
@@ -809,7 +804,7 @@ __global__ __launch_bounds__(256) void softmax_ce_reg_kernel(CeArgs a)
             keep[q].z = exp_fast(keep[q].z - m); keep[q].w = exp_fast(keep[q].w - m);
             s += (keep[q].x + keep[q].y) + (keep[q].z + keep[q].w);
         }
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        s = wave_sum(s);
         if (lane == 0) s_s[wave] = s;
         __syncthreads();
         s = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
@@ -829,13 +824,9 @@ __global__ __launch_bounds__(256) void softmax_ce_reg_kernel(CeArgs a)
                 float e[4] = {keep[q].x, keep[q].y, keep[q].z, keep[q].w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) e[k] = e[k] * g - ((c + k) == label ? scale : 0.f);
-                if (a.grad16) {      // bf16 mode: the GEMM operand panel itself (RNE, what the conversion pass would have written)
-                    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-                    const f2 lo = {e[0], e[1]}, hi = {e[2], e[3]};
-                    const uint2 pk = make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf2)), __builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf2)));
-                    *reinterpret_cast<uint2*>(a.grad16 + (size_t)row * a.V + c) = pk;
-                } else
+                if (a.grad16)        // bf16 mode: the GEMM operand panel itself (RNE, what the conversion pass would have written)
+                    *reinterpret_cast<uint2*>(a.grad16 + (size_t)row * a.V + c) = make_uint2(pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]));
+                else
                 *reinterpret_cast<float4*>(x + c) = make_float4(e[0], e[1], e[2], e[3]);
             }
         }
@@ -879,27 +870,20 @@ __global__ __launch_bounds__(256) void softmax_ce_h16_kernel(CeArgs a)
         }
         if (row + (int)gridDim.x < n) fetch(row + gridDim.x);
         // pass A: maximum and its first position
-        float bv = -INFINITY; int bi = 0x7fffffff; float xl = 0.f; bool mine = false;
+        ArgFirst am; float xl = 0.f; bool mine = false;
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int c = tid * 8 + 2048 * q + k;
-                if (e[q * 8 + k] > bv) { bv = e[q * 8 + k]; bi = c; }
+                am.take(e[q * 8 + k], c);
                 if (c == lab) { xl = e[q * 8 + k]; mine = true; }
             }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_down(bv, o, 64); const int oi = __shfl_down(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
+        am.wave_merge();
         __syncthreads();                                 // (s_* of the previous row have been read)
-        if (lane == 0) { s_m[wave] = bv; s_bi[wave] = bi; }
         if (mine) s_xl = xl;
-        __syncthreads();
-        bv = s_m[0]; bi = s_bi[0];
-#pragma unroll
-        for (int w = 1; w < 4; ++w) if (s_m[w] > bv || (s_m[w] == bv && s_bi[w] < bi)) { bv = s_m[w]; bi = s_bi[w]; }
-        const float m = bv;
+        am.block_merge<4, true>(s_m, s_bi);
+        const float m = am.v; const int bi = am.i;
         // pass B: one exponential per element, kept
         float s = 0.f;
 #pragma unroll
@@ -909,7 +893,7 @@ __global__ __launch_bounds__(256) void softmax_ce_h16_kernel(CeArgs a)
             for (int k = 0; k < 8; ++k) { e[q * 8 + k] = exp_fast(e[q * 8 + k] - m); t += e[q * 8 + k]; }
             s += t;
         }
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+        s = wave_sum(s);
         if (lane == 0) s_s[wave] = s;
         __syncthreads();
         s = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
@@ -920,8 +904,6 @@ __global__ __launch_bounds__(256) void softmax_ce_h16_kernel(CeArgs a)
             if (a.pred) a.pred[row] = bi;
         }
         // pass C: (softmax - onehot) * scale as bf16 (RNE), over the panel
-        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-        typedef float f2 __attribute__((ext_vector_type(2)));
         const float g = scale / s;
         uint4* const out = reinterpret_cast<uint4*>(a.grad16 + (size_t)row * a.V);
 #pragma unroll
@@ -930,10 +912,8 @@ __global__ __launch_bounds__(256) void softmax_ce_h16_kernel(CeArgs a)
             if (c >= a.V) break;
             unsigned pk[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f2 v = {e[q * 8 + 2 * k] * g - ((c + 2 * k) == lab ? scale : 0.f), e[q * 8 + 2 * k + 1] * g - ((c + 2 * k + 1) == lab ? scale : 0.f)};
-                pk[k] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2));
-            }
+            for (int k = 0; k < 4; ++k)
+                pk[k] = pack_bf16(e[q * 8 + 2 * k] * g - ((c + 2 * k) == lab ? scale : 0.f), e[q * 8 + 2 * k + 1] * g - ((c + 2 * k + 1) == lab ? scale : 0.f));
             out[c >> 3] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
         }
     }
@@ -953,36 +933,36 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(CeArgs a)
         float* x = a.logits + (size_t)row * a.V;
         const _Float16* x16 = reinterpret_cast<const _Float16*>(a.grad16) + (size_t)row * a.V;      // (logits16, see the register form)
         const int label = a.gold[a.cidx[row]];
-        float m = -INFINITY, s = 0.f, bv = -INFINITY; int bi = 0x7fffffff;
+        float m = -INFINITY, s = 0.f; ArgFirst am;
         for (int c = tid * 4; c < a.V; c += 1024) {
             const float4 v = a.logits16 ? half4_to_float4(*reinterpret_cast<const uint2*>(x16 + c)) : *reinterpret_cast<const float4*>(x + c);
             float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if (e[k] > bv) { bv = e[k]; bi = c + k; }
+                am.take(e[k], c + k);
                 float nm = fmaxf(m, e[k]);
                 s = s * expf(m - nm) + expf(e[k] - nm);
                 m = nm;
             }
         }
+        // (the online max / sum-exp pair keeps its own merge and its __shfl_down tree: not lse_merge's arithmetic)
         for (int o = 32; o > 0; o >>= 1) {
             float om = __shfl_down(m, o, 64), os = __shfl_down(s, o, 64);
-            float ov = __shfl_down(bv, o, 64); int oi = __shfl_down(bi, o, 64);
             float nm = fmaxf(m, om);
             s = (nm == -INFINITY) ? 0.f : s * expf(m - nm) + os * expf(om - nm);
             m = nm;
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
         }
+        am.wave_merge();
         __syncthreads();
-        if (lane == 0) { s_m[wave] = m; s_s[wave] = s; s_bv[wave] = bv; s_bi[wave] = bi; }
-        __syncthreads();
-        m = s_m[0]; s = s_s[0]; bv = s_bv[0]; bi = s_bi[0];
+        if (lane == 0) { s_m[wave] = m; s_s[wave] = s; }
+        am.block_merge<4, true>(s_bv, s_bi);
+        const int bi = am.i;
+        m = s_m[0]; s = s_s[0];
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
             float nm = fmaxf(m, s_m[w]);
             s = s * expf(m - nm) + s_s[w] * expf(s_m[w] - nm);
             m = nm;
-            if (s_bv[w] > bv || (s_bv[w] == bv && s_bi[w] < bi)) { bv = s_bv[w]; bi = s_bi[w]; }
         }
         const float lse = m + logf(s);
         if (tid == 0) {
@@ -999,13 +979,9 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(CeArgs a)
                 float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) e[k] = (expf(e[k] - lse) - ((c + k) == label ? 1.f : 0.f)) * scale;
-                if (a.grad16) {      // bf16 mode: the GEMM operand panel itself (RNE, what the conversion pass would have written)
-                    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-                    const f2 lo = {e[0], e[1]}, hi = {e[2], e[3]};
-                    const uint2 pk = make_uint2(__builtin_bit_cast(unsigned, __builtin_convertvector(lo, bf2)), __builtin_bit_cast(unsigned, __builtin_convertvector(hi, bf2)));
-                    *reinterpret_cast<uint2*>(a.grad16 + (size_t)row * a.V + c) = pk;
-                } else
+                if (a.grad16)        // bf16 mode: the GEMM operand panel itself (RNE, what the conversion pass would have written)
+                    *reinterpret_cast<uint2*>(a.grad16 + (size_t)row * a.V + c) = make_uint2(pack_bf16(e[0], e[1]), pack_bf16(e[2], e[3]));
+                else
                 *reinterpret_cast<float4*>(x + c) = make_float4(e[0], e[1], e[2], e[3]);
             }
         }
@@ -1034,22 +1010,15 @@ hipError_t softmax_ce(hipStream_t st, const CeArgs& a)
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ logits, int32_t* __restrict__ pred, int n, int V)
 {
     __shared__ float s_bv[4]; __shared__ int s_bi[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     for (int row = blockIdx.x; row < n; row += gridDim.x) {
         const float* x = logits + (size_t)row * V;
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int c = tid; c < V; c += 256) { float v = x[c]; if (v > bv) { bv = v; bi = c; } }
-        for (int o = 32; o > 0; o >>= 1) {
-            float ov = __shfl_down(bv, o, 64); int oi = __shfl_down(bi, o, 64);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
+        ArgFirst am;
+        for (int c = tid; c < V; c += 256) am.take(x[c], c);
+        am.wave_merge();
         __syncthreads();
-        if (lane == 0) { s_bv[wave] = bv; s_bi[wave] = bi; }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; ++w) if (s_bv[w] > bv || (s_bv[w] == bv && s_bi[w] < bi)) { bv = s_bv[w]; bi = s_bi[w]; }
-            pred[row] = bi;
-        }
+        am.block_merge<4, false>(s_bv, s_bi);
+        if (tid == 0) pred[row] = am.i;
     }
 }
 hipError_t argmax_rows(hipStream_t st, const float* logits, int32_t* pred, int n, int V)
@@ -1070,8 +1039,8 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
                                                           int32_t* __restrict__ pred, float* __restrict__ logp)
 {
     __shared__ unsigned s_sel[258];
-    __shared__ float s_f[4][4]; __shared__ int s_i[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float s_pick[5 * 4];
+    const int tid = threadIdx.x;
     const uint64_t key = sample_key(sp.seed);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {
         if (lead && t > 0 && lead[row] == eos) {                  // (uniform over the workgroup)
@@ -1082,33 +1051,14 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
         unsigned thr = 0;                                         // keep everything (NaN: see below)
         if (sp.top_k > 0 && sp.top_k < V)
             thr = kth_largest_key([&](auto f) { for (int c = tid; c < V; c += 256) f(order_key(x[c])); }, (unsigned)sp.top_k, s_sel);
-        const uint64_t base = sample_base(row, t);
-        float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
-        for (int c = tid; c < V; c += 256) {
-            const float l = x[c];
-            if (l != l || order_key(l) < thr) continue;
-            const float xs = l * sp.inv_t;
-            const float sc = sp.noise ? xs + gumbel(key, base, c) : l;
-            if (sc > best) { best = sc; besti = c; bx = xs; }      // ascending c: the first maximum stays
-            lse_add(m, s, xs);
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-            const int oi = __shfl_xor(besti, o, 64);
-            if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
-            lse_merge(m, s, om, os);
-        }
-        __syncthreads();
-        if (lane == 0) { s_f[wave][0] = best; s_f[wave][1] = bx; s_f[wave][2] = m; s_f[wave][3] = s; s_i[wave] = besti; }
-        __syncthreads();
+        Pick p = pick_kept([&](auto f) { for (int c = tid; c < V; c += 256) { const float l = x[c]; if (l == l) f(c, l); } },
+                           thr, sp.inv_t, sp.noise != 0, key, sample_base(row, t));
+        p.wave_merge();
+        __syncthreads();                                          // (s_pick of the previous row has been read)
+        p.block_merge<4>(s_pick);
         if (tid == 0) {
-            for (int w = 1; w < 4; ++w) {
-                if (cand_better(s_f[w][0], s_i[w], best, besti)) { best = s_f[w][0]; besti = s_i[w]; bx = s_f[w][1]; }
-                lse_merge(m, s, s_f[w][2], s_f[w][3]);
-            }
-            const bool none = besti == 0x7fffffff;
-            pred[row] = none ? 0 : besti;
-            if (logp) logp[row] = none ? __int_as_float(0x7fc00000) : lse_logp(bx, m, s);
+            pred[row] = p.token();
+            if (logp) logp[row] = p.none() ? __int_as_float(0x7fc00000) : p.logp();
         }
     }
 }
@@ -1133,7 +1083,7 @@ __global__ __launch_bounds__(256) void sample_rows_p_kernel(const float* __restr
 {
     __shared__ unsigned s_sel[258];
     __shared__ unsigned long long s_mass[260];
-    __shared__ float s_f[4][4]; __shared__ int s_i[4]; __shared__ float s_mx[4];
+    __shared__ float s_pick[5 * 4], s_mx[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint64_t key = sample_key(sp.seed);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {
@@ -1162,7 +1112,7 @@ __global__ __launch_bounds__(256) void sample_rows_p_kernel(const float* __restr
             thr = kth_largest_key([&](auto f) { each([&](int, int, float l) { f(order_key(l)); }); }, (unsigned)sp.top_k, s_sel);
         float mx = -INFINITY;
         each([&](int, int, float l) { if (order_key(l) >= thr) mx = fmaxf(mx, l * sp.inv_t); });
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        mx = wave_max(mx);
         if (lane == 0) s_mx[wave] = mx;
         __syncthreads();
         mx = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
@@ -1178,34 +1128,15 @@ __global__ __launch_bounds__(256) void sample_rows_p_kernel(const float* __restr
                 if constexpr (kReg) f(k, wt[i]); else f(k, mass_weight(l * sp.inv_t, mx));
             });
         }, top_p, s_mass, &nk);
-        const uint64_t base = sample_base(row, t);
-        float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
-        each([&](int, int c, float l) {
-            if (order_key(l) < thr) return;
-            const float xs = l * sp.inv_t;
-            const float sc = xs + gumbel(key, base, c);
-            if (sc > best) { best = sc; besti = c; bx = xs; }      // ascending c: the first maximum stays
-            lse_add(m, s, xs);
-        });
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64), om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-            const int oi = __shfl_xor(besti, o, 64);
-            if (cand_better(ob, oi, best, besti)) { best = ob; besti = oi; bx = ox; }
-            lse_merge(m, s, om, os);
-        }
-        if (lane == 0) { s_f[wave][0] = best; s_f[wave][1] = bx; s_f[wave][2] = m; s_f[wave][3] = s; s_i[wave] = besti; }
-        __syncthreads();
+        Pick p = pick_kept([&](auto f) { each([&](int, int c, float l) { f(c, l); }); }, thr, sp.inv_t, true, key, sample_base(row, t));
+        p.wave_merge();
+        p.block_merge<4>(s_pick);
         if (tid == 0) {
-            for (int w = 1; w < 4; ++w) {
-                if (cand_better(s_f[w][0], s_i[w], best, besti)) { best = s_f[w][0]; besti = s_i[w]; bx = s_f[w][1]; }
-                lse_merge(m, s, s_f[w][2], s_f[w][3]);
-            }
-            const bool none = besti == 0x7fffffff;
-            pred[row] = none ? 0 : besti;
-            if (logp) logp[row] = none ? __int_as_float(0x7fc00000) : lse_logp(bx, m, s);
+            pred[row] = p.token();
+            if (logp) logp[row] = p.none() ? __int_as_float(0x7fc00000) : p.logp();
             if (nkept) nkept[row] = (int)nk;
         }
-        __syncthreads();                                          // s_f, s_i and s_mx are free for the next row
+        __syncthreads();                                          // s_pick and s_mx are free for the next row
     }
 }
 hipError_t sample_rows_p(hipStream_t st, const float* logits, int n, int V, int t, const SampleParams& sp, float top_p, const int32_t* lead,

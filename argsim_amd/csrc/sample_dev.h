@@ -1,8 +1,10 @@
-// sample_dev.h -- device helpers shared by the two samplers (decode.hip: the persistent launch; ops.hip: sample_rows):
-// the counter RNG's mixer, the Gumbel noise of stream 3, order-preserving keys with a workgroup radix select of the
-// k-th largest and one by probability mass (the nucleus), and the running (max, sum exp) pair of a log-sum-exp.  The
-// contract is in include/argsim_vae.h (avae_decode_sample, avae_decode_sample_p); both samplers and the float64
-// references of tests/sampling_ref.py and tests/nucleus_ref.py implement exactly it.
+// sample_dev.h -- device helpers shared by the samplers (decode.hip: the persistent launch; ops.hip: sample_rows, sample_rows_p),
+// beam.hip and score.hip: the counter RNG (mixer, uniform, normal) and the Gumbel noise of stream 3, order-preserving keys with a
+// workgroup radix select of the k-th largest and one by probability mass (the nucleus), the running (max, sum exp) pair of a
+// log-sum-exp, the tie rule cand_better, and the samplers' pick: struct Pick (candidate + log-sum-exp with its wave and workgroup
+// merges) and pick_kept, the final pass over a kept set.  The generic reductions are in reduce_dev.h, which includes this file.
+// The contract is in include/argsim_vae.h (avae_decode_sample, avae_decode_sample_p); both samplers and the float64 references of
+// tests/sampling_ref.py and tests/nucleus_ref.py implement exactly it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -168,7 +170,66 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
 // log-softmax value of x under (m, s)
 __device__ __forceinline__ float lse_logp(float x, float m, float s) { return (x == m ? 0.f : x - m) - logf(s); }
 
-// candidate (score, id) merge: larger score, then smaller id (the first maximum)
+// candidate (score, id) merge: larger score, then smaller id (the first maximum).  THE tie rule of every row kernel: pred is the
+// first maximum, beam search at width 1 equals greedy, top_p 0 equals avae_decode_sample bit for bit.  ArgFirst (reduce_dev.h) and
+// Pick below merge through it and nothing else spells it out.
 __device__ __forceinline__ bool cand_better(float sc, int id, float best, int besti) { return sc > best || (sc == best && id < besti); }
+
+// what a sampler keeps per thread, wave and workgroup: the best candidate (score, id) with its scaled logit bx = l inv_t, and the
+// running log-sum-exp (m, s) of the scaled logits of the whole kept set -- the token and its log-probability
+struct Pick {
+    float best = -INFINITY, bx = 0.f, m = -INFINITY, s = 0.f; int besti = 0x7fffffff;
+    // a thread's own scan in ascending id order: strict >, so the first maximum stays and a NaN score never enters
+    __device__ __forceinline__ void take(float sc, int id, float xs)
+    {
+        if (sc > best) { best = sc; besti = id; bx = xs; }
+        lse_add(m, s, xs);
+    }
+    __device__ __forceinline__ void merge(const Pick& o)
+    {
+        if (cand_better(o.best, o.besti, best, besti)) { best = o.best; besti = o.besti; bx = o.bx; }
+        lse_merge(m, s, o.m, o.s);
+    }
+    // butterfly over aligned groups of W lanes (64: the wave; 8: decode mode 1, whose lanes 8.. hold the neutral element), in every lane
+    template <int W = 64>
+    __device__ __forceinline__ void wave_merge()
+    {
+#pragma unroll
+        for (int o = W / 2; o > 0; o >>= 1)
+            merge(Pick{__shfl_xor(best, o, 64), __shfl_xor(bx, o, 64), __shfl_xor(m, o, 64), __shfl_xor(s, o, 64), __shfl_xor(besti, o, 64)});
+    }
+    // over the NW waves of the workgroup, after wave_merge(): lane 0 of wave w stores its record at sh[5 w .. 5 w + 4] (5 NW words of
+    // LDS), ONE barrier, then thread 0 merges waves 1 .. NW-1 into its own in that order (a sequential LSE merge: the order is part of
+    // the result's bits).  Every thread must call it; the result is valid on thread 0.  No barrier before the stores and none after the
+    // sweep: the caller keeps sh free on both sides.
+    template <int NW>
+    __device__ __forceinline__ void block_merge(float* sh)
+    {
+        if ((threadIdx.x & 63) == 0) {
+            float* r = sh + 5 * (threadIdx.x >> 6);
+            r[0] = best; r[1] = bx; r[2] = m; r[3] = s; r[4] = __int_as_float(besti);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int w = 1; w < NW; ++w) { const float* r = sh + 5 * w; merge(Pick{r[0], r[1], r[2], r[3], __float_as_int(r[4])}); }
+    }
+    __device__ __forceinline__ bool none() const { return besti == 0x7fffffff; }      // nothing above -inf was offered
+    __device__ __forceinline__ int token() const { return none() ? 0 : besti; }
+    __device__ __forceinline__ float logp() const { return lse_logp(bx, m, s); }
+};
+
+// the samplers' final pass over a kept set: each(f) calls f(id, l) for every logit of THIS thread that is a number, in ascending id;
+// kept = order_key(l) >= thr; score = l inv_t + Gumbel noise of (key, base, id), without noise l itself.  Returns the thread's Pick.
+template <class Each>
+__device__ __forceinline__ Pick pick_kept(Each each, unsigned thr, float inv_t, bool noise, uint64_t key, uint64_t base)
+{
+    Pick p;
+    each([=, &p](int id, float l) {
+        if (order_key(l) < thr) return;
+        const float xs = l * inv_t;
+        p.take(noise ? xs + gumbel(key, base, id) : l, id, xs);
+    });
+    return p;
+}
 
 }  // namespace avae

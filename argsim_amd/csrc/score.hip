@@ -5,18 +5,12 @@
 // same inputs give the same bits.
 #include <algorithm>
 #include "kernels.h"
+#include "reduce_dev.h"
 #include "sample_dev.h"
 
 namespace avae {
 
 constexpr uint64_t kScoreStream = 4;      // of the counter generator (sample_dev.h: normal01)
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // ---------------------------------------------------------------- draw
 // One workgroup per (k, r): z = mu[r] + exp(lv[r] / 2) eps[k, r] into the row the pair has in the decoder batches
@@ -97,8 +91,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(ScoreRows a)
         if (c >= 0) { s += a.loss[c]; ++cnt; }
     }
     s = wave_sum(s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = wave_sum(cnt);
     if (lane == 0) {
         const int kk = a.k0 + j / a.rc, r = a.r0 + j % a.rc;
         a.logpx[(size_t)kk * a.B + r] = -s;
@@ -126,8 +119,7 @@ __global__ __launch_bounds__(256) void score_bound_kernel(const float* __restric
         if (logw) logw[i] = w;
         m = fmaxf(m, w);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     float s = 0.f;
     for (int kk = lane; kk < k; kk += 64) {
         const size_t i = (size_t)kk * B + r;

@@ -151,6 +151,29 @@ def test_temperature_0_and_top_k_1_are_the_greedy_ids(name, b, persistent):
         m.set_option('persistent', 1)
 
 
+def test_greedy_takes_the_first_of_bit_equal_logits_in_two_vocabulary_blocks():
+    """embedding row v + V/2 = row v: every logit has a bit-equal twin in a higher vocabulary block (another workgroup of the
+    persistent launch, whose final merge over the blocks must keep the FIRST maximum; another column of the per-token logits for
+    argmax_rows).  Both paths emit only ids < V/2, and the same ones."""
+    from argsim_amd.model import VAE
+    cfg, P, z = _model('tiny')[1:]
+    V = cfg['dim_tgt']
+    P = dict(P)
+    E = P['embed/embedding'].copy()
+    E[V // 2:] = E[:V // 2]
+    P['embed/embedding'] = E
+    m = VAE('infer', init=False, **{k: cfg[k] for k in KEYS})
+    m.set_params(P)
+    out = {}
+    for persistent in (1, 0):
+        m.set_option('persistent', persistent)
+        out[persistent] = m.decode(z[:4], steps=16)
+        print("persistent %d: %s ids, max %d" % (persistent, out[persistent].shape, out[persistent].max(initial=-1)))
+        assert out[persistent].shape[1] >= 1 and (out[persistent] < V // 2).all()
+    m.close()
+    assert out[1].shape == out[0].shape and np.array_equal(out[1], out[0])
+
+
 @pytest.mark.parametrize("persistent", [1, 0])
 def test_same_seed_same_bits_and_rows_and_step_caps_are_independent(persistent):
     m, cfg, P, z = _model('prod')
