@@ -58,7 +58,7 @@ struct avae_ctx {
     int shared_device = 0; int lock_fd = -1;      // option shared_device: persistent launches are taken one at a time ACROSS processes (DeviceTurn)
     int dyn_split = 1;    // ragged batches: narrow backward GEMMs over few expected rows split K instead of leaving the chip at one workgroup per CU (gemm())
     int dyn_thin = 1;     // device-row-count GEMMs with a narrow output run 64x64 tiles (gemm())
-    int enc_top1 = 1;     // the top encoder layer's backward direction runs its ONE live step only (gru.hip "one step from a zero state"); 0: all S steps like the reference's graph
+    int enc_top1 = 1;     // the top encoder layer's backward direction runs its ONE live step only (gru_reg.hip "one step from a zero state"); 0: all S steps like the reference's graph
     int table_l1 = 1;     // layers fed by embedding rows project the TABLE once and gather / scatter by id where a batch has more tokens than the vocabulary (use_table)
     int bf16_act = 1;     // compute_dtype 1: h / h_prev row-major copies written as bf16 by the forward team kernels (the GEMM operands as they stand)
     int bf16_sv = 1;      // compute_dtype 1: saved gates as bf16 where a layer's forward and backward both run the team kernels
@@ -119,7 +119,7 @@ namespace avae { namespace host {
 
 inline int fail(avae_ctx* h, const std::string& m) { h->err = m; return 1; }
 
-// persistent GRU launches: the residency check of gru.hip answers hipErrorCooperativeLaunchTooLarge
+// persistent GRU launches: the residency check of the GRU launchers (gru_dev.h) answers hipErrorCooperativeLaunchTooLarge
 #define AV_GRU(expr)                                                                                                \
     do { hipError_t e_ = (expr);                                                                                    \
          if (e_ == hipErrorCooperativeLaunchTooLarge)                                                               \

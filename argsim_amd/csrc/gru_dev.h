@@ -1,6 +1,7 @@
-// gru_dev.h -- device-side helpers shared by the GRU kernel files (gru.hip, gru_rs.hip): fragment loads with the in-band
+// gru_dev.h -- device-side helpers shared by the GRU kernel files (gru.hip, gru_reg.hip, gru_team.hip, gru_rs.hip): fragment loads with the in-band
 // "not yet written" check, buffer-instruction wrappers, bounded spins, the same-XCD rendezvous, the tiled exchange index maps,
-// team barriers and the team-kernel workgroup map.  Internal; not part of the C ABI.
+// team barriers, the team-kernel workgroup map, the forward and backward cell, and the shared part of the team kernels' scaffold.
+// Internal; not part of the C ABI.
 #pragma once
 #include <type_traits>
 #include "kernels.h"
@@ -32,16 +33,13 @@ __device__ __forceinline__ bool any_half_sentinel(unsigned mx) { return (mx & 0x
 // bf16-operand mode in the register-form kernels: the operand keeps its fp32 register but carries a bf16 value (products of
 // two such values are exact in fp32, so these kernels and the team kernels' bf16 MFMA differ only in summation order)
 __device__ __forceinline__ float opnd(float x, bool bf) { return bf ? __uint_as_float(pack_bf16(0.f, x)) : x; }
-// eight floats (two 16-byte pieces of an MFMA A fragment) -> one v_mfma_f32_16x16x32_bf16 operand.  Which k a slot
-// stands for is the caller's business: the B operand in LDS is packed with the same slot order.
-__device__ __forceinline__ bf16x8 pack_bf16x8(const u32x4& p0, const u32x4& p1)
-{
-    const u32x4 v = {pack_bf16(__uint_as_float(p0.x), __uint_as_float(p0.y)), pack_bf16(__uint_as_float(p0.z), __uint_as_float(p0.w)),
-                     pack_bf16(__uint_as_float(p1.x), __uint_as_float(p1.y)), pack_bf16(__uint_as_float(p1.z), __uint_as_float(p1.w))};
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 constexpr unsigned kSentinel = 0xFFFFFFFFu;
+#ifdef AVAE_DIAG
+constexpr bool kDiagBuild = true;
+#else
+constexpr bool kDiagBuild = false;
+#endif
 
 // An exchanged value must never alias the "not yet written" pattern: a NaN that reaches the gate math with every
 // payload bit set (e.g. from a poisoned parameter) would otherwise make every consumer spin until its 2 s bound.
@@ -71,6 +69,20 @@ __device__ __forceinline__ GruCellOut gru_cell(float gi_r, float gi_u, float gi_
     return c;
 }
 
+// The gate derivatives of one cell, shared by every backward kernel form:
+//   dn = dH (1-u)(1-n^2)   du = dH (h_prev - n) u (1-u)   dr = dn hn r (1-r)     dgi = [dr, du, dn]   dgh = [dr, du, dn r]
+// The two products left to the caller -- dn r, and dH u, what the step before inherits through the update gate -- are formed where
+// they are stored: computed up here they moved in the instruction stream of every kernel.
+struct GruCellGrad { float dr, du, dn; };
+__device__ __forceinline__ GruCellGrad gru_cell_bwd(float dH, float r, float u, float n, float hn, float hprev)
+{
+    GruCellGrad g;
+    g.dn = dH * (1.f - u) * (1.f - n * n);
+    g.du = dH * (hprev - n) * u * (1.f - u);
+    g.dr = g.dn * hn * r * (1.f - r);
+    return g;
+}
+
 // k offset (inside one wave's contiguous K range) of MFMA step ks for lane quarter kh
 template <int NKS>
 __device__ __forceinline__ int kperm(int ks, int kh)
@@ -79,9 +91,9 @@ __device__ __forceinline__ int kperm(int ks, int kh)
     return 4 * ks + kh;
 }
 
-// diagnostic phase stamps (ablate bit 32): 100 MHz real-time counter deltas summed per workgroup
-// (compile-time: the production instantiation carries no stamp code at all)
-#define AVAE_STAMP(i) do { if constexpr (STAMPS) { unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); ph[i] += t_ - tprev; tprev = t_; } } while (0)
+// diagnostic phase stamps: 100 MHz real-time counter deltas summed per workgroup into the caller's ph[] / tprev.  `on` is a
+// template flag (the production instantiation then carries no stamp code at all) or a run-time flag of a diagnostic instantiation.
+#define GRU_STAMP(on, i) do { if (on) { unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); ph[i] += t_ - tprev; tprev = t_; } } while (0)
 
 __device__ __forceinline__ u32x4 load16_sc1(__amdgpu_buffer_rsrc_t rsrc, unsigned byte_off)
 {
@@ -90,6 +102,7 @@ __device__ __forceinline__ u32x4 load16_sc1(__amdgpu_buffer_rsrc_t rsrc, unsigne
 // Buffer forms of the gate-phase accesses: 32-bit byte offsets against a wave-uniform descriptor.  On the texture
 // addresser a buffer instruction costs about half of the global (64-bit address per lane) form of the same access
 // (scripts/micro/ta_cost.hip: x4 store of 4 rows x 256 B 43 vs 83 cycles, dword store 31 vs 63).
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 __device__ __forceinline__ float bload1(__amdgpu_buffer_rsrc_t rs, unsigned off) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0)); }
 __device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t rs, unsigned off)
@@ -139,30 +152,7 @@ struct SpinGuard {
     }
 };
 
-// Loads NQ 16-byte pieces (stride 64 B) of one row per lane and repeats until no dword of the
-// WAVE's fragment equals the sentinel (poll == false: single pass).
-template <int NQ>
-__device__ __forceinline__ void load_frag(float* dst, __amdgpu_buffer_rsrc_t rs, unsigned off, bool poll, int* err)
-{
-    SpinGuard sg;
-    for (;;) {
-        u32x4 v[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v[q] = load16_sc1(rs, off + 64u * q);
-        bool bad = false;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) bad |= (v[q].x == kSentinel) | (v[q].y == kSentinel) | (v[q].z == kSentinel) | (v[q].w == kSentinel);
-        if (!poll || !__any(bad) || sg.expired(err)) {
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                dst[4 * q + 0] = __uint_as_float(v[q].x); dst[4 * q + 1] = __uint_as_float(v[q].y);
-                dst[4 * q + 2] = __uint_as_float(v[q].z); dst[4 * q + 3] = __uint_as_float(v[q].w);
-            }
-            return;
-        }
-    }
-}
-// Pipelined form: the loads of a fragment are ISSUED (no wait) and the fragment is verified later, at its
+// The loads of a fragment are ISSUED (no wait) and the fragment is verified later, at its
 // first use.  Written so that hipcc's waitcnt insertion stays counted on the fast path: younger fragments
 // issued in straight-line code before the check stay in flight (vmcnt(N)); only the rare re-load loop,
 // which consumes what it loads inside the loop, waits for everything.
@@ -233,6 +223,12 @@ __device__ __forceinline__ void frag_ensure16(u32x4 (&v)[NQ], __amdgpu_buffer_rs
 // s_waitcnt statements that name the destination registers, and are fully retired before the code leaves
 // the block that issued them (cdna_hip_programming.md section 5.7 forms (ii)/(iii)).
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+// the buffer descriptor of a whole address space behind p, as the inline-asm loads take it
+__device__ __forceinline__ i32x4 make_srd(const float* p)
+{
+    const unsigned long long pa = (unsigned long long)p;
+    return (i32x4){(int)(unsigned)(pa & 0xffffffffULL), (int)(unsigned)((pa >> 32) & 0xffffULL), -1, 0x00020000};
+}
 template <int OFF>
 __device__ __forceinline__ void asm_issue6(u32x4 (&v)[6], unsigned voff, i32x4 srd)
 {
@@ -439,6 +435,52 @@ __device__ __forceinline__ int team_steps(const int* slens, int row0, int lane)
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) v = max(v, __shfl_xor(v, o, 64));
     return __builtin_amdgcn_readfirstlane(v);
+}
+
+// ---- the scaffold the three 1024-thread team kernels share (gru_fwd_team_kernel, gru_bwd_team_kernel, gru_bwd_rs_kernel).
+// hipcc optimises a helper on its own before it inlines it, and these hand-scheduled kernels then come out with other code (commuted
+// scalar adds, selects for branches, another order of the loop-edge copies).  What is shared here is what left every kernel's
+// instructions as they were; the step counts per row block, the per-row-block registers, the zero fill behind a row block's steps and
+// the bias-gradient epilogue did not, in any spelling tried, and stay written out in the kernels.
+
+// wave -> (team, K-split index; reduce-scatter form: wave of the team), as constants the kernels apply themselves:
+//     team = (wave >> team_shift) & team_mask,   wk = (wave & wk_mask) + wk_mul * (wave >> wk_shift)
+// Waves w and w + 4 share a SIMD; a team's K-split partners meet at a barrier every step.  Which SIMDs a team sits on is a 1-3 % effect
+// since the operand loads stopped saturating the texture addresser; the mapping per form is the best of {one SIMD, a SIMD pair, all
+// four} measured in-process (scripts/ab_classes.py).  CMP = the compact layout, i.e. a ragged batch: teams run
+// out of steps at different times and the ones still running should have every SIMD -- the pipelined forms at 1024 x 64 RAGGED:
+// 32.97 -> 30.37 ms with all four, FULL 59.06 -> 59.88.  The reduce-scatter kernel's waves split N, not K, and always sit on all four.
+enum class TeamKernel { fwd, bwd, rs };
+struct WaveSplit { int team_shift, team_mask, wk_mask, wk_mul, wk_shift; };
+constexpr WaveSplit team_wave_split(TeamKernel k, int T, bool pipe, bool cmp)
+{
+    const bool packed = k != TeamKernel::rs && pipe && !cmp;
+    if (T == 4 && packed) return {0, 3, 0, 1, 2};         // one SIMD:       team = wave & 3,        wk = wave >> 2
+    if (T == 4) return {2, 3, 3, 0, 0};                   // all four SIMDs: team = wave >> 2,       wk = wave & 3   (forward, RAGGED 10.56 -> 10.43 ms; FULL unchanged)
+    if (packed) return {1, 1, 1, 2, 2};                   // a SIMD pair:    team = (wave >> 1) & 1, wk = (wave & 1) + 2 * (wave >> 2)
+    // T = 2 on all four SIMDs: a team whose partner has run out of steps (ragged batches) has the whole CU -- forward, RAGGED 256 x 64
+    // 10.76 -> 10.54 ms, FULL 16.50 -> 16.45
+    if (k == TeamKernel::fwd) return {2, 1, 3, 4, 3};     //                 team = (wave >> 2) & 1, wk = (wave & 3) + 4 * (wave >> 3)
+    return {3, 1, 7, 0, 0};                               //                 team = wave >> 3,       wk = wave & 7
+}
+// one consistent arbitration order on all four SIMDs: a team's K-split partners sit on different SIMDs and meet at the team
+// barrier, so if every SIMD serves the teams in the same order the partners finish together (otherwise the barrier pays the
+// arbitration skew, measured at 2-3 us per step)
+__device__ __forceinline__ void team_set_priority(int team)
+{
+    const int tq = __builtin_amdgcn_readfirstlane(team);
+    if (tq == 0) __builtin_amdgcn_s_setprio(3);
+    else if (tq == 1) __builtin_amdgcn_s_setprio(2);
+    else if (tq == 2) __builtin_amdgcn_s_setprio(1);
+}
+// PIPE forms: the item after (p, r) -- the next row block that still has step p, else row block 0 of the next step (FWD: p + 1; the
+// backward runs downwards and its tail item p = -1 exists for every row block).  nst_of(r): steps of row block r.
+struct NextItem { int r, p; };
+template <bool FWD, class N>
+__device__ __forceinline__ NextItem team_next_item(N&& nst_of, int nrb, int p, int r)
+{
+    const bool same_p = r + 1 < nrb && ((!FWD && p < 0) || p < nst_of(r + 1));
+    return {same_p ? r + 1 : 0, same_p ? p : (FWD ? p + 1 : p - 1)};
 }
 
 // ---- host side: residency check and launch of the 1024-thread team kernels

@@ -51,15 +51,16 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_rs_kernel(GruArgs a)
 {
     constexpr int D = 512, HT = 32, KS = 16 / T, NT = 32 / KS, RB = 16 * T, AST = 52;
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int oAimg = 96 * 256, oRed = oAimg + T * 2 * 16 * AST, oSync = oRed + 64;      // float offsets into lds[]
+    static_assert((oSync + 2 * T) * 4 <= kRsLdsBytes<T>, "lds[] is carved inside the dynamic LDS the launch asks for");
     float* Wl = lds;                                        // [t 32][q 3][lane 64][4]: B fragments of R'[ht*48 + 16q + 4kh + e][16t + n]   96 KB
-    float* Aimg = Wl + 96 * 256;                            // [team T][buf 2][row 16][AST]: this step's dgh of the team's rows, the A operand
-    float* red = Aimg + T * 2 * 16 * AST;                   // [4][16] bias-gradient sums
-    unsigned* sync = reinterpret_cast<unsigned*>(red + 64); // [team T] barrier counters, [team T] exchange-ready epochs
+    float* Aimg = lds + oAimg;                              // [team T][buf 2][row 16][AST]: this step's dgh of the team's rows, the A operand
+    float* red = lds + oRed;                                // [4][16] bias-gradient sums
+    unsigned* sync = reinterpret_cast<unsigned*>(lds + oSync);       // [team T] barrier counters, [team T] exchange-ready epochs
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int team, wk;                                           // wave -> (team, wave of the team); waves w and w + 4 share a SIMD
-    if (T == 4) { team = wave >> 2; wk = wave & 3; }        // a team's waves on all four SIMDs
-    else        { team = wave >> 3; wk = wave & 7; }
+    constexpr WaveSplit ws = team_wave_split(TeamKernel::rs, T, PIPE, CMP);      // (placement: gru_dev.h)
+    const int team = (wave >> ws.team_shift) & ws.team_mask, wk = (wave & ws.wk_mask) + ws.wk_mul * (wave >> ws.wk_shift);
     const int n = lane & 15, kh = lane >> 4;
     const TeamMap tm = team_map(a, RB);
     const int cid = tm.cid, ht = tm.ht;
@@ -88,12 +89,7 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_rs_kernel(GruArgs a)
     unsigned* tsync = sync + team;
     unsigned* ready = sync + T + team;
     unsigned epoch = 0;
-    {
-        const int tq = __builtin_amdgcn_readfirstlane(team);      // one arbitration order on all four SIMDs (see gru.hip)
-        if (tq == 0) __builtin_amdgcn_s_setprio(3);
-        else if (tq == 1) __builtin_amdgcn_s_setprio(2);
-        else if (tq == 2) __builtin_amdgcn_s_setprio(1);
-    }
+    team_set_priority(team);
     const float* __restrict__ p_sv = J.sv;
     const float* __restrict__ p_hp = J.hp;
     const float* __restrict__ p_do = J.dh_out;
@@ -266,10 +262,9 @@ __global__ __launch_bounds__(1024, 4) void gru_bwd_rs_kernel(GruArgs a)
             if (p < 0) { if (inb) p_dh0[(size_t)ge_cur * D + j] = carried; }
             else {
                 const float dH = carried + s_do;
-                const float r_ = sv.x, u = sv.y, nn = sv.z;
-                const float dn = dH * (1.f - u) * (1.f - nn * nn);
-                const float du = dH * (s_hp - nn) * u * (1.f - u);
-                const float dr = dn * sv.w * r_ * (1.f - r_);
+                const float r_ = sv.x, u = sv.y;
+                const GruCellGrad cg = gru_cell_bwd(dH, r_, u, sv.z, sv.w, s_hp);
+                const float dr = cg.dr, du = cg.du, dn = cg.dn;
                 const float dnr = dn * r_;
                 if (produce) {      // the A operand of this step's product: position c' = 3 gn + gate of row gr
                     float* ap = timg + (buf * 16 + gr) * AST + gn * 3;

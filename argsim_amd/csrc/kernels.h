@@ -76,7 +76,7 @@ hipError_t gemm_bf16_tn(hipStream_t st, const unsigned short* A, int lda, const 
 // bf16 [K][X] (row stride ld) -> bf16 [X][ldk] (ldk = K rounded up to 8, pad zero-filled)
 hipError_t transpose_bf16(hipStream_t st, const unsigned short* src, int ld, int K, int X, unsigned short* dst, int ldk);
 
-// ---------------------------------------------------------------- GRU (gru.hip)
+// ---------------------------------------------------------------- GRU (gru.hip; kernels in gru_reg.hip, gru_team.hip, gru_rs.hip)
 // Gate-interleaved layout ("G16"): the 3D gate rows of W, R, bW, bR and the 3D columns of
 // gi / dgi / dgh are stored in the order  c' = ht*48 + u*3 + gate   (ht = unit/16, u = unit%16,
 // gate: 0=r 1=u 2=n) so that the 48 values one workgroup owns are contiguous and the three gates of
@@ -112,7 +112,7 @@ struct GruArgs {
     GruJob job[kMaxGruJobs];
     int njobs, S, B, D, ldg, ldh;
     const int* lens;      // (B) or nullptr
-    // optional, team kernels only (gru.hip "Padding skipped"): steps each SLOT really has and the batch row sitting in it;
+    // optional, team kernels only (gru_dev.h "Padding skipped"): steps each SLOT really has and the batch row sitting in it;
     // both or neither.  The other kernel forms ignore them and run every step of every row.
     const int* slens;     // (B) by slot
     const int* perm;      // (B) slot -> batch row
@@ -131,7 +131,7 @@ struct GruArgs {
     int* err;             // device error word (set on spin timeout)
     unsigned long long* stamps;   // 32 words of diagnostic phase sums (ablate bit 32) or nullptr
     int item_pipeline;    // 1: use the software-pipelined D = 512 forward kernel where its geometry applies
-    float* xbuf;          // scratch for the team kernels' exchange in MFMA-tile order (see gru.hip "tiled exchange"): at least
+    float* xbuf;          // scratch for the team kernels' exchange in MFMA-tile order (see gru_dev.h "tiled exchange"): at least
     size_t xbuf_floats;   // njobs*S*B*D floats (forward) / njobs*S*B*3D (backward); nullptr / too small: register-form kernels
     int stagger;          // 1: delay the second half of the grid by ~half a step (co-resident chains de-phased)
     int force_slow;       // 1: never use the same-XCD L2 fast path
@@ -162,7 +162,13 @@ bool gru_dim_supported(int D);
 // reduce-scatter form of the backward team kernels (gru_rs.hip): floats of exchange scratch it needs for njobs jobs over `rows` slots
 size_t gru_bwd_rs_xbuf_floats(int njobs, int rows);
 hipError_t gru_bwd_rs_launch(hipStream_t st, const GruArgs& a, const GruPlan& p);
-// one GRU step from a zero state for B rows (the top encoder layer's backward direction: gru.hip "one step from a zero
+// the launches gru_forward / gru_backward choose between, after planning and preparing the exchange: the team forms (gru_team.hip), the
+// register-resident forms (gru_reg.hip; grid = njobs * G * D/16 workgroups, need_resident: a persistent launch) and the item form
+hipError_t gru_fwd_team_launch(hipStream_t st, const GruArgs& a, const GruPlan& p);
+hipError_t gru_bwd_team_launch(hipStream_t st, const GruArgs& a, const GruPlan& p);
+hipError_t gru_reg_launch(hipStream_t st, const GruArgs& a, bool fwd, int grid, bool need_resident);
+hipError_t gru_fwd_item_launch(hipStream_t st, const GruArgs& a, int grid);
+// one GRU step from a zero state for B rows (the top encoder layer's backward direction: gru_reg.hip "one step from a zero
 // state"): gi (B, 3D) / bR G16; h -> h_out[b * ldo + j]; sv (B, D, 4) = r, u, n, hn or nullptr
 hipError_t gru_first_step_fwd(hipStream_t st, const float* gi, const float* bR, float* h_out, int ldo, float* sv, int B, int D, const int32_t* lens = nullptr);      // lens: rows of length 0 get h = 0
 // its backward: dh[b * ldd + j] -> dgi, dgh (B, 3D) G16
