@@ -1,5 +1,5 @@
-// clustering.cpp -- Ward clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
-// (contract: include/argsim_vae.h; kernels: ward.hip).
+// clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
+// (kernels: ward.hip) and of avae_affinity (kernels: affinity.hip).  Contract: include/argsim_vae.h.
 #include "ctx.h"
 
 using namespace avae;
@@ -100,6 +100,66 @@ int avae_ward_cut(avae_handle h, const int32_t* pair, const int32_t* group_off, 
     lay(real);
     AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardCutGroup), hipMemcpyHostToDevice, h->stream));
     AV_CHECK(ward_cut(h->stream, dev, G, nmax, pair, parent, label));
+    return 0;
+}
+
+int avae_affinity(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_affinity_config* ac, int32_t* label, int32_t* stat,
+                  float* s_out, float* a, float* r)
+{
+    if (!h) return 1;
+    if (!ac) return fail(h, "affinity config is null");
+    if (!x || !label || !stat) return fail(h, "affinity: x, label and stat must be given");
+    if (N < 1 || N > kApMaxN) return fail(h, "affinity: N must be in [1, 2^14]");
+    if (ac->metric < 0 || ac->metric > 2) return fail(h, "affinity: metric must be 0 (euclidean), 1 (cosine) or 2 (precomputed)");
+    if (ac->metric == 2) {
+        if (dim != N) return fail(h, "affinity: a precomputed similarity is (N, N): dim must equal N");
+    } else {
+        if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "affinity: dim must be a multiple of 4 in [4, 1024]");
+        if ((uintptr_t)x & 15) return fail(h, "affinity: x must be 16-byte aligned");
+    }
+    if (ac->max_iter < 1 || ac->max_iter > 10000) return fail(h, "affinity: max_iter must be in [1, 10000]");
+    if (ac->convergence_iter < 1 || ac->convergence_iter > ac->max_iter) return fail(h, "affinity: convergence_iter must be in [1, max_iter]");
+    if (!(ac->damping >= 0.5f && ac->damping < 1.f)) return fail(h, "affinity: damping must be in [0.5, 1)");
+    if ((a == nullptr) != (r == nullptr)) return fail(h, "affinity: a and r are given together or not at all");
+    if (ac->warm && !a) return fail(h, "affinity: a warm start reads a and r, which are not given");
+    if (ac->reserved[0] != 0 || ac->reserved[1] != 0) return fail(h, "affinity: the reserved fields must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    if (N == 1) { AV_CHECK(ap_single(h->stream, label, stat)); return 0; }
+    // Workspace, every buffer on a 256-byte boundary: S, A and R of 4 N^2 bytes each where the caller does not give
+    // the buffer itself, the column partials (row blocks x N doubles), five vectors of N and the state
+    const size_t n = (size_t)N, nblk = (n + ap_row_block(N) - 1) / ap_row_block(N);
+    ApBuffers b{};
+    auto lay = [&](Bump& bp) {
+        b.st = bp.take<ApState>(1);
+        b.S = s_out ? s_out : bp.take<float>(n * n);
+        b.A = a ? a : bp.take<float>(n * n);
+        b.R = r ? r : bp.take<float>(n * n);
+        b.part = bp.take<double>(nblk * n);
+        b.cv = bp.take<double>(n);
+        b.best = bp.take<unsigned long long>(n);
+        b.E = bp.take<int>(n); b.run = bp.take<int>(n); b.E2 = bp.take<int>(n);
+        b.c = bp.take<int32_t>(n);
+    };
+    Bump probe{nullptr};
+    lay(probe);
+    AV_TRY(reserve_named(h, probe.off + 4096, "affinity"));     // sized once per call; nothing is allocated between the launches
+    Bump real{h->ws};
+    lay(real);
+    AV_CHECK(hipMemsetAsync(b.st, 0, sizeof(ApState), h->stream));
+    AV_CHECK(hipMemsetAsync(b.E, 0, n * sizeof(int), h->stream));
+    if (!ac->warm) {
+        AV_CHECK(hipMemsetAsync(b.A, 0, n * n * sizeof(float), h->stream));
+        AV_CHECK(hipMemsetAsync(b.R, 0, n * n * sizeof(float), h->stream));
+    }
+    if (ac->metric == 2) {
+        if (b.S != x) AV_CHECK(hipMemcpyAsync(b.S, x, n * n * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    } else {
+        AV_CHECK(ap_similarity(h->stream, x, N, dim, ac->metric, b.S));
+    }
+    AV_CHECK(ap_prepare(h->stream, b.S, N, ac->use_preference, ac->preference, ac->noise, ac->seed, b.st));
+    // every round is enqueued; a launch that finds the stop decided returns at once.  Never a synchronisation
+    for (int it = 0; it < ac->max_iter; ++it) AV_CHECK(ap_iteration(h->stream, b, N, ac->damping, it, ac->convergence_iter));
+    AV_CHECK(ap_labels(h->stream, b, N, label, stat));
     return 0;
 }
 

@@ -432,6 +432,35 @@ hipError_t ward_tree(hipStream_t st, const WardGroup* gs, int G, int nmax, int d
 hipError_t ward_round(hipStream_t st, const WardGroup* gs, int G, int nmax, int dim, int t, int32_t* pair, float* delta, int32_t* size);      // launch-per-merge form: merge t of every group
 hipError_t ward_cut(hipStream_t st, const WardCutGroup* gs, int G, int nmax, const int32_t* pair, int32_t* p /* (N) workspace */, int32_t* label);
 
+// ---------------------------------------------------------------- affinity propagation of latent rows (affinity.hip)
+// One set of N rows per call (contract: include/argsim_vae.h, avae_affinity).  The buffers are workspace laid out by the caller
+// (clustering.cpp), or the caller's own s_out / a / r; the state is zero-filled before the first launch.
+constexpr int kApMaxN = 1 << 14;
+constexpr int kApMaxRB = 16;          // rows per workgroup of the row passes: ap_row_block(N) <= this for N <= kApMaxN
+struct ApState {
+    int stop_at;                      // 0: running; it + 1: iteration it ended the loop (a launch of a later iteration returns at once)
+    int iters, conv, K;               // iterations run, converged, exemplars of the last iteration run
+    int cnt[2][2];                    // by iteration parity: columns whose run is shorter than convergence_iter, exemplars
+    float pref;                       // the median, where the call asks for it
+    unsigned prefix[2], rank[2];      // radix select of the two middle ranks
+    unsigned hist[512];
+};
+struct ApBuffers {
+    float *S, *A, *R;                 // (N, N)
+    double* part;                     // (row blocks, N) column sums of max(0, R) over a block's rows i != k
+    double* cv;                       // (N) R_kk + the column's sum
+    int *E, *run, *E2;                // (N) exemplar flags, run lengths, the refined exemplars
+    int32_t* c;                       // (N) the first assignment
+    unsigned long long* best;         // (N) per exemplar: (order key of the refinement sum) << 32 | ~j
+    ApState* st;
+};
+int ap_row_block(int N);
+hipError_t ap_single(hipStream_t st, int32_t* label, int32_t* stat);                        // N = 1
+hipError_t ap_similarity(hipStream_t st, const float* x, int N, int dim, int metric, float* S);
+hipError_t ap_prepare(hipStream_t st, float* S, int N, int use_pref, float pref, int noise, uint64_t seed, ApState* state);      // median, diagonal, noise
+hipError_t ap_iteration(hipStream_t st, const ApBuffers& b, int N, float lam, int it, int conv_iter);      // three launches
+hipError_t ap_labels(hipStream_t st, const ApBuffers& b, int N, int32_t* label, int32_t* stat);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

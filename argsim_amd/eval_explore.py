@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""explorative clustering of the embeddings on the device (counterpart of reference src/eval_clustering_explorative.py:69-132):
+affinity propagation over all rows on Euclidean and on cosine similarities, for the embeddings and, where given, for the embeddings
+of the sampled segmentation; per run the topics' purity listing and the cluster count, then every row's distance to its cluster
+centroid, written with the cluster numbers as CSV.  Every run is ONE device call (VAE.affinity).
+
+    python -m argsim_amd.eval_explore --inputs data/test_data_emb.npy --labels data/test_labels.npy \\
+        [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
+
+The labels are eval_cluster's topic-stance-reason strings; the topics are listed in order of first appearance.  A purity line is the
+topic, then share|members|cluster for the clusters of which at least half the members (and at least two) belong to the topic."""
+import argparse
+import csv
+
+import numpy as np
+
+RUNS = (('euc', 'euclidean', 'sqeuclidean', False), ('euc_sp', 'euclidean', 'sqeuclidean', True), ('cos', 'cosine', 'cosine', False),
+        ('cos_sp', 'cosine', 'cosine', True))
+COLUMNS = "post topic labels cls_euc dist_euc cls_euc_sp dist_euc_sp cls_cos dist_cos cls_cos_sp dist_cos_sp".split()
+
+
+def purity_lines(pred, topics, order):
+    """the lines of eval_clustering_explorative.py:77-81 for one run"""
+    from . import affinity
+    lines = []
+    for topic in order:
+        cells = ["{:.3f}|{:03d}|{:03d}".format(acc, n, c) for c, n, acc in affinity.purity(pred, topics == topic)]
+        lines.append(" ".join([topic.ljust(9)] + cells))
+    return lines + ["%d clusters" % len(set(np.asarray(pred).tolist()))]
+
+
+def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200):
+    """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed"""
+    from . import affinity
+    from .eval_cluster import split_labels
+    topics = np.array([p[0] for p in split_labels(labels)])
+    order = list(dict.fromkeys(topics.tolist()))
+    cols, lines = {}, []
+    for name, metric, dist, sampled in RUNS:
+        x = z_sp if sampled else z
+        if x is None:
+            continue
+        res = vae.affinity(x, metric, max_iter=max_iter, seed=seed)
+        if not res['converged']:
+            lines.append("%s: did not converge in %d iterations" % (name, res['n_iter']))
+        lines += purity_lines(res['labels'], topics, order)
+        cols['cls_' + name] = res['labels']
+        cols['dist_' + name] = affinity.dist_to_centroids(x, res['labels'], dist)
+    return cols, lines
+
+
+def write_csv(path, posts, topics, labels, cols):
+    """eval_clustering_explorative.py:121-132: the id, then the columns in the reference's order (those of absent runs left out)"""
+    names = [c for c in COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
+    data = dict(cols, post=posts, topic=topics, labels=labels)
+    with open(path, 'w', newline='') as f:
+        w = csv.writer(f)
+        w.writerow(['id'] + names)
+        for i in range(len(labels)):
+            w.writerow([i] + [data[c][i] for c in names])
+
+
+def build_parser():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--inputs', required=True, help=".npy (n, dim) float32 embeddings (eval_embed's output)")
+    ap.add_argument('--labels', required=True, help=".npy (n,) strings topic-stance-reason")
+    ap.add_argument('--inputs-sp', default=None, help=".npy (n, dim) embeddings of the sampled segmentation: the two *_sp runs")
+    ap.add_argument('--posts', default=None, help=".npy (n,) the posts' text, for the CSV's post column (empty without)")
+    ap.add_argument('--csv', default=None, help="write the cluster numbers and centroid distances here")
+    ap.add_argument('--max-iter', type=int, default=200)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--device', type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    from .eval_cluster import make_vae, split_labels
+    A = build_parser().parse_args(argv)
+    z = np.ascontiguousarray(np.load(A.inputs), dtype=np.float32)
+    z_sp = np.ascontiguousarray(np.load(A.inputs_sp), dtype=np.float32) if A.inputs_sp else None
+    labels = np.load(A.labels)
+    if z.shape[0] != len(labels) or (z_sp is not None and z_sp.shape[0] != len(labels)):
+        raise ValueError("one label per row of the inputs")
+    cols, lines = evaluate(make_vae(A.device), z, z_sp, labels, A.seed, A.max_iter)
+    for line in lines:
+        print(line)
+    if A.csv:
+        posts = np.load(A.posts) if A.posts else np.array([''] * len(labels))
+        write_csv(A.csv, posts, [p[0] for p in split_labels(labels)], [str(v) for v in labels], cols)
+    return cols
+
+
+if __name__ == '__main__':
+    main()

@@ -73,6 +73,12 @@ class AvaeWardConfig(C.Structure):
     _fields_ = [('reserved', C.c_int32 * 2)]
 
 
+class AvaeAffinityConfig(C.Structure):
+    _fields_ = [('metric', C.c_int32), ('max_iter', C.c_int32), ('convergence_iter', C.c_int32), ('use_preference', C.c_int32),
+                ('noise', C.c_int32), ('warm', C.c_int32), ('damping', C.c_float), ('preference', C.c_float), ('seed', C.c_uint64),
+                ('reserved', C.c_int32 * 2)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -114,6 +120,7 @@ SIGNATURES = {
     'avae_probe_fit_l1': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(AvaeProbeL1Config), _P, _P]),
     'avae_ward': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(AvaeWardConfig), _P, _P, _P]),
     'avae_ward_cut': (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P]),
+    'avae_affinity': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeAffinityConfig), _P, _P, _P, _P, _P]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),

@@ -18,6 +18,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) linear probes of latent rows (liblinear CV)  -> VAE.probe_fit(z, labels) / VAE.probe_cv(z, labels, folds, groups)
     (new) L1 probes: the useful dimensions (liblinear) -> VAE.probe_fit_l1(z, labels) / VAE.select_dims(z, labels)
     (new) Ward clustering of latent rows (ARS, V_MSR)  -> VAE.ward(z, groups) / VAE.ward_cut(res, k) / VAE.cluster_eval(z, gold, groups)
+    (new) affinity propagation of latent rows          -> VAE.affinity(z, metric, ...) / affinity(vae, z, ...)
 """
 import ctypes as C
 
@@ -632,6 +633,15 @@ class VAE:
         from . import cluster
         return cluster.cluster_eval(self, z, gold, groups)
 
+    def affinity(self, z, metric='euclidean', preference=None, damping=0.5, max_iter=200, convergence_iter=15, seed=0, noise=True,
+                 return_messages=False):
+        """affinity propagation of the rows of z (sklearn's AffinityPropagation; src/eval_clustering_explorative.py:83-103) in ONE
+        device call (include/argsim_vae.h, avae_affinity).  metric: 'euclidean' (minus the squared distance), 'cosine' (minus the
+        cosine distance) or 'precomputed' (z is the (N, N) similarity matrix); preference None: the median similarity
+        -> dict(labels 0 .. K - 1 in ascending exemplar row or all -1, exemplars, n_iter, converged) (argsim_amd/affinity.py)"""
+        from . import affinity
+        return affinity.affinity(self, z, metric, preference, damping, max_iter, convergence_iter, seed, noise, return_messages)
+
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
 
@@ -843,6 +853,12 @@ def ward(vae, z, groups=None):
 def ward_cut(vae, res, k):
     """functional form of VAE.ward_cut"""
     return vae.ward_cut(res, k)
+
+
+def affinity(vae, z, metric='euclidean', preference=None, damping=0.5, max_iter=200, convergence_iter=15, seed=0, noise=True,
+             return_messages=False):
+    """functional form of VAE.affinity"""
+    return vae.affinity(z, metric, preference, damping, max_iter, convergence_iter, seed, noise, return_messages)
 
 
 def cluster_eval(vae, z, gold, groups=None):

@@ -486,6 +486,65 @@ int  avae_ward(avae_handle h, const float* x /* (N, dim) device */, int32_t dim,
 int  avae_ward_cut(avae_handle h, const int32_t* pair /* device, as returned */, const int32_t* group_off /* HOST */, int32_t G,
                    const int32_t* k /* HOST (G) */, int32_t* label /* (N) */);
 
+/* ---- affinity propagation of latent rows ------------------------------------------------------ */
+/* The explorative clustering of the reference (src/eval_clustering_explorative.py:83-103: AffinityPropagation on Euclidean and on
+ * cosine similarities) as ONE call over one set of rows: similarities, preference, the message passing with its stopping rule and the
+ * labels, enqueued on the handle's stream with no synchronisation inside.  x (N, dim) is a row-major float32 device array,
+ * 1 <= N <= 2^14; for metric 0 and 1 dim is a multiple of 4 in [4, 1024], x 16-byte aligned, independent of the handle's dim_rep;
+ * for metric 2 x IS the (N, N) similarity matrix and dim == N, whatever N.
+ *   similarity S_ik is evaluated in double, accumulated in a fixed order and rounded ONCE to fp32.  Metric 0: -|x_i - x_k|^2, the
+ *              difference first and then its square.  Metric 1: -(1 - x_i.x_k / (|x_i||x_k|)); a zero row gives NaN.  Symmetric by
+ *              construction, S_ii = 0 before the preference.
+ *   preference use_preference 0: numpy's median of all N^2 entries of that fp32 matrix, the diagonal included -- the middle value,
+ *              or for even N^2 the fp32 sum of the two middle values, halved -- found by a radix select over order keys with integer
+ *              histograms.  use_preference 1: `preference`.  The diagonal is then set to it.
+ *   noise      noise 1: S_ik += (2^-23 S_ik + 100 FLT_MIN) normal01(seed, 5, i N + k) in fp32, the diagonal included: sklearn's
+ *              perturbation on the library's counter generator, stream 5.  A draw depends on (seed, i, k, N) alone.
+ *   s_out      optional: S exactly as the iterations use it.
+ *   iteration  sklearn's loop with lambda = damping, all arithmetic in fp32 but the column sums:
+ *                R_ik <- lambda R_ik + (1 - lambda) (S_ik - max_{k' != k} (A_ik' + S_ik'))
+ *                A_ik <- lambda A_ik + (1 - lambda) min(0, R_kk + sum_{i' not in {i, k}} max(0, R_i'k))      i != k
+ *                A_kk <- lambda A_kk + (1 - lambda) sum_{i' != k} max(0, R_i'k)
+ *              The first maximum of A + S takes the lowest column on ties.  The column sums are taken in double in a fixed order
+ *              (ascending rows within a block of rows, then ascending blocks) and rounded once; E_k = (A_kk + R_kk > 0) in fp32.
+ *   stop       run_k counts the latest consecutive iterations, the current one included, in which E_k kept its value.  After
+ *              iteration it (0-based) the call stops if it >= convergence_iter, min_k run_k >= convergence_iter and K = sum E_k > 0
+ *              (sklearn's rolling window); otherwise after max_iter iterations.  The stop is decided on the device: all max_iter
+ *              rounds of three launches are enqueued, and a launch that finds the stop decided returns at once.
+ *   labels     whenever K > 0, converged or not: (1) c_i = argmax over the exemplars k of S_ik, the lowest k on ties, an exemplar
+ *              takes itself; (2) every cluster's exemplar is replaced by its member j with the largest sum of S_ij over the
+ *              cluster's rows i, S_jj included -- the sum in double in ascending i, rounded once to fp32, compared by order key,
+ *              the lowest j on ties; (3) step 1 again with the new exemplars.  label[i] is the ROW of i's exemplar; every label is
+ *              -1 if K = 0.  stat = (iterations run, converged 0 / 1, K, 0).  N = 1: label 0, stat (0, 1, 1, 0), nothing else runs.
+ *   a, r       optional, both or neither: the (N, N) messages.  The call works in them and leaves the final messages there; with
+ *              warm 1 it starts from their contents, else from zero.
+ *   not finite inputs are NOT checked.  A value that is not finite gives an unspecified but complete result: every label is -1 or the
+ *              row of an exemplar (-1 also where no exemplar's similarity to the row is a number above -inf); never a hang.
+ *   bits       no float atomics, fixed-order reductions: the same arguments give the same bits.  No kernel waits on another
+ *              workgroup; every loop is bounded by N, dim or max_iter.
+ *   workspace  4 N^2 bytes for each of S, A and R that the caller does not give (s_out, a, r), 8 N ceil(N / rb) bytes of column
+ *              partials (rb = 4 rows up to N = 4096, then ceil(N / 1024)), 32 N bytes of vectors and the state, reserved once per call.
+ * Errors (text through avae_last_error): a null ac, x, label or stat; N outside [1, 2^14]; a metric outside 0 .. 2; metric 2 with
+ * dim != N; for the other metrics dim not a multiple of 4 in [4, 1024] or x not 16-byte aligned; max_iter outside [1, 10000];
+ * convergence_iter outside [1, max_iter]; damping outside [0.5, 1); only one of a and r; warm without a and r; reserved != 0; a
+ * workspace the device cannot give (the text names its size).                                                                      */
+typedef struct avae_affinity_config {
+    int32_t metric;            /* 0: -|xi - xk|^2   1: -(1 - cos(xi, xk))   2: x IS the (N, N) similarity, dim == N */
+    int32_t max_iter;          /* [1, 10000]; sklearn's default 200 */
+    int32_t convergence_iter;  /* [1, max_iter]; 15 */
+    int32_t use_preference;    /* 0: the median of the similarities; 1: `preference` */
+    int32_t noise;             /* 1: the degeneracy-breaking perturbation from `seed`; 0: none */
+    int32_t warm;              /* 1: start from the contents of a / r; 0: from zero */
+    float   damping;           /* [0.5, 1) */
+    float   preference;
+    uint64_t seed;
+    int32_t reserved[2];
+} avae_affinity_config;
+int  avae_affinity(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim,
+                   const avae_affinity_config* ac,
+                   int32_t* label /* (N) */, int32_t* stat /* (4) */,
+                   float* s_out /* (N, N), optional */, float* a /* (N, N) */, float* r /* (N, N), both or neither */);
+
 #ifdef __cplusplus
 }
 #endif
