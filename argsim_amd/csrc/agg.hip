@@ -16,6 +16,7 @@
 // No float atomics; every sum has a fixed order: the same arguments and options give the same bits.
 #include "kernels.h"
 #include "mfma_tile.h"
+#include "row_parts.h"
 
 #include <algorithm>
 #include <cmath>
@@ -86,8 +87,8 @@ __global__ __launch_bounds__(256, 2) void agg_tile_kernel(AggTileArgs g)
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int part = blockIdx.x % g.parts, qt = blockIdx.x / g.parts;
     const int m0 = qt * kTQ;
-    const long long c_begin = (long long)part * g.chunk;
-    const int c_end = c_begin + g.chunk < (long long)g.N ? (int)(c_begin + g.chunk) : g.N;
+    long long c_begin; int c_end;
+    part_range(part, g.chunk, g.N, c_begin, c_end);
     const int dim = g.dim;
 
     float run_m[kQPT], run_s[kQPT];
@@ -262,9 +263,9 @@ __global__ __launch_bounds__(256) void moments_final_kernel(const double* __rest
     }
 }
 
-int moments_blocks(int N) { return std::max(1, std::min(256, (N + 255) / 256)); }
-
 }  // namespace
+
+int moments_blocks(int N) { return std::max(1, std::min(256, (N + 255) / 256)); }
 
 // The launch shape, from the problem shape alone: query tiles of 128 rows, and enough bank parts for 4 workgroups per CU on
 // 256 CUs (36 KB of LDS each), at least one 64-row bank tile per part and at most kAggMaxParts parts.  The target is a first
@@ -276,29 +277,20 @@ AggPlan agg_plan(int n, int N, int dim, int chunk_opt)
     AggPlan p{};
     p.qtiles = (n + kTQ - 1) / kTQ;
     if (N < 1) return p;
-    long long chunk;
-    if (chunk_opt > 0) chunk = chunk_opt;
-    else {
-        const int want = std::max(1, std::min(kAggMaxParts, (1024 + p.qtiles - 1) / std::max(p.qtiles, 1)));
-        const long long tiles = ((long long)N + kTB - 1) / kTB;
-        chunk = ((tiles + want - 1) / want) * kTB;
-    }
-    if (((long long)N + chunk - 1) / chunk > kAggMaxParts) chunk = ((((long long)N + kAggMaxParts - 1) / kAggMaxParts + kTB - 1) / kTB) * kTB;
-    p.chunk = (int)std::min<long long>(chunk, 0x7fffff80);
-    p.parts = (int)(((long long)N + p.chunk - 1) / p.chunk);
+    const RowParts r = row_parts(N, kTB, std::min(kAggMaxParts, (1024 + p.qtiles - 1) / std::max(p.qtiles, 1)), kAggMaxParts, chunk_opt);
+    p.parts = r.parts; p.chunk = r.chunk;
     return p;
 }
 
-size_t agg_ws_bytes(const AggPlan& p, int n) { return (size_t)std::max(p.parts, 1) * (size_t)n * sizeof(float2); }
-
-hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, void* ws)
+// parts_ms: (parts, n) float2, the parts' (max, sum) pairs
+hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, float2* parts_ms)
 {
     if (g.n < 1 || g.N < 1 || (g.dim & 3) || g.dim < 4 || g.dim > 1024 || g.self_base < -1 || g.self_base + (long long)g.n > (long long)g.N) return hipErrorInvalidValue;
     if (p.parts < 1 || p.parts > kAggMaxParts || (long long)p.qtiles * p.parts > 0x7fffffffLL || (long long)p.parts * p.chunk < (long long)g.N) return hipErrorInvalidValue;
     if (g.logqx && g.self_base < 0) return hipErrorInvalidValue;
     const float cst = (float)(0.5 * g.dim * std::log(2.0 * M_PI));
     AggTileArgs a{};
-    a.z = g.z; a.mu = g.mu; a.lv = g.lv; a.parts_ms = reinterpret_cast<float2*>(ws); a.logqx = g.logqx;
+    a.z = g.z; a.mu = g.mu; a.lv = g.lv; a.parts_ms = parts_ms; a.logqx = g.logqx;
     a.n = g.n; a.N = g.N; a.dim = g.dim; a.parts = p.parts; a.chunk = p.chunk; a.self_base = (int)g.self_base; a.cst = cst;
     hipLaunchKernelGGL(agg_tile_kernel, dim3((unsigned)(p.qtiles * p.parts)), dim3(256), 0, st, a);
     hipError_t e = hipGetLastError();
@@ -307,14 +299,11 @@ hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, void* ws
     return hipGetLastError();
 }
 
-size_t moments_ws_bytes(int N, int dim) { return ((size_t)moments_blocks(N) * 3 + 1) * (size_t)dim * sizeof(double); }
-
-hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, void* ws)
+// mean: dim doubles; part: moments_blocks(N) x 3 x dim doubles
+hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, double* mean, double* part)
 {
     if (N < 1 || (dim & 3) || dim < 4 || dim > 1024) return hipErrorInvalidValue;
     const int P = moments_blocks(N), rows = (N + P - 1) / P;
-    double* mean = reinterpret_cast<double*>(ws);
-    double* part = mean + dim;
     const dim3 grid((unsigned)P, (unsigned)((dim + 255) / 256)), fin((unsigned)((dim + 255) / 256));
     hipLaunchKernelGGL(moments_partial_kernel<0>, grid, dim3(256), 0, st, mu, lv, N, dim, rows, mean, part);
     hipLaunchKernelGGL(moments_final_kernel<0>, fin, dim3(256), 0, st, part, P, N, dim, mean, out);

@@ -53,18 +53,13 @@ int avae_ward(avae_handle h, const float* x, int32_t dim, const int32_t* group_o
     if (!x || !group_off || !pair || !delta) return fail(h, "ward: x, group_off, pair and delta must be given");
     int nmax = 0;
     AV_TRY(check_groups(h, "ward", group_off, G, &nmax));
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "ward: dim must be a multiple of 4 in [4, 1024]");
-    if ((uintptr_t)x & 15) return fail(h, "ward: x must be 16-byte aligned");
+    AV_TRY(check_rows(h, "ward", dim, "x", {x}));
     if (wc->reserved[0] != 0 || wc->reserved[1] != 0) return fail(h, "ward: the reserved fields must be 0");
     if (nmax < 2) return 0;                                     // every group a single row: no merge, nothing written
     AV_CHECK(hipSetDevice(h->device));
     std::vector<WardGroup> gs((size_t)G);
     WardGroup* dev = nullptr;
-    Bump probe{nullptr};
-    ward_layout(probe, gs, &dev, group_off, G, dim);
-    AV_TRY(reserve_named(h, probe.off + 4096, "ward"));         // sized once per call; nothing is allocated between the launches
-    Bump real{h->ws};
-    ward_layout(real, gs, &dev, group_off, G, dim);
+    AV_TRY(place_ws(h, "ward", [&](Bump& b) { ward_layout(b, gs, &dev, group_off, G, dim); }));
     AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardGroup), hipMemcpyHostToDevice, h->stream));
     AV_CHECK(ward_init(h->stream, dev, G, nmax, x, dim));
     const int form = h->ward_form ? h->ward_form : (nmax <= kWardOneWgMax ? 1 : 2);
@@ -92,12 +87,7 @@ int avae_ward_cut(avae_handle h, const int32_t* pair, const int32_t* group_off, 
     }
     AV_CHECK(hipSetDevice(h->device));
     WardCutGroup* dev = nullptr; int32_t* parent = nullptr;
-    auto lay = [&](Bump& b) { dev = b.take<WardCutGroup>((size_t)G); parent = b.take<int32_t>((size_t)group_off[G]); };
-    Bump probe{nullptr};
-    lay(probe);
-    AV_TRY(reserve_named(h, probe.off + 4096, "ward cut"));
-    Bump real{h->ws};
-    lay(real);
+    AV_TRY(place_ws(h, "ward cut", [&](Bump& b) { dev = b.take<WardCutGroup>((size_t)G); parent = b.take<int32_t>((size_t)group_off[G]); }));
     AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardCutGroup), hipMemcpyHostToDevice, h->stream));
     AV_CHECK(ward_cut(h->stream, dev, G, nmax, pair, parent, label));
     return 0;
@@ -113,10 +103,7 @@ int avae_affinity(avae_handle h, const float* x, int32_t N, int32_t dim, const a
     if (ac->metric < 0 || ac->metric > 2) return fail(h, "affinity: metric must be 0 (euclidean), 1 (cosine) or 2 (precomputed)");
     if (ac->metric == 2) {
         if (dim != N) return fail(h, "affinity: a precomputed similarity is (N, N): dim must equal N");
-    } else {
-        if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "affinity: dim must be a multiple of 4 in [4, 1024]");
-        if ((uintptr_t)x & 15) return fail(h, "affinity: x must be 16-byte aligned");
-    }
+    } else AV_TRY(check_rows(h, "affinity", dim, "x", {x}));
     if (ac->max_iter < 1 || ac->max_iter > 10000) return fail(h, "affinity: max_iter must be in [1, 10000]");
     if (ac->convergence_iter < 1 || ac->convergence_iter > ac->max_iter) return fail(h, "affinity: convergence_iter must be in [1, max_iter]");
     if (!(ac->damping >= 0.5f && ac->damping < 1.f)) return fail(h, "affinity: damping must be in [0.5, 1)");
@@ -129,7 +116,7 @@ int avae_affinity(avae_handle h, const float* x, int32_t N, int32_t dim, const a
     // the buffer itself, the column partials (row blocks x N doubles), five vectors of N and the state
     const size_t n = (size_t)N, nblk = (n + ap_row_block(N) - 1) / ap_row_block(N);
     ApBuffers b{};
-    auto lay = [&](Bump& bp) {
+    AV_TRY(place_ws(h, "affinity", [&](Bump& bp) {
         b.st = bp.take<ApState>(1);
         b.S = s_out ? s_out : bp.take<float>(n * n);
         b.A = a ? a : bp.take<float>(n * n);
@@ -139,12 +126,7 @@ int avae_affinity(avae_handle h, const float* x, int32_t N, int32_t dim, const a
         b.best = bp.take<unsigned long long>(n);
         b.E = bp.take<int>(n); b.run = bp.take<int>(n); b.E2 = bp.take<int>(n);
         b.c = bp.take<int32_t>(n);
-    };
-    Bump probe{nullptr};
-    lay(probe);
-    AV_TRY(reserve_named(h, probe.off + 4096, "affinity"));     // sized once per call; nothing is allocated between the launches
-    Bump real{h->ws};
-    lay(real);
+    }));
     AV_CHECK(hipMemsetAsync(b.st, 0, sizeof(ApState), h->stream));
     AV_CHECK(hipMemsetAsync(b.E, 0, n * sizeof(int), h->stream));
     if (!ac->warm) {

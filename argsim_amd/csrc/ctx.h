@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -118,6 +119,16 @@ namespace avae { namespace host {
 #define AV_TRY(expr) do { int r_ = (expr); if (r_) return r_; } while (0)
 
 inline int fail(avae_ctx* h, const std::string& m) { h->err = m; return 1; }
+// the rule every latent-row entry has for its row operands: dim a multiple of 4 in [4, 1024], the pointers in `ptrs` (which `names`
+// names in the message) 16-byte aligned
+inline int check_rows(avae_ctx* h, const char* what, int dim, const char* names, std::initializer_list<const void*> ptrs)
+{
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, std::string(what) + ": dim must be a multiple of 4 in [4, 1024]");
+    uintptr_t bits = 0;
+    for (const void* p : ptrs) bits |= (uintptr_t)p;
+    if (bits & 15) return fail(h, std::string(what) + ": " + names + " must be 16-byte aligned");
+    return 0;
+}
 
 // persistent GRU launches: the residency check of the GRU launchers (gru_dev.h) answers hipErrorCooperativeLaunchTooLarge
 #define AV_GRU(expr)                                                                                                \
@@ -315,6 +326,17 @@ template <class F> int place_scratch(avae_ctx* h, const char* what, F lay)
     lay(probe);
     AV_TRY(grow_scratch(h, probe.off, what));
     Bump real{reinterpret_cast<char*>(h->scratch)};
+    lay(real);
+    return 0;
+}
+// The same for a call's buffers in the workspace h->ws, sized once per call: nothing is allocated between the launches.  A refusal
+// names the call and the byte count (reserve_named).  `from`: the buffers start behind that many bytes, which the caller lays out itself.
+template <class F> int place_ws(avae_ctx* h, const char* what, F lay, size_t from = 0)
+{
+    Bump probe{nullptr, from};
+    lay(probe);
+    AV_TRY(reserve_named(h, probe.off + 4096, what));
+    Bump real{h->ws, from};
     lay(real);
     return 0;
 }

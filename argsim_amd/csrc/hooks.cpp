@@ -394,5 +394,16 @@ int avae_debug_beam_select(avae_handle h, const float* logits, int n, int width,
     AV_CHECK(beam_select(h->stream, a));
     return 0;
 }
+// test hook: the launch plan of a latent-row entry.  kind 0 knn_plan(n, N, k, chunk_opt), 1 agg_plan(n, N, dim, chunk_opt), 2 probe_plan(N, P, dim,
+// chunk_opt); out = every field: qrows or ptiles, qtiles or Ppad, LD or 0, parts, chunk (agg: 0, qtiles, 0, parts, chunk).  Host arithmetic only:
+// callable without a GPU.
+int avae_debug_latent_plan(int kind, int64_t n, int64_t N, int k_or_P, int dim, int chunk_opt, int32_t out[5])
+{
+    if (!out || kind < 0 || kind > 2 || n < 0 || n > 0x7fffffff || N < 0 || N > 0x7fffffff) return 1;
+    if (kind == 0) { const KnnPlan p = knn_plan((int)n, (int)N, k_or_P, chunk_opt); const int32_t f[5] = {p.qrows, p.qtiles, 0, p.parts, p.chunk}; std::copy(f, f + 5, out); }
+    else if (kind == 1) { const AggPlan p = agg_plan((int)n, (int)N, dim, chunk_opt); const int32_t f[5] = {0, p.qtiles, 0, p.parts, p.chunk}; std::copy(f, f + 5, out); }
+    else { const ProbePlan p = probe_plan((int)N, k_or_P, dim, chunk_opt); const int32_t f[5] = {p.ptiles, p.Ppad, p.LD, p.parts, p.chunk}; std::copy(f, f + 5, out); }
+    return 0;
+}
 
 }  // extern "C"

@@ -350,11 +350,12 @@ struct KnnArgs {
     int64_t* out_idx; float* out_score;
 };
 // the launch shape (knn.hip, knn_plan: a pure host function of the problem shape): query tiles of qrows rows, the bank cut into
-// `parts` runs of `chunk` rows, one workgroup per (query tile, part); chunk_opt > 0 caps chunk (option knn_chunk)
+// `parts` runs of `chunk` rows (row_parts.h), one workgroup per (query tile, part); chunk_opt > 0 caps chunk (option knn_chunk)
 struct KnnPlan { int qrows, qtiles, parts, chunk; };
 KnnPlan knn_plan(int n, int N, int k, int chunk_opt);
-size_t knn_ws_bytes(const KnnPlan& p, int n, int N, int k);      // workspace: the rows' norms + the parts' lists (n x parts x k x 8 bytes)
-hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, void* ws);
+// workspace laid out by the caller (scoring.cpp): the rows' norms qn (n) and bn (N), the parts' lists (n, parts, k)
+struct KnnWs { float *qn, *bn; unsigned long long* lists; };
+hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, const KnnWs& w);
 
 // ---------------------------------------------------------------- aggregate-posterior diagnostics (agg.hip)
 // log q(z_i) under the aggregate posterior of N encoded rows (contract: include/argsim_vae.h, avae_agg_logq): z (n, dim), mu and
@@ -367,15 +368,15 @@ struct AggArgs {
     float* logq; float* logqx;
 };
 // the launch shape (agg.hip, agg_plan: a pure host function of the problem shape): query tiles of 128 rows, the bank cut into
-// `parts` runs of `chunk` rows, one workgroup per (query tile, part); chunk_opt > 0 caps chunk (option agg_chunk)
+// `parts` runs of `chunk` rows (row_parts.h), one workgroup per (query tile, part); chunk_opt > 0 caps chunk (option agg_chunk)
 struct AggPlan { int qtiles, parts, chunk; };
 AggPlan agg_plan(int n, int N, int dim, int chunk_opt);
-size_t agg_ws_bytes(const AggPlan& p, int n);                    // workspace: the parts' (max, sum) pairs (parts x n x 8 bytes)
-hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, void* ws);
+// parts_ms: workspace laid out by the caller (scoring.cpp), the parts' (max, sum) pairs (parts, n)
+hipError_t agg_logq(hipStream_t st, const AggArgs& g, const AggPlan& p, float2* parts_ms);
 // out (4, dim) = per dimension over the N rows: mean mu, unbiased variance of mu (0 for N = 1), mean exp(lv), mean KL term; sums in
-// double, fixed order
-size_t moments_ws_bytes(int N, int dim);
-hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, void* ws);
+// double, fixed order.  Workspace laid out by the caller: mean (dim) and part (moments_blocks(N), 3, dim) doubles
+int moments_blocks(int N);
+hipError_t latent_moments(hipStream_t st, const float* mu, const float* lv, int N, int dim, float* out, double* mean, double* part);
 
 // ---------------------------------------------------------------- linear probes of latent rows (probe.hip)
 // P independent L2 (avae_probe_fit) or L1 (avae_probe_fit_l1) logistic regressions over x (N, dim) in lockstep (contract:

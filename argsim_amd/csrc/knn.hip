@@ -19,6 +19,7 @@
 // float atomics; the only atomics are integer LDS ones: the same arguments give the same bits.
 #include "kernels.h"
 #include "mfma_tile.h"
+#include "row_parts.h"
 #include "sample_dev.h"
 
 #include <algorithm>
@@ -115,8 +116,8 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnTileArgs a)
     const int wm = wave / WN, wn = wave % WN;
     const int part = blockIdx.x % a.parts, qt = blockIdx.x / a.parts;
     const int m0 = qt * BM;
-    const long long c_begin = (long long)part * a.chunk;
-    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    long long c_begin; int c_end;
+    part_range(part, a.chunk, a.N, c_begin, c_end);
     const int k = a.k, dim = a.dim;
     // query row i never takes column self_off + i; column - row is an int above INT_MIN, which so stands for "no exclusion"
     const int self_d = (a.has_self && a.self_off > -0x7fffffffLL && a.self_off <= 0x7fffffffLL) ? (int)a.self_off : (int)0x80000000;
@@ -282,42 +283,24 @@ KnnPlan knn_plan(int n, int N, int k, int chunk_opt)
     p.qrows = n <= 64 ? 32 : 128;
     p.qtiles = (n + p.qrows - 1) / p.qrows;
     if (N < 1) return p;
-    const int max_parts = knn_max_parts(k);
-    long long chunk;
-    if (chunk_opt > 0) chunk = chunk_opt;
-    else {
-        const int target = 256 * (p.qrows == 32 ? 4 : 1);
-        const int want = std::max(1, std::min(max_parts, (target + p.qtiles - 1) / p.qtiles));
-        const long long tiles = ((long long)N + kBN - 1) / kBN;
-        chunk = ((tiles + want - 1) / want) * kBN;
-    }
-    if (((long long)N + chunk - 1) / chunk > max_parts) chunk = ((((long long)N + max_parts - 1) / max_parts + kBN - 1) / kBN) * kBN;
-    p.chunk = (int)std::min<long long>(chunk, 0x7fffff80);
-    p.parts = (int)(((long long)N + p.chunk - 1) / p.chunk);
+    const int max_parts = knn_max_parts(k), target = 256 * (p.qrows == 32 ? 4 : 1);
+    const RowParts r = row_parts(N, kBN, std::min(max_parts, (target + p.qtiles - 1) / p.qtiles), max_parts, chunk_opt);
+    p.parts = r.parts; p.chunk = r.chunk;
     return p;
 }
 
-size_t knn_ws_bytes(const KnnPlan& p, int n, int N, int k)
-{
-    const size_t norms = (((size_t)n + (size_t)N) * sizeof(float) + 15) & ~(size_t)15;
-    return norms + (size_t)n * p.parts * k * sizeof(u64);
-}
-
-hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, void* ws)
+hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, const KnnWs& w)
 {
     if (g.n < 1 || g.N < 0 || g.k < 1 || g.k > kKnnMaxK || g.metric < 0 || g.metric > 2 || (g.dim & 3) || g.dim < 4 || g.dim > 1024)
         return hipErrorInvalidValue;
     if (p.parts > knn_max_parts(g.k) || (long long)p.qtiles * std::max(p.parts, 1) > 0x7fffffffLL) return hipErrorInvalidValue;
-    float* qn = reinterpret_cast<float*>(ws);
-    float* bn = qn + g.n;
-    u64* lists = reinterpret_cast<u64*>(reinterpret_cast<char*>(ws) + ((((size_t)g.n + (size_t)g.N) * sizeof(float) + 15) & ~(size_t)15));
     if (g.N > 0) {
         if (g.metric != 0) {
             const long long rows = (long long)g.n + g.N;
-            hipLaunchKernelGGL(knn_norms_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, g.q, g.n, g.bank, g.N, g.dim, g.metric, qn, bn);
+            hipLaunchKernelGGL(knn_norms_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, g.q, g.n, g.bank, g.N, g.dim, g.metric, w.qn, w.bn);
         }
         KnnTileArgs a{};
-        a.q = g.q; a.bank = g.bank; a.qn = qn; a.bn = bn; a.lists = lists;
+        a.q = g.q; a.bank = g.bank; a.qn = w.qn; a.bn = w.bn; a.lists = w.lists;
         a.n = g.n; a.N = g.N; a.dim = g.dim; a.k = g.k; a.metric = g.metric; a.parts = p.parts; a.chunk = p.chunk;
         a.has_self = g.self_base >= 0 ? 1 : 0; a.self_off = g.self_base - g.idx_base;
         const dim3 grid((unsigned)(p.qtiles * p.parts));
@@ -333,7 +316,7 @@ hipError_t knn_search(hipStream_t st, const KnnArgs& g, const KnnPlan& p, void* 
         if (e != hipSuccess) return e;
     }
     const int L = p.parts + (g.carry ? 1 : 0);
-    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)g.n), dim3(256), (size_t)std::max(L, 1) * g.k * 12, st, lists, p.parts, g.k, (long long)g.idx_base,
+    hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)g.n), dim3(256), (size_t)std::max(L, 1) * g.k * 12, st, w.lists, p.parts, g.k, (long long)g.idx_base,
                        g.carry, reinterpret_cast<long long*>(g.out_idx), g.out_score);
     return hipGetLastError();
 }

@@ -131,12 +131,7 @@ int reserve_ws(avae_ctx* h, size_t need)
 
 int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train)
 {
-    Bump probe{nullptr};
-    layout(h, probe, w, B, Ss, St, train);
-    AV_TRY(reserve_ws(h, probe.off + 4096));
-    Bump real{h->ws};
-    layout(h, real, w, B, Ss, St, train);
-    return 0;
+    return place_ws(h, "step", [&](Bump& b) { layout(h, b, w, B, Ss, St, train); });
 }
 
 static int grow_bf16(avae_ctx* h, unsigned short** buf, size_t* cap, size_t need)

@@ -25,6 +25,7 @@
 // per-problem kernel probe_l1_vec, the curvature column sums probe_l1_curv and the row check probe_l1_rows, at the end of this file's kernels.
 #include "kernels.h"
 #include "mfma_tile.h"
+#include "row_parts.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -74,8 +75,8 @@ __global__ __launch_bounds__(256) void probe_pass_kernel(ProbePassArgs a)
         const int busy = tid < kTP ? a.flags[(size_t)(p0 + tid) * 8 + a.flag] : 0;
         if (!__syncthreads_or(busy)) return;
     }
-    const long long c_begin = (long long)part * a.chunk;
-    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    long long c_begin; int c_end;
+    part_range(part, a.chunk, a.N, c_begin, c_end);
     const float vb = a.v[(size_t)prob * a.LD + dim];
 
     f32x16 g[MODE == 2 ? 1 : DT];
@@ -261,32 +262,123 @@ __global__ void probe_finish_kernel(ProbeWs b, float* __restrict__ w, float* __r
     }
 }
 
-// the sum of one double per thread over the 256 threads, as a fixed binary tree; every thread gets it
-__device__ __forceinline__ double block_sum(double v, double* s)
+// ---------------------------------------------------------------- what the two per-problem kernels (probe_vec, probe_l1_vec) share
+// NV values per thread reduced over the 256 threads by one fixed binary tree behind one set of barriers; every thread gets the results
+struct OpAdd { __device__ double operator()(double a, double b) const { return a + b; } };
+struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
+template <int NV, class Op>
+__device__ __forceinline__ void block_reduce(double (&v)[NV], double (*s)[256])
 {
     const int tid = threadIdx.x;
-    s[tid] = v;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s[i][tid] = v[i];
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) s[tid] += s[tid + o];
+        if (tid < o) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) s[i][tid] = Op()(s[i][tid], s[i][tid + o]);
+        }
         __syncthreads();
     }
-    const double r = s[0];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) v[i] = s[i][0];
     __syncthreads();
-    return r;
+}
+__device__ __forceinline__ double block_sum(double v, double (*s)[256])
+{
+    double a[1] = {v};
+    block_reduce<1, OpAdd>(a, s);
+    return a[0];
+}
+// the largest of one float per thread (values >= 0; fmax on doubles: a NaN is dropped)
+__device__ __forceinline__ float block_max(float v, double (*s)[256])
+{
+    double a[1] = {v};
+    block_reduce<1, OpMax>(a, s);
+    return (float)a[0];
 }
 
 __device__ __forceinline__ bool finite_d(double v) { return v - v == 0.0; }
 
 constexpr int kVecPer = 5;      // (1024 + 1 + 255) / 256 elements of a vector per thread
 
-// partial of the last pass for element d of problem p, the parts added in part order
+// partial of the last pass for element d of problem p, the parts added in part order; 16 parts' loads are in flight at once (the
+// strided loads of one element are independent, only the additions form a chain)
 __device__ __forceinline__ float merge_parts(const ProbeWs& b, int p, int d)
 {
+    const float* src = b.gp + (size_t)d * b.Ppad + p;
+    const size_t step = (size_t)b.LD * b.Ppad;
     float s = 0.f;
-#pragma unroll 8
-    for (int q = 0; q < b.parts; ++q) s += b.gp[((size_t)q * b.LD + d) * b.Ppad + p];
+    int q = 0;
+    for (; q + 16 <= b.parts; q += 16) {
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = src[(size_t)(q + i) * step];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s += v[i];
+    }
+    if (q < b.parts) {
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = q + i < b.parts ? src[(size_t)(q + i) * step] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (q + i < b.parts) s += v[i];
+    }
     return s;
+}
+
+// the state words and the vectors of problem p that both methods keep
+struct ProbeState { int* is; float* fs; double* ds; float *W, *G, *Dv, *Pv; };
+__device__ __forceinline__ ProbeState probe_state(const ProbeWs& b, int p)
+{
+    const size_t v = (size_t)p * b.LD;
+    return ProbeState{b.is + (size_t)p * 8, b.fs + (size_t)p * 8, b.ds + (size_t)p * 8, b.W + v, b.G + v, b.Dv + v, b.Pv + v};
+}
+
+// the problem takes no further part in the fit (the caller clears I_CG / I_LS where one is set)
+__device__ __forceinline__ void end_problem(int* is, int status) { is[I_STATUS] = status; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+
+// after a GRAD pass: -1 go on, else the status the problem ends with -- 2 f or the optimality measure is not finite, 0 the measure
+// is within tol of its first value, 1 max_newton iterations are done
+__device__ __forceinline__ int newton_stop(float f, float norm, float norm0, float tol, int it, int max_newton)
+{
+    if (!(f - f == 0.f) || !(norm - norm == 0.f)) return 2;
+    if (norm <= tol * norm0) return 0;
+    if (it >= max_newton) return 1;
+    return -1;
+}
+
+// The Armijo scan of trial round k by one thread: slot j's loss sum is the parts' added in part order; slot 0 of round 0 is the step
+// length 0 (kept in D_PHI0).  The first step length a with (loss - loss at 0) + reg(j, a, bad) <= rhs(a) is taken; reg is the change
+// of the regulariser (it may set bad), rhs the decrease asked for.  take < 0: none of this round; bad: a sum is not finite.
+struct ArmijoPick { float take; bool bad; };
+template <class Reg, class Rhs>
+__device__ __forceinline__ ArmijoPick armijo_scan(const ProbeWs& b, int p, int k, const ProbeAlphas& al, double* ds, Reg reg, Rhs rhs)
+{
+    float take = -1.f; bool bad = false;
+#pragma unroll
+    for (int j = 0; j < kNA; ++j) {
+        if (j >= al.n || take >= 0.f || bad) break;
+        double L = 0.0;
+        for (int q = 0; q < b.parts; ++q) L += b.tp[((size_t)q * kNA + j) * b.Ppad + p];
+        if (k == 0 && j == 0) { ds[D_PHI0] = L; if (!finite_d(L)) bad = true; continue; }
+        const double a = al.a[j];
+        bool rbad = false;
+        const double r = reg(j, a, rbad);
+        if (!finite_d(L) || rbad) { bad = true; break; }
+        const double lhs = (L - ds[D_PHI0]) + r;
+        if (lhs <= rhs(a)) take = al.a[j];
+    }
+    return ArmijoPick{take, bad};
+}
+
+// what both kernels do with the pick: the problem ends (status 2), moves on to its next Newton iteration, or waits for the next round
+__device__ __forceinline__ float armijo_settle(int* is, const ArmijoPick& pk, int last)
+{
+    if (pk.bad || (pk.take < 0.f && last)) { end_problem(is, 2); is[I_LS] = 0; }
+    else if (pk.take >= 0.f) { is[I_LS] = 0; is[I_ITER] += 1; }
+    return pk.bad ? -1.f : pk.take;
 }
 
 // PHASE 0: after a GRAD pass -- f, g, the stop rule, else the start of CG.  PHASE 1: after the k-th HV pass -- one CG iteration.
@@ -294,17 +386,11 @@ __device__ __forceinline__ float merge_parts(const ProbeWs& b, int p, int d)
 template <int PHASE>
 __global__ __launch_bounds__(256) void probe_vec_kernel(ProbeWs b, int k, int max_newton, int max_cg, float tol, ProbeAlphas al)
 {
-    __shared__ double s_sum[256];
+    __shared__ double s_sum[1][256];
     __shared__ float s_alpha;
     const int p = blockIdx.x, tid = threadIdx.x, n = b.dim + 1;
-    int* is = b.is + (size_t)p * 8;
-    float* fs = b.fs + (size_t)p * 8;
-    double* ds = b.ds + (size_t)p * 8;
-    float* W = b.W + (size_t)p * b.LD;
-    float* G = b.G + (size_t)p * b.LD;
-    float* Dv = b.Dv + (size_t)p * b.LD;
+    const auto [is, fs, ds, W, G, Dv, Pv] = probe_state(b, p);
     float* Rv = b.Rv + (size_t)p * b.LD;
-    float* Pv = b.Pv + (size_t)p * b.LD;
 
     if (PHASE == 0) {
         if (is[I_FROZEN]) return;
@@ -320,15 +406,12 @@ __global__ __launch_bounds__(256) void probe_vec_kernel(ProbeWs b, int k, int ma
         const int it = is[I_ITER];
         const float f = (float)(0.5 * ww) + loss, gnorm = (float)sqrt(gg);
         const float g0 = it == 0 ? gnorm : fs[F_G0];
-        int status = -1;
-        if (!(f - f == 0.f) || !(gnorm - gnorm == 0.f)) status = 2;
-        else if (gnorm <= tol * g0) status = 0;
-        else if (it >= max_newton) status = 1;
+        const int status = newton_stop(f, gnorm, g0, tol, it, max_newton);
         if (status < 0)
             for (int d = tid; d < n; d += 256) { const float gv = G[d]; Pv[d] = 0.f; Rv[d] = -gv; Dv[d] = -gv; }
         if (tid == 0) {
             fs[F_F] = f; fs[F_GNORM] = gnorm; fs[F_G0] = g0;
-            if (status >= 0) { is[I_STATUS] = status; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            if (status >= 0) end_problem(is, status);
             else { ds[D_RR] = gg; is[I_CG] = 1; }
         }
     } else if (PHASE == 1) {
@@ -374,26 +457,15 @@ __global__ __launch_bounds__(256) void probe_vec_kernel(ProbeWs b, int k, int ma
         gtp = block_sum(gtp, s_sum); wtp = block_sum(wtp, s_sum); pp = block_sum(pp, s_sum);
         if (tid == 0) {
             is[I_CG] = 0;
-            if (!finite_d(dhd) || !finite_d(rrn) || !finite_d(gtp) || !finite_d(pp)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            if (!finite_d(dhd) || !finite_d(rrn) || !finite_d(gtp) || !finite_d(pp)) end_problem(is, 2);
             else { ds[D_GTP] = gtp; ds[D_WTP] = wtp; ds[D_PP] = pp; is[I_LS] = 1; }
         }
     } else {
         if (!is[I_LS]) return;
         if (tid == 0) {
-            // trial slot j of round k: its loss sum, the parts added in part order; slot 0 of round 0 is the step length 0
-            float take = -1.f; bool bad = false;
-            for (int j = 0; j < al.n && take < 0.f && !bad; ++j) {
-                double L = 0.0;
-                for (int q = 0; q < b.parts; ++q) L += b.tp[((size_t)q * kNA + j) * b.Ppad + p];
-                if (k == 0 && j == 0) { ds[D_PHI0] = L; if (!finite_d(L)) bad = true; continue; }
-                if (!finite_d(L)) { bad = true; break; }
-                const double a = al.a[j];
-                const double lhs = (L - ds[D_PHI0]) + (a * ds[D_WTP] + 0.5 * a * a * ds[D_PP]);
-                if (lhs <= 1e-4 * a * ds[D_GTP]) take = al.a[j];
-            }
-            if (bad || (take < 0.f && al.last)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; is[I_LS] = 0; }
-            else if (take >= 0.f) { is[I_LS] = 0; is[I_ITER] += 1; }
-            s_alpha = bad ? -1.f : take;
+            const ArmijoPick pk = armijo_scan(b, p, k, al, ds, [ds = ds](int, double a, bool&) { return a * ds[D_WTP] + 0.5 * a * a * ds[D_PP]; },
+                                              [ds = ds](double a) { return 1e-4 * a * ds[D_GTP]; });
+            s_alpha = armijo_settle(is, pk, al.last);
         }
         __syncthreads();
         const float a = s_alpha;
@@ -419,8 +491,8 @@ __global__ __launch_bounds__(256) void probe_trial_kernel(ProbeTrialArgs a)
     const int part = blockIdx.x % a.parts, p0 = (blockIdx.x / a.parts) * kTP, prob = p0 + pl;
     const int active = a.flags[(size_t)prob * 8 + I_LS];
     if (!__syncthreads_or(active)) return;
-    const long long c_begin = (long long)part * a.chunk;
-    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    long long c_begin; int c_end;
+    part_range(part, a.chunk, a.N, c_begin, c_end);
     double acc[kNA];
 #pragma unroll
     for (int j = 0; j < kNA; ++j) acc[j] = 0.0;
@@ -469,61 +541,6 @@ __device__ __forceinline__ float subgrad_abs(float g, float w)
     return e <= 0.f ? 0.f : e;
 }
 
-// the largest of one float per thread over the 256 threads (values >= 0, fmaxf: a NaN is dropped); every thread gets it
-__device__ __forceinline__ float block_max(float v, double* s)
-{
-    const int tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) s[tid] = fmax(s[tid], s[tid + o]);
-        __syncthreads();
-    }
-    const float r = (float)s[0];
-    __syncthreads();
-    return r;
-}
-
-// block_sum of three values behind one set of barriers (the same tree for each)
-__device__ __forceinline__ void block_sum3(double& a, double& b, double& c, double (*s)[256])
-{
-    const int tid = threadIdx.x;
-    s[0][tid] = a; s[1][tid] = b; s[2][tid] = c;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { s[0][tid] += s[0][tid + o]; s[1][tid] += s[1][tid + o]; s[2][tid] += s[2][tid + o]; }
-        __syncthreads();
-    }
-    a = s[0][0]; b = s[1][0]; c = s[2][0];
-    __syncthreads();
-}
-
-// merge_parts with 16 parts' loads in flight at once: the same additions in the same order, so the same bits (the strided loads of
-// one element are independent, only the additions form a chain; the L2 fit's kernel keeps its own merge)
-__device__ __forceinline__ float merge_parts_deep(const ProbeWs& b, int p, int d)
-{
-    const float* src = b.gp + (size_t)d * b.Ppad + p;
-    const size_t step = (size_t)b.LD * b.Ppad;
-    float s = 0.f;
-    int q = 0;
-    for (; q + 16 <= b.parts; q += 16) {
-        float v[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = src[(size_t)(q + i) * step];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) s += v[i];
-    }
-    if (q < b.parts) {
-        float v[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = q + i < b.parts ? src[(size_t)(q + i) * step] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (q + i < b.parts) s += v[i];
-    }
-    return s;
-}
-
 // xs (N, dim) <- x with every row that holds a value that is not finite replaced by zeros, and every problem with a nonzero cost on
 // such a row ended with status 2 before the first pass: x~^T (tile) would carry the row's NaN into every problem of the call, 0 cost
 // or not.  One wave per row.
@@ -554,7 +571,7 @@ __global__ __launch_bounds__(256) void probe_l1_rows_kernel(const float* __restr
     if (any)
         for (int p = lane; p < Ppad; p += 64)
             if (sT[(size_t)row * Ppad + p] != 0.f) {          // (every writer stores the same words)
-                is[(size_t)p * 8 + I_STATUS] = 2; is[(size_t)p * 8 + I_FROZEN] = 1; is[(size_t)p * 8 + I_ALIVE] = 0;
+                end_problem(is + (size_t)p * 8, 2);
             }
 }
 
@@ -574,8 +591,8 @@ __global__ __launch_bounds__(256) void probe_l1_curv_kernel(ProbeCurvArgs a)
     const int part = blockIdx.x % a.parts, p0 = (blockIdx.x / a.parts) * kTP, prob = p0 + pl;
     const int busy = tid < kTP ? a.flags[(size_t)(p0 + tid) * 8 + I_CG] : 0;
     if (!__syncthreads_or(busy)) return;
-    const long long c_begin = (long long)part * a.chunk;
-    const int c_end = c_begin + a.chunk < (long long)a.N ? (int)(c_begin + a.chunk) : a.N;
+    long long c_begin; int c_end;
+    part_range(part, a.chunk, a.N, c_begin, c_end);
     const int j = blockIdx.y * 32 + jg * 4;
     const bool jok = j < a.dim, bias = blockIdx.y == 0 && jg == 0;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, accb = 0.f;
@@ -601,17 +618,10 @@ __global__ __launch_bounds__(256) void probe_l1_curv_kernel(ProbeCurvArgs a)
 template <int PHASE>
 __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int max_newton, int max_inner, float tol, ProbeAlphas al)
 {
-    __shared__ double s_sum3[3][256];
-    double* s_sum = s_sum3[0];
+    __shared__ double s_sum[3][256];
     __shared__ float s_alpha;
     const int p = blockIdx.x, tid = threadIdx.x, n = b.dim + 1;
-    int* is = b.is + (size_t)p * 8;
-    float* fs = b.fs + (size_t)p * 8;
-    double* ds = b.ds + (size_t)p * 8;
-    float* W = b.W + (size_t)p * b.LD;
-    float* G = b.G + (size_t)p * b.LD;
-    float* Dv = b.Dv + (size_t)p * b.LD;
-    float* Pv = b.Pv + (size_t)p * b.LD;
+    const auto [is, fs, ds, W, G, Dv, Pv] = probe_state(b, p);
     float* Yv = b.Yv + (size_t)p * b.LD;
     float* Hd = b.Hd + (size_t)p * b.LD;
     float* Hy = b.Hy + (size_t)p * b.LD;
@@ -622,7 +632,7 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
         const float v0_kept = fs[F_G0];
         double w1 = 0.0, vn = 0.0;
         for (int d = tid; d < n; d += 256) {
-            const float w = W[d], gv = merge_parts_deep(b, p, d);
+            const float w = W[d], gv = merge_parts(b, p, d);
             G[d] = gv;
             w1 += (double)fabsf(w); vn += (double)subgrad_abs(gv, w);
         }
@@ -631,27 +641,24 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
         for (int q = 0; q < b.parts; ++q) loss += b.lp[(size_t)q * b.Ppad + p];
         const float f = (float)w1 + loss, vnorm = (float)vn;
         const float v0 = it == 0 ? vnorm : v0_kept;
-        int status = -1;
-        if (!(f - f == 0.f) || !(vnorm - vnorm == 0.f)) status = 2;
-        else if (vnorm <= tol * v0) status = 0;
-        else if (it >= max_newton) status = 1;
+        const int status = newton_stop(f, vnorm, v0, tol, it, max_newton);
         if (tid == 0) {
             fs[F_F] = f; fs[F_GNORM] = vnorm; fs[F_G0] = v0;
-            if (status >= 0) { is[I_STATUS] = status; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            if (status >= 0) end_problem(is, status);
             else { ds[D_W1] = w1; is[I_CG] = 1; }
         }
     } else if (PHASE == 3) {
         if (!is[I_CG]) return;
         const float rho = fs[F_RHO];
         float mx = 0.f;
-        for (int d = tid; d < n; d += 256) mx = fmaxf(mx, merge_parts_deep(b, p, d));
+        for (int d = tid; d < n; d += 256) mx = fmaxf(mx, merge_parts(b, p, d));
         mx = block_max(mx, s_sum);
         // L starts at the largest diagonal entry of H (a lower bound of its largest eigenvalue; the backtracking doubles it), from the
         // second inner solve on at half of what the last one ended with, relative to that entry
         float L = mx;
         if (rho > 2.f && rho - rho == 0.f) L = mx * (0.5f * rho);
         if (!(L > 0.f) || !(L - L == 0.f)) {
-            if (tid == 0) { is[I_CG] = 0; is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            if (tid == 0) { is[I_CG] = 0; end_problem(is, 2); }
             return;
         }
         const float iL = 1.f / L;
@@ -669,7 +676,7 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
 #pragma unroll
         for (int j = 0; j < kVecPer; ++j) {          // (a loop of loads alone: nothing stored between them, every element's in flight)
             const int d = tid + 256 * j;
-            hp[j] = d < n ? merge_parts_deep(b, p, d) : 0.f;
+            hp[j] = d < n ? merge_parts(b, p, d) : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < kVecPer; ++j) {
@@ -679,7 +686,9 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
                 dHd += (double)del * (double)(hp[j] - Hy[d]); dd += (double)del * del; rs += (double)(yv - c) * (double)(c - Pv[d]);
             }
         }
-        block_sum3(dHd, dd, rs, s_sum3);
+        double sums[3] = {dHd, dd, rs};
+        block_reduce<3, OpAdd>(sums, s_sum);
+        dHd = sums[0]; dd = sums[1]; rs = sums[2];
         bool bad = !finite_d(dHd) || !finite_d(dd);
         // the backtracking test on the quadratic: q_s(d+) - q_s(y) - grad q_s(y).(d+ - y) = 1/2 (d+ - y).H (d+ - y) <= L/2 |d+ - y|^2
         const bool accept = !bad && dHd <= (double)L * dd;
@@ -724,7 +733,7 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
             }
         }
         if (bad) {
-            if (tid == 0) { is[I_CG] = 0; is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            if (tid == 0) { is[I_CG] = 0; end_problem(is, 2); }
             return;
         }
         if (!stop) {
@@ -738,7 +747,7 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
         if (tid == 0) {
             const double delta = gtd + (w1d - ds[D_W1]);
             is[I_CG] = 0;
-            if (!finite_d(delta)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; }
+            if (!finite_d(delta)) end_problem(is, 2);
             else { ds[D_DELTA] = delta; is[I_LS] = 1; fs[F_RHO] = Ln / fs[F_MX]; }
         }
     } else {
@@ -755,22 +764,9 @@ __global__ __launch_bounds__(256) void probe_l1_vec_kernel(ProbeWs b, int k, int
             }
         }
         if (tid == 0) {
-            // trial slot j of round k: its loss sum, the parts added in part order; slot 0 of round 0 is the step length 0
-            float take = -1.f; bool bad = false;
-#pragma unroll
-            for (int j = 0; j < kNA; ++j) {
-                if (j >= al.n || take >= 0.f || bad) break;
-                double Ls = 0.0;
-                for (int q = 0; q < b.parts; ++q) Ls += b.tp[((size_t)q * kNA + j) * b.Ppad + p];
-                if (k == 0 && j == 0) { ds[D_PHI0] = Ls; if (!finite_d(Ls)) bad = true; continue; }
-                if (!finite_d(Ls) || !finite_d(l1[j])) { bad = true; break; }
-                const double a = al.a[j];
-                const double lhs = (Ls - ds[D_PHI0]) + (l1[j] - ds[D_W1]);
-                if (lhs <= 0.01 * a * ds[D_DELTA]) take = al.a[j];
-            }
-            if (bad || (take < 0.f && al.last)) { is[I_STATUS] = 2; is[I_FROZEN] = 1; is[I_ALIVE] = 0; is[I_LS] = 0; }
-            else if (take >= 0.f) { is[I_LS] = 0; is[I_ITER] += 1; }
-            s_alpha = bad ? -1.f : take;
+            const ArmijoPick pk = armijo_scan(b, p, k, al, ds, [ds = ds, &l1](int j, double, bool& bad) { bad = !finite_d(l1[j]); return l1[j] - ds[D_W1]; },
+                                              [ds = ds](double a) { return 0.01 * a * ds[D_DELTA]; });
+            s_alpha = armijo_settle(is, pk, al.last);
         }
         __syncthreads();
         const float a = s_alpha;
@@ -798,16 +794,8 @@ ProbePlan probe_plan(int N, int P, int dim, int chunk_opt)
     p.ptiles = (P + kProbeTile - 1) / kProbeTile;
     p.Ppad = p.ptiles * kProbeTile;
     p.LD = dim + 4;
-    long long chunk;
-    if (chunk_opt > 0) chunk = chunk_opt;
-    else {
-        const long long tiles = ((long long)N + kTR - 1) / kTR;
-        const long long want = std::max<long long>(1, std::min<long long>(tiles, 256));
-        chunk = ((tiles + want - 1) / want) * kTR;
-    }
-    if (((long long)N + chunk - 1) / chunk > kProbeMaxParts) chunk = ((((long long)N + kProbeMaxParts - 1) / kProbeMaxParts + kTR - 1) / kTR) * kTR;
-    p.chunk = (int)std::min<long long>(chunk, 0x7fffff80);
-    p.parts = (int)(((long long)N + p.chunk - 1) / p.chunk);
+    const RowParts r = row_parts(N, kTR, 256, kProbeMaxParts, chunk_opt);
+    p.parts = r.parts; p.chunk = r.chunk;
     return p;
 }
 
@@ -848,13 +836,19 @@ hipError_t probe_pass(hipStream_t st, const ProbeWs& b, const float* x, int mode
     return hipGetLastError();
 }
 
+// one workgroup per problem of the per-problem kernel of a phase
+typedef void (*ProbeVecKernel)(ProbeWs, int, int, int, float, ProbeAlphas);
+static hipError_t launch_vec(hipStream_t st, ProbeVecKernel kern, const ProbeWs& b, int P, int k, int max_newton, int inner, float tol, const ProbeAlphas& al)
+{
+    hipLaunchKernelGGL(kern, dim3((unsigned)P), dim3(256), 0, st, b, k, max_newton, inner, tol, al);
+    return hipGetLastError();
+}
+
 hipError_t probe_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_cg, float tol, const ProbeAlphas& al)
 {
-    const dim3 grid((unsigned)P);
-    if (phase == 0) hipLaunchKernelGGL(probe_vec_kernel<0>, grid, dim3(256), 0, st, b, k, max_newton, max_cg, tol, al);
-    else if (phase == 1) hipLaunchKernelGGL(probe_vec_kernel<1>, grid, dim3(256), 0, st, b, k, max_newton, max_cg, tol, al);
-    else hipLaunchKernelGGL(probe_vec_kernel<2>, grid, dim3(256), 0, st, b, k, max_newton, max_cg, tol, al);
-    return hipGetLastError();
+    static const ProbeVecKernel kern[3] = {probe_vec_kernel<0>, probe_vec_kernel<1>, probe_vec_kernel<2>};
+    if (phase < 0 || phase > 2) return hipErrorInvalidValue;
+    return launch_vec(st, kern[phase], b, P, k, max_newton, max_cg, tol, al);
 }
 
 hipError_t probe_trial(hipStream_t st, const ProbeWs& b, const ProbeAlphas& al)
@@ -892,12 +886,9 @@ hipError_t probe_l1_curv(hipStream_t st, const ProbeWs& b)
 
 hipError_t probe_l1_vec(hipStream_t st, const ProbeWs& b, int P, int phase, int k, int max_newton, int max_inner, float tol, const ProbeAlphas& al)
 {
-    const dim3 grid((unsigned)P);
-    if (phase == 0) hipLaunchKernelGGL(probe_l1_vec_kernel<0>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
-    else if (phase == 1) hipLaunchKernelGGL(probe_l1_vec_kernel<1>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
-    else if (phase == 2) hipLaunchKernelGGL(probe_l1_vec_kernel<2>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
-    else hipLaunchKernelGGL(probe_l1_vec_kernel<3>, grid, dim3(256), 0, st, b, k, max_newton, max_inner, tol, al);
-    return hipGetLastError();
+    static const ProbeVecKernel kern[4] = {probe_l1_vec_kernel<0>, probe_l1_vec_kernel<1>, probe_l1_vec_kernel<2>, probe_l1_vec_kernel<3>};
+    if (phase < 0 || phase > 3) return hipErrorInvalidValue;
+    return launch_vec(st, kern[phase], b, P, k, max_newton, max_inner, tol, al);
 }
 
 // out (n, P) = x~ w^T: w packed into W (Ppad, LD) first, then the PANEL pass

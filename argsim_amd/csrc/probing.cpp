@@ -1,5 +1,5 @@
-// probing.cpp -- linear probes of latent rows: the lockstep truncated-Newton loop of avae_probe_fit, the lockstep proximal-Newton loop
-// of avae_probe_fit_l1, and avae_probe_decision (contract: include/argsim_vae.h; kernels: probe.hip).
+// probing.cpp -- linear probes of latent rows: the lockstep Newton loop that avae_probe_fit (truncated Newton) and avae_probe_fit_l1
+// (proximal Newton) share, and avae_probe_decision (contract: include/argsim_vae.h; kernels: probe.hip).
 #include "ctx.h"
 
 using namespace avae;
@@ -52,6 +52,72 @@ void probe_rounds(ProbeAlphas (&r)[4])
     }
 }
 
+// what the three entries ask of their shape: n rows of x (n, dim) against P problems w (P, dim + 1)
+int check_probe_shape(avae_ctx* h, const char* what, int n, int P, int dim, const float* x, const float* w)
+{
+    const std::string p(what);
+    if (n < 1 || P < 1) return fail(h, p + ": N and P must be >= 1");
+    if (P > (1 << 20)) return fail(h, p + ": at most 2^20 problems per call");
+    if (n > 0x7fffffff - 255) return fail(h, p + ": at most 2^31 - 256 rows per call");
+    return check_rows(h, what, dim, "x and w", {x, w});
+}
+
+// One fit as the two entries state it: l1 -- the proximal Newton method; inner -- max_cg or max_inner.
+struct ProbeFit { const char* what; bool l1; int max_newton, inner; float tol; int reserved; };
+
+// Per Newton iteration GRAD + vec, the synchronisation, max `inner` x (HV + vec), PANEL, 4 x (trial + vec).  The L1 fit has the
+// workspace of the L2 fit, 3 more vectors per problem and the copy xs of x (probe_l1_layout) which its passes read in place of x,
+// its own per-problem kernel, and the curvature sums + vec behind the synchronisation.
+int probe_fit(avae_ctx* h, const ProbeFit& f, const float* x, int N, int dim, const float* s, int P, float* w, float* stats)
+{
+    const std::string name(f.what);
+    if (!x || !s || !w) return fail(h, name + ": x, s and w must be given");
+    AV_TRY(check_probe_shape(h, f.what, N, P, dim, x, w));
+    if (f.max_newton < 1 || f.inner < 1) return fail(h, name + (f.l1 ? ": max_newton and max_inner must be >= 1" : ": max_newton and max_cg must be >= 1"));
+    if (!(f.tol >= 0.f)) return fail(h, name + ": tol must be >= 0 (and not NaN)");
+    if (f.reserved != 0) return fail(h, name + ": the reserved field must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    const ProbePlan p = probe_plan(N, P, dim, h->probe_chunk);
+    if ((long long)p.parts * p.ptiles > 0x7fffffffLL) return fail(h, name + ": too many (row part, problem tile) workgroups for one launch");
+    ProbeWs b{};
+    AV_TRY(place_ws(h, f.what, [&](Bump& bp) { f.l1 ? probe_l1_layout(bp, b, p, N, dim) : probe_layout(bp, b, p, N, dim); }));
+    ProbeAlphas rounds[4];
+    probe_rounds(rounds);
+    const ProbeAlphas none{};
+    auto vec = [&](int phase, int k, const ProbeAlphas& al) {
+        return f.l1 ? probe_l1_vec(h->stream, b, P, phase, k, f.max_newton, f.inner, f.tol, al) : probe_vec(h->stream, b, P, phase, k, f.max_newton, f.inner, f.tol, al);
+    };
+    std::vector<int> state((size_t)p.Ppad * 8);
+    if (f.l1) { AV_CHECK(probe_l1_prepare(h->stream, b, x, s, P)); x = b.xs; }
+    else AV_CHECK(probe_prepare(h->stream, b, s, P));
+    for (int it = 0; it <= f.max_newton; ++it) {
+        AV_CHECK(probe_pass(h->stream, b, x, 0));
+        AV_CHECK(vec(0, it, none));
+        // the one synchronisation of a Newton iteration: is any problem still running?  (What every problem does next is decided on
+        // the device; an answer read later would stop the loop later and change nothing.)
+        AV_CHECK(hipMemcpyAsync(state.data(), b.is, state.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        AV_CHECK(hipStreamSynchronize(h->stream));
+        bool alive = false;
+        for (int q = 0; q < P; ++q) alive = alive || state[(size_t)q * 8 + 2] == 0;
+        if (!alive) break;
+        if (f.l1) {
+            AV_CHECK(probe_l1_curv(h->stream, b));
+            AV_CHECK(vec(3, it, none));
+        }
+        for (int k = 0; k < f.inner; ++k) {
+            AV_CHECK(probe_pass(h->stream, b, x, 1));
+            AV_CHECK(vec(1, k, none));
+        }
+        AV_CHECK(probe_pass(h->stream, b, x, 2));
+        for (int r = 0; r < 4; ++r) {
+            AV_CHECK(probe_trial(h->stream, b, rounds[r]));
+            AV_CHECK(vec(2, r, rounds[r]));
+        }
+    }
+    AV_CHECK(probe_finish(h->stream, b, P, w, stats));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -60,121 +126,27 @@ int avae_probe_fit(avae_handle h, const float* x, int32_t N, int32_t dim, const 
 {
     if (!h) return 1;
     if (!pc) return fail(h, "probe config is null");
-    if (!x || !s || !w) return fail(h, "probe: x, s and w must be given");
-    if (N < 1 || P < 1) return fail(h, "probe: N and P must be >= 1");
-    if (P > (1 << 20)) return fail(h, "probe: at most 2^20 problems per call");
-    if (N > 0x7fffffff - 255) return fail(h, "probe: at most 2^31 - 256 rows per call");
-    if (pc->max_newton < 1 || pc->max_cg < 1) return fail(h, "probe: max_newton and max_cg must be >= 1");
-    if (!(pc->tol >= 0.f)) return fail(h, "probe: tol must be >= 0 (and not NaN)");
-    if (pc->reserved != 0) return fail(h, "probe: the reserved field must be 0");
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "probe: dim must be a multiple of 4 in [4, 1024]");
-    if (((uintptr_t)x | (uintptr_t)w) & 15) return fail(h, "probe: x and w must be 16-byte aligned");
-    AV_CHECK(hipSetDevice(h->device));
-    const ProbePlan p = probe_plan(N, P, dim, h->probe_chunk);
-    if ((long long)p.parts * p.ptiles > 0x7fffffffLL ) return fail(h, "probe: too many (row part, problem tile) workgroups for one launch");
-    ProbeWs b{};
-    Bump probe{nullptr};
-    probe_layout(probe, b, p, N, dim);
-    AV_TRY(reserve_named(h, probe.off + 4096, "probe"));        // sized once per call; nothing is allocated between the launches
-    Bump real{h->ws};
-    probe_layout(real, b, p, N, dim);
-    ProbeAlphas rounds[4];
-    probe_rounds(rounds);
-    const ProbeAlphas none{};
-    std::vector<int> state((size_t)p.Ppad * 8);
-    AV_CHECK(probe_prepare(h->stream, b, s, P));
-    for (int it = 0; it <= pc->max_newton; ++it) {
-        AV_CHECK(probe_pass(h->stream, b, x, 0));
-        AV_CHECK(probe_vec(h->stream, b, P, 0, it, pc->max_newton, pc->max_cg, pc->tol, none));
-        // the one synchronisation of a Newton iteration: is any problem still running?  (What every problem does next is decided on
-        // the device; an answer read later would stop the loop later and change nothing.)
-        AV_CHECK(hipMemcpyAsync(state.data(), b.is, state.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        AV_CHECK(hipStreamSynchronize(h->stream));
-        bool alive = false;
-        for (int q = 0; q < P; ++q) alive = alive || state[(size_t)q * 8 + 2] == 0;
-        if (!alive) break;
-        for (int k = 0; k < pc->max_cg; ++k) {
-            AV_CHECK(probe_pass(h->stream, b, x, 1));
-            AV_CHECK(probe_vec(h->stream, b, P, 1, k, pc->max_newton, pc->max_cg, pc->tol, none));
-        }
-        AV_CHECK(probe_pass(h->stream, b, x, 2));
-        for (int r = 0; r < 4; ++r) {
-            AV_CHECK(probe_trial(h->stream, b, rounds[r]));
-            AV_CHECK(probe_vec(h->stream, b, P, 2, r, pc->max_newton, pc->max_cg, pc->tol, rounds[r]));
-        }
-    }
-    AV_CHECK(probe_finish(h->stream, b, P, w, stats));
-    return 0;
+    return probe_fit(h, ProbeFit{"probe", false, pc->max_newton, pc->max_cg, pc->tol, pc->reserved}, x, N, dim, s, P, w, stats);
 }
 
-// The L1 fit: the workspace of the L2 fit, 3 more vectors per problem and the copy of x (probe_l1_layout), and per proximal Newton
-// iteration GRAD + vec, the synchronisation, the curvature sums + vec, max_inner x (HV + vec), PANEL, 4 x (trial + vec).
 int avae_probe_fit_l1(avae_handle h, const float* x, int32_t N, int32_t dim, const float* s, int32_t P, const avae_probe_l1_config* pc, float* w, float* stats)
 {
     if (!h) return 1;
     if (!pc) return fail(h, "probe l1 config is null");
-    if (!x || !s || !w) return fail(h, "probe l1: x, s and w must be given");
-    if (N < 1 || P < 1) return fail(h, "probe l1: N and P must be >= 1");
-    if (P > (1 << 20)) return fail(h, "probe l1: at most 2^20 problems per call");
-    if (N > 0x7fffffff - 255) return fail(h, "probe l1: at most 2^31 - 256 rows per call");
-    if (pc->max_newton < 1 || pc->max_inner < 1) return fail(h, "probe l1: max_newton and max_inner must be >= 1");
-    if (!(pc->tol >= 0.f)) return fail(h, "probe l1: tol must be >= 0 (and not NaN)");
-    if (pc->reserved != 0) return fail(h, "probe l1: the reserved field must be 0");
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "probe l1: dim must be a multiple of 4 in [4, 1024]");
-    if (((uintptr_t)x | (uintptr_t)w) & 15) return fail(h, "probe l1: x and w must be 16-byte aligned");
-    AV_CHECK(hipSetDevice(h->device));
-    const ProbePlan p = probe_plan(N, P, dim, h->probe_chunk);
-    if ((long long)p.parts * p.ptiles > 0x7fffffffLL ) return fail(h, "probe l1: too many (row part, problem tile) workgroups for one launch");
-    ProbeWs b{};
-    Bump probe{nullptr};
-    probe_l1_layout(probe, b, p, N, dim);
-    AV_TRY(reserve_named(h, probe.off + 4096, "probe l1"));     // sized once per call; nothing is allocated between the launches
-    Bump real{h->ws};
-    probe_l1_layout(real, b, p, N, dim);
-    ProbeAlphas rounds[4];
-    probe_rounds(rounds);
-    const ProbeAlphas none{};
-    std::vector<int> state((size_t)p.Ppad * 8);
-    AV_CHECK(probe_l1_prepare(h->stream, b, x, s, P));
-    for (int it = 0; it <= pc->max_newton; ++it) {
-        AV_CHECK(probe_pass(h->stream, b, b.xs, 0));
-        AV_CHECK(probe_l1_vec(h->stream, b, P, 0, it, pc->max_newton, pc->max_inner, pc->tol, none));
-        // the one synchronisation of an iteration, as in avae_probe_fit
-        AV_CHECK(hipMemcpyAsync(state.data(), b.is, state.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        AV_CHECK(hipStreamSynchronize(h->stream));
-        bool alive = false;
-        for (int q = 0; q < P; ++q) alive = alive || state[(size_t)q * 8 + 2] == 0;
-        if (!alive) break;
-        AV_CHECK(probe_l1_curv(h->stream, b));
-        AV_CHECK(probe_l1_vec(h->stream, b, P, 3, it, pc->max_newton, pc->max_inner, pc->tol, none));
-        for (int k = 0; k < pc->max_inner; ++k) {
-            AV_CHECK(probe_pass(h->stream, b, b.xs, 1));
-            AV_CHECK(probe_l1_vec(h->stream, b, P, 1, k, pc->max_newton, pc->max_inner, pc->tol, none));
-        }
-        AV_CHECK(probe_pass(h->stream, b, b.xs, 2));
-        for (int r = 0; r < 4; ++r) {
-            AV_CHECK(probe_trial(h->stream, b, rounds[r]));
-            AV_CHECK(probe_l1_vec(h->stream, b, P, 2, r, pc->max_newton, pc->max_inner, pc->tol, rounds[r]));
-        }
-    }
-    AV_CHECK(probe_finish(h->stream, b, P, w, stats));
-    return 0;
+    return probe_fit(h, ProbeFit{"probe l1", true, pc->max_newton, pc->max_inner, pc->tol, pc->reserved}, x, N, dim, s, P, w, stats);
 }
 
 int avae_probe_decision(avae_handle h, const float* x, int32_t n, int32_t dim, const float* w, int32_t P, float* out)
 {
     if (!h) return 1;
     if (!x || !w || !out) return fail(h, "probe decision: x, w and out must be given");
-    if (n < 1 || P < 1) return fail(h, "probe decision: n and P must be >= 1");
-    if (P > (1 << 20)) return fail(h, "probe decision: at most 2^20 problems per call");
-    if (n > 0x7fffffff - 255) return fail(h, "probe decision: at most 2^31 - 256 rows per call");
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "probe decision: dim must be a multiple of 4 in [4, 1024]");
-    if (((uintptr_t)x | (uintptr_t)w) & 15) return fail(h, "probe decision: x and w must be 16-byte aligned");
+    AV_TRY(check_probe_shape(h, "probe decision", n, P, dim, x, w));
     AV_CHECK(hipSetDevice(h->device));
     const ProbePlan p = probe_plan(n, P, dim, h->probe_chunk);
     if ((long long)p.parts * p.ptiles > 0x7fffffffLL ) return fail(h, "probe decision: too many (row part, problem tile) workgroups for one launch");
-    AV_TRY(reserve_named(h, (size_t)p.Ppad * p.LD * sizeof(float) + 4096, "probe decision"));
-    AV_CHECK(probe_decision(h->stream, p, x, n, dim, w, P, reinterpret_cast<float*>(h->ws), out));
+    float* W = nullptr;
+    AV_TRY(place_ws(h, "probe decision", [&](Bump& b) { W = b.take<float>((size_t)p.Ppad * p.LD); }));
+    AV_CHECK(probe_decision(h->stream, p, x, n, dim, w, P, W, out));
     return 0;
 }
 

@@ -47,12 +47,7 @@ int score_ws(avae_ctx* h, const ScorePlan& sp, int B, int k, int Ss, int St, Sco
             seen.push_back(n);
             Bump b{nullptr}; layout(h, b, w, n, 1, St, false); top = std::max(top, b.off);
         }
-    Bump probe{nullptr}; probe.off = top;
-    score_layout(probe, s, B, k, h->cfg.dim_rep, sp.N, St);
-    AV_TRY(reserve_ws(h, probe.off + 4096));
-    Bump real{h->ws}; real.off = top;
-    score_layout(real, s, B, k, h->cfg.dim_rep, sp.N, St);
-    return 0;
+    return place_ws(h, "score", [&](Bump& b) { score_layout(b, s, B, k, h->cfg.dim_rep, sp.N, St); }, top);
 }
 
 // Teacher-forced log p(tgt row | z row) for the k draws of B rows, s.z in decoder-batch order (kernels.h ScoreDraw): s.logpx (k, B),
@@ -128,20 +123,22 @@ int avae_knn(avae_handle h, const float* q, int32_t n, const float* bank, int32_
     if (N > 0x7fffffff - 256) return fail(h, "knn: at most 2^31 - 256 bank rows per call (stream a larger bank with carry)");
     if (kc->k < 1 || kc->k > 32) return fail(h, "knn: k must be in [1, 32]");
     if (kc->metric < 0 || kc->metric > 2) return fail(h, "knn: metric must be 0 (dot), 1 (cosine) or 2 (squared Euclidean)");
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "knn: dim must be a multiple of 4 in [4, 1024]");
     if (kc->idx_base < 0 || kc->self_base < -1) return fail(h, "knn: idx_base must be >= 0 and self_base >= -1");
     if (kc->carry != 0 && kc->carry != 1) return fail(h, "knn: carry must be 0 or 1");
     if (kc->reserved != 0) return fail(h, "knn: the reserved field must be 0");
-    if (((uintptr_t)q | (uintptr_t)bank) & 15) return fail(h, "knn: q and bank must be 16-byte aligned");
+    AV_TRY(check_rows(h, "knn", dim, "q and bank", {q, bank}));
     AV_CHECK(hipSetDevice(h->device));
     const KnnPlan p = knn_plan(n, N, kc->k, h->knn_chunk);
     if ((long long)p.qtiles * std::max(p.parts, 1) > 0x7fffffffLL) return fail(h, "knn: too many (query tile, bank part) workgroups for one launch");
-    const size_t need = knn_ws_bytes(p, n, N, kc->k);
-    AV_TRY(reserve_ws(h, need + 4096));                          // sized once per call; nothing is allocated between the launches
+    KnnWs w{};
+    AV_TRY(place_ws(h, "knn", [&](Bump& b) {
+        w.qn = b.take<float>((size_t)n); w.bn = b.take<float>((size_t)N);
+        w.lists = b.take<unsigned long long>((size_t)n * p.parts * kc->k);
+    }));
     KnnArgs a{};
     a.q = q; a.bank = bank; a.n = n; a.N = N; a.dim = dim; a.k = kc->k; a.metric = kc->metric;
     a.idx_base = kc->idx_base; a.self_base = kc->self_base; a.carry = kc->carry; a.out_idx = out_idx; a.out_score = out_score;
-    AV_CHECK(knn_search(h->stream, a, p, h->ws));
+    AV_CHECK(knn_search(h->stream, a, p, w));
     return 0;
 }
 
@@ -155,8 +152,7 @@ int avae_agg_logq(avae_handle h, const float* z, int32_t n, const float* mu, con
     if (!z || !mu || !lv || !logq) return fail(h, "agg: z, mu, lv and logq must be given");
     if (n < 1 || N < 1) return fail(h, "agg: n and N must be >= 1");
     if (N > 0x7fffffff - 256) return fail(h, "agg: at most 2^31 - 256 bank rows per call");
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "agg: dim must be a multiple of 4 in [4, 1024]");
-    if (((uintptr_t)z | (uintptr_t)mu | (uintptr_t)lv) & 15) return fail(h, "agg: z, mu and lv must be 16-byte aligned");
+    AV_TRY(check_rows(h, "agg", dim, "z, mu and lv", {z, mu, lv}));
     if (ac->self_base < -1) return fail(h, "agg: self_base must be >= -1");
     if (ac->self_base >= 0 && ac->self_base + (int64_t)n > (int64_t)N) return fail(h, "agg: self_base + n exceeds N (query i's own bank row is self_base + i)");
     if (logqx && ac->self_base < 0) return fail(h, "agg: logqx needs self_base >= 0");
@@ -164,10 +160,11 @@ int avae_agg_logq(avae_handle h, const float* z, int32_t n, const float* mu, con
     AV_CHECK(hipSetDevice(h->device));
     const AggPlan p = agg_plan(n, N, dim, h->agg_chunk);
     if ((long long)p.qtiles * p.parts > 0x7fffffffLL) return fail(h, "agg: too many (query tile, bank part) workgroups for one launch");
-    AV_TRY(reserve_ws(h, agg_ws_bytes(p, n) + 4096));            // sized once per call; nothing is allocated between the launches
+    float2* parts_ms = nullptr;
+    AV_TRY(place_ws(h, "agg", [&](Bump& b) { parts_ms = b.take<float2>((size_t)p.parts * n); }));
     AggArgs a{};
     a.z = z; a.mu = mu; a.lv = lv; a.n = n; a.N = N; a.dim = dim; a.self_base = ac->self_base; a.logq = logq; a.logqx = logqx;
-    AV_CHECK(agg_logq(h->stream, a, p, h->ws));
+    AV_CHECK(agg_logq(h->stream, a, p, parts_ms));
     return 0;
 }
 
@@ -177,11 +174,11 @@ int avae_latent_moments(avae_handle h, const float* mu, const float* lv, int32_t
     if (!mu || !lv || !out) return fail(h, "moments: mu, lv and out must be given");
     if (N < 1) return fail(h, "moments: N must be >= 1");
     if (N > 0x7fffffff - 256) return fail(h, "moments: at most 2^31 - 256 rows per call");
-    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "moments: dim must be a multiple of 4 in [4, 1024]");
-    if (((uintptr_t)mu | (uintptr_t)lv) & 15) return fail(h, "moments: mu and lv must be 16-byte aligned");
+    AV_TRY(check_rows(h, "moments", dim, "mu and lv", {mu, lv}));
     AV_CHECK(hipSetDevice(h->device));
-    AV_TRY(reserve_ws(h, moments_ws_bytes(N, dim) + 4096));
-    AV_CHECK(latent_moments(h->stream, mu, lv, N, dim, out, h->ws));
+    double *mean = nullptr, *part = nullptr;
+    AV_TRY(place_ws(h, "moments", [&](Bump& b) { mean = b.take<double>((size_t)dim); part = b.take<double>((size_t)moments_blocks(N) * 3 * dim); }));
+    AV_CHECK(latent_moments(h->stream, mu, lv, N, dim, out, mean, part));
     return 0;
 }
 
