@@ -1,5 +1,6 @@
 // clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
-// (kernels: ward.hip) and of avae_affinity (kernels: affinity.hip).  Contract: include/argsim_vae.h.
+// (kernels: ward.hip), of avae_affinity (kernels: affinity.hip) and of avae_tsne (kernels: tsne.hip, the distances affinity.hip's).
+// Contract: include/argsim_vae.h.
 #include "ctx.h"
 
 using namespace avae;
@@ -142,6 +143,70 @@ int avae_affinity(avae_handle h, const float* x, int32_t N, int32_t dim, const a
     // every round is enqueued; a launch that finds the stop decided returns at once.  Never a synchronisation
     for (int it = 0; it < ac->max_iter; ++it) AV_CHECK(ap_iteration(h->stream, b, N, ac->damping, it, ac->convergence_iter));
     AV_CHECK(ap_labels(h->stream, b, N, label, stat));
+    return 0;
+}
+
+int avae_tsne(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_tsne_config* tc, const double* p_in, float* y, double* kl,
+              int32_t* stat, double* p_out, double* beta_out, double* trace, float* grad, float* ug, double* prog)
+{
+    if (!h) return 1;
+    if (!tc) return fail(h, "tsne config is null");
+    if (!y || !kl || !stat) return fail(h, "tsne: y, kl and stat must be given");
+    if (!x && !p_in) return fail(h, "tsne: x or p_in must be given");
+    if (N < 2 || N > kTsneMaxN) return fail(h, "tsne: N must be in [2, 2^14]");
+    if (!p_in) {
+        AV_TRY(check_rows(h, "tsne", dim, "x", {x}));
+        if (!(tc->perplexity > 0.0 && tc->perplexity < (double)N)) return fail(h, "tsne: perplexity must be in (0, N)");
+    }
+    if (((uintptr_t)y | (uintptr_t)ug) & 7) return fail(h, "tsne: y and ug must be 8-byte aligned");
+    if (tc->max_iter < 0 || tc->max_iter > 32768) return fail(h, "tsne: max_iter must be in [0, 32768]");
+    if (tc->it0 < 0 || tc->it0 > tc->max_iter) return fail(h, "tsne: it0 must be in [0, max_iter]");
+    if (tc->exaggeration_iter < 0) return fail(h, "tsne: exaggeration_iter must be >= 0");
+    if (tc->n_iter_check < 1) return fail(h, "tsne: n_iter_check must be >= 1");
+    if (tc->n_iter_without_progress < 0) return fail(h, "tsne: n_iter_without_progress must be >= 0");
+    if (!(tc->early_exaggeration >= 1.0)) return fail(h, "tsne: early_exaggeration must be >= 1");
+    if (tc->learning_rate != tc->learning_rate) return fail(h, "tsne: learning_rate is NaN");
+    if (tc->init < 0 || tc->init > 1) return fail(h, "tsne: init must be 0 (y holds the start) or 1 (random)");
+    if ((ug == nullptr) != (prog == nullptr)) return fail(h, "tsne: ug and prog are given together or not at all");
+    if (tc->warm && !ug) return fail(h, "tsne: a warm continuation reads ug and prog, which are not given");
+    if (tc->reserved[0] != 0 || tc->reserved[1] != 0) return fail(h, "tsne: the reserved fields must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    // Workspace, every buffer on a 256-byte boundary: P of 8 N^2 bytes unless the caller gives p_in or p_out, with x the
+    // distances of 4 N^2 bytes, beta and the row sums, the partials of the walks (48 N parts bytes), update and gains unless ug is
+    // given, and the state
+    const size_t n = (size_t)N;
+    const TsnePlan plan = tsne_plan(N, h->tsne_chunk);
+    if (plan.chunk > kTsneMaxChunk || plan.parts < 1) return fail(h, "tsne: no plan for this N");
+    TsneArgs a{};
+    double *P = nullptr, *beta = nullptr, *rowsum = nullptr; float* D = nullptr;
+    AV_TRY(place_ws(h, "tsne", [&](Bump& b) {
+        a.st = b.take<TsneState>(1);
+        P = p_out ? p_out : (p_in ? nullptr : b.take<double>(n * n));
+        if (!p_in) { D = b.take<float>(n * n); rowsum = b.take<double>(n); beta = beta_out ? beta_out : b.take<double>(n); }
+        a.part = b.take<double>(n * plan.parts * 5);
+        a.errp = b.take<double>(n * plan.parts);
+        a.upd = ug ? ug : b.take<float>(2 * n);
+        a.gains = ug ? ug + 2 * n : b.take<float>(2 * n);
+    }));
+    if (p_in) {
+        if (P && P != p_in) AV_CHECK(hipMemcpyAsync(P, p_in, n * n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        a.P = P ? P : p_in;
+    } else {
+        AV_CHECK(ap_similarity(h->stream, x, N, dim, 0, D));
+        AV_CHECK(tsne_conditionals(h->stream, D, N, tc->perplexity, P, beta));
+        AV_CHECK(tsne_joint(h->stream, P, N, rowsum));
+        a.P = P;
+    }
+    a.y = y; a.grad = grad; a.trace = trace;
+    a.N = N; a.rs = plan.rs; a.parts = plan.parts; a.chunk = plan.chunk;
+    a.max_iter = tc->max_iter; a.exag_iter = tc->exaggeration_iter; a.X = std::min(tc->exaggeration_iter, tc->max_iter);
+    a.nic = tc->n_iter_check; a.nwp = tc->n_iter_without_progress;
+    a.lr = tc->learning_rate > 0.f ? tc->learning_rate : (float)std::max((double)N / tc->early_exaggeration / 4.0, 50.0);
+    a.ee = tc->early_exaggeration; a.min_gn = tc->min_grad_norm;
+    AV_CHECK(tsne_init(h->stream, a, tc->it0, tc->warm, tc->init, tc->seed, prog));
+    // every iteration is enqueued; a launch that finds the stop decided returns at once.  Never a synchronisation
+    for (int it = tc->it0; it < tc->max_iter; ++it) AV_CHECK(tsne_iteration(h->stream, a, it));
+    AV_CHECK(tsne_finish(h->stream, a, kl, stat, prog));
     return 0;
 }
 

@@ -462,6 +462,37 @@ hipError_t ap_prepare(hipStream_t st, float* S, int N, int use_pref, float pref,
 hipError_t ap_iteration(hipStream_t st, const ApBuffers& b, int N, float lam, int it, int conv_iter);      // three launches
 hipError_t ap_labels(hipStream_t st, const ApBuffers& b, int N, int32_t* label, int32_t* stat);
 
+// ---------------------------------------------------------------- exact t-SNE of latent rows (tsne.hip)
+// One set of N rows per call (contract: include/argsim_vae.h, avae_tsne).  The buffers are workspace laid out by the caller
+// (clustering.cpp) or the caller's own outputs; tsne_init writes the state before the first iteration.
+constexpr int kTsneMaxN = 1 << 14;
+constexpr int kTsneMaxChunk = 4096;   // columns of a part at most: its slice of y is staged in LDS
+struct TsneState {
+    int stop_at;                      // 0: running; it + 1: iteration it ended phase 2 (a launch of a later iteration returns at once)
+    int phase, best_iter;             // 1 or 2; sklearn's best_iter of the phase
+    int last_it, how, p1_last;        // the last iteration run, how phase 2 ended, the last iteration of phase 1 in this call or -1
+    int pad[2];
+    double best_error, last_err, p1_err;      // sklearn's best_error; the last error computed; the error of phase 1's last iteration
+};
+struct TsnePlan { int rs, parts, chunk; };      // rows per workgroup, column parts, columns per part of the walks
+struct TsneArgs {
+    const double* P;                  // (N, N) the joint matrix
+    float *y, *upd, *gains;           // (N, 2) each
+    float* grad;                      // (N, 2) or null
+    double* trace;                    // (2, max_iter) or null
+    double *part, *errp;              // (N, parts, 5) pair sums; (N, parts) error sums
+    TsneState* st;
+    int N, rs, parts, chunk;
+    int max_iter, X, exag_iter, nic, nwp;      // X = min(exag_iter, max_iter): phase 1's window
+    float lr; double ee, min_gn;
+};
+TsnePlan tsne_plan(int N, int chunk_opt);
+hipError_t tsne_conditionals(hipStream_t st, const float* S /* -D: ap_similarity, metric 0 */, int N, double perplexity, double* C, double* beta);
+hipError_t tsne_joint(hipStream_t st, double* P /* the conditionals, in place */, int N, double* rowsum /* (N) workspace */);
+hipError_t tsne_init(hipStream_t st, const TsneArgs& a, int it0, int warm, int init, uint64_t seed, const double* prog);
+hipError_t tsne_iteration(hipStream_t st, const TsneArgs& a, int it);      // two launches, three where the error may be computed
+hipError_t tsne_finish(hipStream_t st, const TsneArgs& a, double* kl, int32_t* stat, double* prog);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

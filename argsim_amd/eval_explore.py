@@ -6,6 +6,10 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
 
     python -m argsim_amd.eval_explore --inputs data/test_data_emb.npy --labels data/test_labels.npy \\
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
+        [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]]
+
+With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
+device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
 
 The labels are eval_cluster's topic-stance-reason strings; the topics are listed in order of first appearance.  A purity line is the
 topic, then share|members|cluster for the clusters of which at least half the members (and at least two) belong to the topic."""
@@ -49,6 +53,17 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200):
     return cols, lines
 
 
+def embed(vae, z, labels, out, plot=None, perplexity=40.0, max_iter=20000, seed=0):
+    """eval_clustering_explorative.py:45-66 -> (the result of VAE.tsne, the line that is printed); the embedding goes to `out`"""
+    from . import tsne
+    from .eval_cluster import split_labels
+    res = vae.tsne(z, perplexity=perplexity, max_iter=max_iter, init='random', seed=seed)
+    np.save(out, res['y'])
+    if plot:
+        tsne.plot(plot, res['y'], [p[0] for p in split_labels(labels)])
+    return res, "t-SNE: KL %.6f after %d iterations (%s)" % (res['kl'], res['n_iter'], res['stop'])
+
+
 def write_csv(path, posts, topics, labels, cols):
     """eval_clustering_explorative.py:121-132: the id, then the columns in the reference's order (those of absent runs left out)"""
     names = [c for c in COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
@@ -68,6 +83,10 @@ def build_parser():
     ap.add_argument('--posts', default=None, help=".npy (n,) the posts' text, for the CSV's post column (empty without)")
     ap.add_argument('--csv', default=None, help="write the cluster numbers and centroid distances here")
     ap.add_argument('--max-iter', type=int, default=200)
+    ap.add_argument('--tsne', default=None, help="write the two-dimensional t-SNE embedding of the inputs here (.npy)")
+    ap.add_argument('--tsne-plot', default=None, help="with --tsne: the scatter by topic as an image (needs matplotlib)")
+    ap.add_argument('--perplexity', type=float, default=40.0)
+    ap.add_argument('--tsne-iter', type=int, default=20000)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -81,7 +100,12 @@ def main(argv=None):
     labels = np.load(A.labels)
     if z.shape[0] != len(labels) or (z_sp is not None and z_sp.shape[0] != len(labels)):
         raise ValueError("one label per row of the inputs")
-    cols, lines = evaluate(make_vae(A.device), z, z_sp, labels, A.seed, A.max_iter)
+    if A.tsne_plot and not A.tsne:
+        raise ValueError("--tsne-plot needs --tsne")
+    vae = make_vae(A.device)
+    if A.tsne:
+        print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
+    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter)
     for line in lines:
         print(line)
     if A.csv:

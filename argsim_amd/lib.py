@@ -79,6 +79,13 @@ class AvaeAffinityConfig(C.Structure):
                 ('reserved', C.c_int32 * 2)]
 
 
+class AvaeTsneConfig(C.Structure):
+    _fields_ = [('perplexity', C.c_double), ('early_exaggeration', C.c_double), ('min_grad_norm', C.c_double), ('learning_rate', C.c_float),
+                ('max_iter', C.c_int32), ('it0', C.c_int32), ('exaggeration_iter', C.c_int32), ('n_iter_check', C.c_int32),
+                ('n_iter_without_progress', C.c_int32), ('init', C.c_int32), ('warm', C.c_int32), ('seed', C.c_uint64),
+                ('reserved', C.c_int32 * 2)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -121,6 +128,7 @@ SIGNATURES = {
     'avae_ward': (C.c_int, [_P, _P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(AvaeWardConfig), _P, _P, _P]),
     'avae_ward_cut': (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P]),
     'avae_affinity': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeAffinityConfig), _P, _P, _P, _P, _P]),
+    'avae_tsne': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeTsneConfig)] + [_P] * 10),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),

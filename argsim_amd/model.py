@@ -19,6 +19,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) L1 probes: the useful dimensions (liblinear) -> VAE.probe_fit_l1(z, labels) / VAE.select_dims(z, labels)
     (new) Ward clustering of latent rows (ARS, V_MSR)  -> VAE.ward(z, groups) / VAE.ward_cut(res, k) / VAE.cluster_eval(z, gold, groups)
     (new) affinity propagation of latent rows          -> VAE.affinity(z, metric, ...) / affinity(vae, z, ...)
+    (new) exact t-SNE of latent rows                   -> VAE.tsne(z, perplexity, ...) / tsne(vae, z, ...)
 """
 import ctypes as C
 
@@ -642,6 +643,17 @@ class VAE:
         from . import affinity
         return affinity.affinity(self, z, metric, preference, damping, max_iter, convergence_iter, seed, noise, return_messages)
 
+    def tsne(self, z, perplexity=30.0, max_iter=1000, init='pca', seed=0, learning_rate='auto', early_exaggeration=12.0,
+             exaggeration_iter=250, n_iter_check=50, n_iter_without_progress=300, min_grad_norm=1e-7, p=None, return_p=False,
+             return_trace=False):
+        """exact t-SNE of the rows of z into two dimensions (sklearn's TSNE(method='exact'); src/eval_clustering_explorative.py:45-66)
+        in ONE device call (include/argsim_vae.h, avae_tsne).  init: 'pca', 'random' (the generator's stream 6 from seed; what the
+        reference's sklearn did) or an (N, 2) array; p: the joint matrix of an earlier call with return_p
+        -> dict(y, kl, n_iter, stop, and with the flags p, beta, trace) (argsim_amd/tsne.py)"""
+        from . import tsne
+        return tsne.tsne(self, z, perplexity, max_iter, init, seed, learning_rate, early_exaggeration, exaggeration_iter, n_iter_check,
+                         n_iter_without_progress, min_grad_norm, p, return_p, return_trace)
+
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
 
@@ -864,3 +876,10 @@ def affinity(vae, z, metric='euclidean', preference=None, damping=0.5, max_iter=
 def cluster_eval(vae, z, gold, groups=None):
     """functional form of VAE.cluster_eval"""
     return vae.cluster_eval(z, gold, groups)
+
+
+def tsne(vae, z, perplexity=30.0, max_iter=1000, init='pca', seed=0, learning_rate='auto', early_exaggeration=12.0, exaggeration_iter=250,
+         n_iter_check=50, n_iter_without_progress=300, min_grad_norm=1e-7, p=None, return_p=False, return_trace=False):
+    """functional form of VAE.tsne"""
+    return vae.tsne(z, perplexity, max_iter, init, seed, learning_rate, early_exaggeration, exaggeration_iter, n_iter_check,
+                    n_iter_without_progress, min_grad_norm, p, return_p, return_trace)

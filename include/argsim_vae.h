@@ -545,6 +545,96 @@ int  avae_affinity(avae_handle h, const float* x /* (N, dim) device */, int32_t 
                    int32_t* label /* (N) */, int32_t* stat /* (4) */,
                    float* s_out /* (N, N), optional */, float* a /* (N, N) */, float* r /* (N, N), both or neither */);
 
+/* ---- exact t-SNE of latent rows ---------------------------------------------------------------- */
+/* The embedding plot of the reference (src/eval_clustering_explorative.py:45-66: TSNE(n_components=2, perplexity=40, n_iter=20000)
+ * over the post embeddings) as ONE call: distances, the perplexity bisection, the joint matrix and sklearn's exact gradient descent
+ * with its two phases and its stopping rule, enqueued on the handle's stream with no synchronisation inside.  Two components only.
+ * x (N, dim) is a row-major float32 device array, 16-byte aligned, dim a multiple of 4 in [4, 1024] and independent of the handle's
+ * dim_rep; 2 <= N <= 2^14; perplexity in (0, N).  With p_in, an (N, N) double joint matrix exactly as the iterations use it, x may
+ * be null and the distance and bisection stages do not run (one P, several seeds).  Every other array is a device array too.
+ *   distances  D_ij is evaluated in double, the difference first and then its square, in a fixed order, and rounded ONCE to fp32:
+ *              exactly the negative of avae_affinity's metric 0 (the same kernel).
+ *   condit.    per row i sklearn's _binary_search_perplexity in double over the fp32 D_ij, j != i: beta = 1, lo = -inf, hi = +inf, at
+ *              most 100 steps of: p_j = exp(-D_ij beta); s = sum p_j in a fixed order, the fp32 value nearest 1e-8 if that is 0;
+ *              p_j /= s; h = log s + beta sum D_ij p_j; stop when |h - log perplexity| <= the fp32 value nearest 1e-5; if h is too
+ *              large lo = beta and beta = 2 beta while hi is infinite, else (beta + hi) / 2; if too small hi = beta and beta = beta / 2
+ *              while lo is infinite, else (beta + lo) / 2.  beta_out (N) double, optional: the beta the row's p were evaluated at.
+ *   joint      i != j: P_ij = max((c_ij + c_ji) / max(Sigma, eps), eps), eps = 2^-52, Sigma the sum of all c_ij + c_ji (per row in a
+ *              fixed order, then over ascending rows); P_ii = 0.  P is double and symmetric bit for bit.  p_out (N, N) double,
+ *              optional (with p_in: a copy of it).
+ *   init       init 0: y (N, 2) fp32, in and out, holds the start.  init 1: y_ic = 1e-4f normal01(seed, 6, 2 i + c) in fp32 on the
+ *              library's counter generator, stream 6.  A warm call reads y whatever init says.
+ *   rate       learning_rate > 0 is used; otherwise max(N / early_exaggeration / 4, 50), in double on the host, rounded to fp32.
+ *   loop       iterations i = it0 .. max_iter - 1 in two phases, as sklearn's _tsne runs them.  Phase 1 covers i < X =
+ *              min(exaggeration_iter, max_iter): P' = early_exaggeration P (the product in double), momentum 0.5, window W = X.  Phase
+ *              2 starts at the iteration after phase 1's last -- exaggeration_iter - 1, or the iteration at which a check ended phase 1
+ *              -- and runs to max_iter - 1; it may be empty: P' = P, momentum 0.8, W = n_iter_without_progress.  At a phase's start
+ *              update = 0, gains = 1, best_error = DBL_MAX, best_iter = the phase's first i.  (A call that ends before
+ *              exaggeration_iter - 1 leaves phase 1 open: ug and prog hold its state.  A call whose last iteration ended phase 1
+ *              returns the fresh state of phase 2 there.)
+ *   iteration  from the fp32 y in double: d_ij = y_i - y_j, q_ij = 1 / (1 + |d_ij|^2) by IEEE division, Z = sum_{i != j} q_ij;
+ *              g_i = fp32(4 (sum_j P'_ij q_ij d_ij - (sum_j q_ij^2 d_ij) / Z)), the sums in double in a fixed order (a lane's columns
+ *              ascending, the wave butterfly, the column parts ascending; Z over all partials in one fixed order), one rounding at the end.  This is
+ *              sklearn's gradient WITHOUT its floor on Q: it differs only where q_ij / Z < eps, by less than eps q_ij |d_ij| per
+ *              pair.  Z and both sums come out of ONE pass over P.  Then in fp32, every operation rounded, nothing fused:
+ *                gains = (update g < 0) ? gains + 0.2f : gains 0.8f;  gains = max(gains, 0.01f);  g' = g gains
+ *                update = fl(fl(m update) - fl(lr g'));  y = fl(y + update)
+ *   error      computed when check = ((i + 1) % n_iter_check == 0) holds or i is the last planned iteration of its phase (X - 1, or
+ *              max_iter - 1): sum_{i != j} P'_ij log(max(P'_ij, eps) / max(q_ij / Z, eps)) in double in a fixed order, at the y the
+ *              iteration started from: sklearn's quantity.
+ *   checks     when check holds, gn = sqrt(sum g'^2) in double, then sklearn's rule: if error < best_error record it and i; else if
+ *              i - best_iter > W the phase ends; then, if it has not ended, gn <= min_grad_norm ends it.  A phase-1 end of either
+ *              kind starts phase 2 at i + 1; a phase-2 end stops the call.
+ *   stop       decided on the device: all iterations are enqueued (two launches each, three where the error may be computed) and a
+ *              launch that finds the stop decided returns at once.  No kernel waits on another workgroup; every loop is bounded by
+ *              N, dim, 100 or max_iter.
+ *   outputs    y; kl (2) double: [0] the last error computed (sklearn's kl_divergence_), [1] the error at phase 1's last iteration
+ *              (NaN where the call ran none of either); with an empty phase 2, [0] = [1].  stat (4) int32: the last iteration index run
+ *              (it0 - 1 if none), how phase 2 ended (0 ran out, 1 no progress, 2 gradient norm), phase 1's last iteration (-1 if the
+ *              call ran none), 0.  trace (2, max_iter) double, optional: the error and gn of every iteration that computed them, NaN
+ *              elsewhere (a warm call leaves the entries before it0 alone).  grad (N, 2) fp32, optional: the last iteration's g
+ *              before the gains.  ug (2, N, 2) fp32: update, then gains; prog (4) double: best_error, best_iter, phase, 0.  ug and
+ *              prog come both or neither; with warm 1 the call continues from it0 using y, ug and prog as found, and a warm
+ *              continuation is bit-identical to the uninterrupted call: after a call over [it0, m) with max_iter = m and a warm one
+ *              over [m, max_iter), y, ug and prog hold the bits that one call over [it0, max_iter) leaves.  (The call that ends at m
+ *              computes one more error, at its own last iteration; that changes kl and trace there, and no state.)
+ *   range      max_iter in [0, 32768]; with it0 = max_iter the call returns the init and P only.
+ *   not finite inputs are NOT checked.  The result is then unspecified but complete; never a hang.
+ *   bits       no float atomics, fixed-order reductions: the same arguments and option give the same bits.
+ *   workspace  8 N^2 bytes for P unless p_out or p_in is given; with x 4 N^2 bytes for D and 16 N bytes of vectors; 48 N parts bytes of
+ *              row partials (five doubles of the pair walk and one of the error walk per row and column part; parts is at most
+ *              max(1, floor(1024 / ceil(N / rb)), ceil(N / 4096)), rb = 4 rows up to N = 4096, then 16); 16 N bytes of state
+ *              unless ug is given; + 256-byte rounding, reserved once per call.  The conditionals are symmetrised
+ *              in place, one thread owning the pair (i, j), (j, i).
+ * Errors (text through avae_last_error; checked on the host, before any launch): a null tc, y, kl or stat; neither x nor p_in; N
+ * outside [2, 2^14]; with x: dim not a multiple of 4 in [4, 1024], x not 16-byte aligned, perplexity outside (0, N); y or ug not
+ * 8-byte aligned; max_iter outside [0, 32768]; it0 outside [0, max_iter]; exaggeration_iter < 0; n_iter_check < 1;
+ * n_iter_without_progress < 0; early_exaggeration < 1; a NaN learning_rate; init outside 0 .. 1; only one of ug and prog; warm
+ * without them; reserved != 0; a workspace the device cannot give (the text names its size).
+ * Option tsne_chunk (avae_set_option; a test aid): caps the columns of a part, so that small tests run several parts that are no
+ * tile multiples; 0 lets the planner decide.  A cap above 4096 or one that would give more than 256 parts is adjusted.  Another
+ * tsne_chunk sums in another order.                                                                                              */
+typedef struct avae_tsne_config {
+    double  perplexity;               /* (0, N); sklearn's default 30, the reference's 40 */
+    double  early_exaggeration;       /* >= 1; 12 */
+    double  min_grad_norm;            /* 1e-7 */
+    float   learning_rate;            /* > 0: used as it is; otherwise max(N / early_exaggeration / 4, 50) */
+    int32_t max_iter;                 /* [0, 32768]; 1000 */
+    int32_t it0;                      /* first iteration index, [0, max_iter] */
+    int32_t exaggeration_iter;        /* 250 */
+    int32_t n_iter_check;             /* >= 1; 50 */
+    int32_t n_iter_without_progress;  /* 300 */
+    int32_t init;                     /* 0: y holds the start; 1: random from `seed` */
+    int32_t warm;                     /* 1: continue from it0 with y, ug and prog as found */
+    uint64_t seed;
+    int32_t reserved[2];
+} avae_tsne_config;
+int  avae_tsne(avae_handle h, const float* x /* (N, dim) device, or null with p_in */, int32_t N, int32_t dim,
+               const avae_tsne_config* tc, const double* p_in /* (N, N), optional */,
+               float* y /* (N, 2) */, double* kl /* (2) */, int32_t* stat /* (4) */,
+               double* p_out /* (N, N), optional */, double* beta_out /* (N), optional */, double* trace /* (2, max_iter), optional */,
+               float* grad /* (N, 2), optional */, float* ug /* (2, N, 2) */, double* prog /* (4), both or neither */);
+
 #ifdef __cplusplus
 }
 #endif
