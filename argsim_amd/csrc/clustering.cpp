@@ -1,5 +1,6 @@
 // clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
-// (kernels: ward.hip), of avae_affinity (kernels: affinity.hip) and of avae_tsne (kernels: tsne.hip, the distances affinity.hip's).
+// (kernels: ward.hip), of avae_affinity (kernels: affinity.hip), of avae_tsne (kernels: tsne.hip, the distances affinity.hip's) and of
+// avae_kmeans (kernels: kmeans.hip).
 // Contract: include/argsim_vae.h.
 #include "ctx.h"
 
@@ -207,6 +208,67 @@ int avae_tsne(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_
     // every iteration is enqueued; a launch that finds the stop decided returns at once.  Never a synchronisation
     for (int it = tc->it0; it < tc->max_iter; ++it) AV_CHECK(tsne_iteration(h->stream, a, it));
     AV_CHECK(tsne_finish(h->stream, a, kl, stat, prog));
+    return 0;
+}
+
+int avae_kmeans(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_kmeans_config* kc, const float* centers_in, int32_t* label,
+                float* centers, int32_t* stat, double* inertia, int32_t* label_all, double* centers_all, int32_t* stat_all)
+{
+    if (!h) return 1;
+    if (!kc) return fail(h, "kmeans config is null");
+    if (!x || !label || !centers || !stat || !inertia) return fail(h, "kmeans: x, label, centers, stat and inertia must be given");
+    if (N < 1 || N > kKmMaxN) return fail(h, "kmeans: N must be in [1, 2^22]");
+    AV_TRY(check_rows(h, "kmeans", dim, "x and centers_in", {x, centers_in}));
+    if (kc->k < 1 || kc->k > std::min(N, kKmMaxK)) return fail(h, "kmeans: k must be in [1, min(N, 4096)]");
+    if (kc->n_init < 1 || kc->n_init > kKmMaxInit) return fail(h, "kmeans: n_init must be in [1, 64]");
+    if (kc->max_iter < 1 || kc->max_iter > 10000) return fail(h, "kmeans: max_iter must be in [1, 10000]");
+    if (kc->metric < 0 || kc->metric > 1) return fail(h, "kmeans: metric must be 0 (euclidean) or 1 (cosine)");
+    if (kc->init < 0 || kc->init > 1) return fail(h, "kmeans: init must be 0 (k-means++) or 1 (centers_in)");
+    if (kc->init == 1 && !centers_in) return fail(h, "kmeans: init 1 reads centers_in, which is not given");
+    if (!(kc->tol >= 0.0)) return fail(h, "kmeans: tol must be >= 0");
+    if (kc->reserved != 0) return fail(h, "kmeans: the reserved field must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    // Workspace, every buffer on a 256-byte boundary, R = n_init: the state (R), the centres (R, k, dim) double, the parts'
+    // minima (R, parts, N) double + int, labels and sorted rows (R, N) int each, distances (R, N) double, histograms and offsets
+    // (R, blocks, k) int each, first positions (R, k + 1), member-sum partials (R, slices + k, dim) double, relocations (R, k, 3),
+    // shift (R, k) and inertia (R, tiles) partials, the variance's (256 + 1, dim), with the cosine the row norms (N); with init 0 the
+    // closest distances (R, N), candidate distances (R, T, N), candidate rows (R, T, dim) and (R, T), scan-tile sums (R, scans) and
+    // potential partials (R, T, scans)
+    const size_t n = (size_t)N, R = (size_t)kc->n_init, k = (size_t)kc->k, d = (size_t)dim;
+    KmArgs a{};
+    a.x = x; a.N = N; a.dim = dim; a.k = kc->k; a.R = kc->n_init; a.max_iter = kc->max_iter; a.seed = kc->seed;
+    a.T = std::min(kKmMaxTrials, 2 + (int)std::floor(std::log((double)kc->k)));
+    a.p = km_plan(N, kc->k, kc->n_init, h->kmeans_chunk);
+    const KmPlan& p = a.p;
+    double* rnorm = nullptr;
+    AV_TRY(place_ws(h, "kmeans", [&](Bump& b) {
+        a.st = b.take<KmState>(R);
+        a.best = b.take<int>(1);
+        a.C = b.take<double>(R * k * d);
+        a.pd = b.take<double>(R * p.parts * n); a.pi = b.take<int>(R * p.parts * n);
+        a.lab = b.take<int>(R * n); a.order = b.take<int>(R * n); a.dist = b.take<double>(R * n);
+        a.hist = b.take<int>(R * p.blks * k); a.off = b.take<int>(R * p.blks * k);
+        a.start = b.take<int>(R * (k + 1));
+        a.psum = b.take<double>(R * ((size_t)p.slices + k) * d);
+        a.rel = b.take<int>(R * k * 3);
+        a.shiftp = b.take<double>(R * k); a.ipart = b.take<double>(R * p.tiles);
+        a.vpart = b.take<double>((size_t)kKmMaxBlocks * d); a.mean = b.take<double>(d);
+        rnorm = b.opt<double>(kc->metric == 1, n);
+        if (kc->init == 0) {
+            a.closest = b.take<double>(R * n); a.D = b.take<double>(R * a.T * n); a.candC = b.take<double>(R * a.T * d);
+            a.cand = b.take<int>(R * a.T); a.tsum = b.take<double>(R * p.scans); a.ppart = b.take<double>(R * a.T * p.scans);
+        }
+    }));
+    a.rnorm = rnorm;
+    AV_CHECK(hipMemsetAsync(a.st, 0, R * sizeof(KmState), h->stream));
+    AV_CHECK(hipMemsetAsync(a.lab, 0xff, R * n * sizeof(int), h->stream));
+    AV_CHECK(hipMemsetAsync(a.hist, 0, R * p.blks * k * sizeof(int), h->stream));
+    AV_CHECK(km_prepare(h->stream, a, kc->tol));
+    if (kc->init == 1) AV_CHECK(km_load(h->stream, a, centers_in));
+    else AV_CHECK(km_seed(h->stream, a));
+    // every iteration is enqueued; a launch that finds the restart's stop decided returns at once.  Never a synchronisation
+    for (int it = 0; it < kc->max_iter; ++it) AV_CHECK(km_iteration(h->stream, a, it));
+    AV_CHECK(km_finish(h->stream, a, label, centers, stat, inertia, label_all, centers_all, stat_all));
     return 0;
 }
 

@@ -493,6 +493,53 @@ hipError_t tsne_init(hipStream_t st, const TsneArgs& a, int it0, int warm, int i
 hipError_t tsne_iteration(hipStream_t st, const TsneArgs& a, int it);      // two launches, three where the error may be computed
 hipError_t tsne_finish(hipStream_t st, const TsneArgs& a, double* kl, int32_t* stat, double* prog);
 
+// ---------------------------------------------------------------- k-means of latent rows (kmeans.hip)
+// One set of N rows and R = n_init restarts side by side per call (contract: include/argsim_vae.h, avae_kmeans).  Every buffer is
+// workspace laid out by the caller (clustering.cpp); the state, the labels (-1) and the block histograms (0) are filled before the
+// first launch.
+constexpr int kKmMaxN = 1 << 22;
+constexpr int kKmMaxK = 4096, kKmMaxInit = 64, kKmMaxParts = 16, kKmMaxBlocks = 256, kKmMaxTrials = 10;      // trials: 2 + floor(ln 4096)
+constexpr int kKmTile = 64;           // rows of a tile of the distance kernel
+constexpr int kKmScanRows = 1024;     // rows of a tile of the seeding's cumulative sum
+struct KmState {
+    int stop_at;                      // 0: running; it + 1: iteration it ended the restart (a launch of a later iteration returns at once)
+    int how, reloc;                   // 0 converged, 1 tol, 2 max_iter; relocations so far
+    int changed, nempty;              // this iteration: a label differs from the previous iteration's; empty clusters
+    int chosen;                       // seeding: the candidate picked in this round
+    int pad[2];
+    double tol_abs, total;            // the absolute tolerance; seeding: the sum of the closest distances
+};
+// tile x parts: the distance kernel's grid; slice: sorted positions per workgroup of the member sums; blk: rows per block of the stable
+// counting sort; scan: rows per tile of the seeding's cumulative sum
+struct KmPlan { int tile, tiles, parts, chunk, slice, slices, blk, blks, scan, scans; };
+struct KmArgs {
+    const float* x; const double* rnorm;      // rows; their norms (cosine) or null
+    int N, dim, k, R, max_iter, T;    // T: seeding trials per centre
+    uint64_t seed;
+    KmPlan p;
+    KmState* st;                      // (R)
+    double* C;                        // (R, k, dim) the centres, updated in place
+    double* pd; int* pi;              // (R, parts, N) a part's first minimum per row
+    int* lab; double* dist;           // (R, N) labels; distance to the own centre as assigned
+    int *hist, *off;                  // (R, blks, k) members per row block; their first position inside the cluster's run
+    int* start;                       // (R, k + 1) first sorted position of a cluster
+    int* order;                       // (R, N) rows by (label, row)
+    double* psum;                     // (R, slices + k, dim) member sums of (slice, cluster) at slice + cluster
+    int* rel;                         // (R, k, 3) relocations: row or -1, its cluster, the empty cluster
+    double *shiftp, *ipart;           // (R, k) squared shift per centre; (R, tiles) inertia partials
+    double *vpart, *mean;             // (kKmMaxBlocks, dim), (dim): the column variance
+    int* best;                        // (1) the best restart
+    double *closest, *D, *candC, *tsum, *ppart;      // seeding: (R, N); (R, T, N); (R, T, dim); (R, scans); (R, T, scans)
+    int* cand;                        // (R, T) candidate rows
+};
+KmPlan km_plan(int N, int k, int R, int chunk_opt);
+hipError_t km_prepare(hipStream_t st, const KmArgs& a, double tol);      // row norms (cosine), the absolute tolerance
+hipError_t km_load(hipStream_t st, const KmArgs& a, const float* centers_in);      // the given start as doubles into C
+hipError_t km_seed(hipStream_t st, const KmArgs& a);                     // greedy k-means++ into C: five launches per centre
+hipError_t km_iteration(hipStream_t st, const KmArgs& a, int it);        // seven launches
+hipError_t km_finish(hipStream_t st, const KmArgs& a, int32_t* label, float* centers, int32_t* stat, double* inertia, int32_t* label_all,
+                     double* centers_all, int32_t* stat_all);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

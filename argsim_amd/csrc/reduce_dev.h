@@ -58,4 +58,32 @@ struct ArgFirst {
     }
 };
 
+// the FIRST minimum in double as (value, index): ArgFirst's sibling for distances (kmeans.hip).  The neutral element loses against
+// every number; a NaN never enters.
+struct ArgMinFirst {
+    double v = INFINITY; int i = 0x7fffffff;
+    // a thread's own scan in ascending index order: strict <, so the first minimum stays
+    __device__ __forceinline__ void take(double x, int idx) { if (x < v) { v = x; i = idx; } }
+    // any two records: smaller value, then smaller index (order-free for non-NaN values)
+    __device__ __forceinline__ void merge(const ArgMinFirst& o) { if (o.v < v || (o.v == v && o.i < i)) *this = o; }
+    // butterfly over aligned groups of W lanes, in every lane
+    template <int W = 64>
+    __device__ __forceinline__ void wave_merge()
+    {
+#pragma unroll
+        for (int o = W / 2; o > 0; o >>= 1) merge(ArgMinFirst{__shfl_xor(v, o, 64), __shfl_xor(i, o, 64)});
+    }
+    // over the NW waves of the workgroup, after wave_merge(): as ArgFirst::block_merge, every thread gets the result, and a barrier
+    // follows the sweep (the caller may call it again at once)
+    template <int NW>
+    __device__ __forceinline__ void block_merge(double* sv, int* si)
+    {
+        if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = i; }
+        __syncthreads();
+        v = sv[0]; i = si[0];
+        for (int w = 1; w < NW; ++w) merge(ArgMinFirst{sv[w], si[w]});
+        __syncthreads();
+    }
+};
+
 }  // namespace avae

@@ -6,13 +6,16 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
 
     python -m argsim_amd.eval_explore --inputs data/test_data_emb.npy --labels data/test_labels.npy \\
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
-        [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]]
+        [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]] [--kmeans K [--kmeans-init 10]]
 
 With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
 device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
 
 The labels are eval_cluster's topic-stance-reason strings; the topics are listed in order of first appearance.  A purity line is the
-topic, then share|members|cluster for the clusters of which at least half the members (and at least two) belong to the topic."""
+topic, then share|members|cluster for the clusters of which at least half the members (and at least two) belong to the topic.
+
+With --kmeans K the same runs follow with k-means into K clusters (VAE.kmeans: k-means++ seeding, the best of --kmeans-init restarts, ONE
+device call each), the same lines per run and the columns cls_km_* / dist_km_* in the CSV.  Without it nothing changes."""
 import argparse
 import csv
 
@@ -21,6 +24,7 @@ import numpy as np
 RUNS = (('euc', 'euclidean', 'sqeuclidean', False), ('euc_sp', 'euclidean', 'sqeuclidean', True), ('cos', 'cosine', 'cosine', False),
         ('cos_sp', 'cosine', 'cosine', True))
 COLUMNS = "post topic labels cls_euc dist_euc cls_euc_sp dist_euc_sp cls_cos dist_cos cls_cos_sp dist_cos_sp".split()
+KM_COLUMNS = "cls_km_euc dist_km_euc cls_km_euc_sp dist_km_euc_sp cls_km_cos dist_km_cos cls_km_cos_sp dist_km_cos_sp".split()      # with --kmeans
 
 
 def purity_lines(pred, topics, order):
@@ -33,8 +37,9 @@ def purity_lines(pred, topics, order):
     return lines + ["%d clusters" % len(set(np.asarray(pred).tolist()))]
 
 
-def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200):
-    """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed"""
+def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10):
+    """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed.  kmeans = k adds the
+    same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*"""
     from . import affinity
     from .eval_cluster import split_labels
     topics = np.array([p[0] for p in split_labels(labels)])
@@ -50,6 +55,16 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200):
         lines += purity_lines(res['labels'], topics, order)
         cols['cls_' + name] = res['labels']
         cols['dist_' + name] = affinity.dist_to_centroids(x, res['labels'], dist)
+    for name, metric, dist, sampled in RUNS if kmeans else ():
+        x = z_sp if sampled else z
+        if x is None:
+            continue
+        res = vae.kmeans(x, kmeans, metric, n_init=kmeans_init, seed=seed)
+        if res['stop'] == 'max_iter':
+            lines.append("km_%s: stopped after %d iterations" % (name, res['n_iter']))
+        lines += purity_lines(res['labels'], topics, order)
+        cols['cls_km_' + name] = res['labels']
+        cols['dist_km_' + name] = affinity.dist_to_centroids(x, res['labels'], dist)
     return cols, lines
 
 
@@ -66,13 +81,20 @@ def embed(vae, z, labels, out, plot=None, perplexity=40.0, max_iter=20000, seed=
 
 def write_csv(path, posts, topics, labels, cols):
     """eval_clustering_explorative.py:121-132: the id, then the columns in the reference's order (those of absent runs left out)"""
-    names = [c for c in COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
+    names = [c for c in COLUMNS + KM_COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
     data = dict(cols, post=posts, topic=topics, labels=labels)
     with open(path, 'w', newline='') as f:
         w = csv.writer(f)
         w.writerow(['id'] + names)
         for i in range(len(labels)):
             w.writerow([i] + [data[c][i] for c in names])
+
+
+def _positive(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be >= 1, got %r" % (text,))
+    return v
 
 
 def build_parser():
@@ -87,6 +109,8 @@ def build_parser():
     ap.add_argument('--tsne-plot', default=None, help="with --tsne: the scatter by topic as an image (needs matplotlib)")
     ap.add_argument('--perplexity', type=float, default=40.0)
     ap.add_argument('--tsne-iter', type=int, default=20000)
+    ap.add_argument('--kmeans', type=_positive, default=None, help="also cluster with k-means into this many clusters (VAE.kmeans)")
+    ap.add_argument('--kmeans-init', type=_positive, default=10, help="with --kmeans: restarts, the best of which is listed")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -105,7 +129,7 @@ def main(argv=None):
     vae = make_vae(A.device)
     if A.tsne:
         print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
-    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter)
+    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init)
     for line in lines:
         print(line)
     if A.csv:

@@ -86,6 +86,11 @@ class AvaeTsneConfig(C.Structure):
                 ('reserved', C.c_int32 * 2)]
 
 
+class AvaeKmeansConfig(C.Structure):
+    _fields_ = [('k', C.c_int32), ('n_init', C.c_int32), ('max_iter', C.c_int32), ('metric', C.c_int32), ('init', C.c_int32),
+                ('reserved', C.c_int32), ('tol', C.c_double), ('seed', C.c_uint64)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -129,6 +134,7 @@ SIGNATURES = {
     'avae_ward_cut': (C.c_int, [_P, _P, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), _P]),
     'avae_affinity': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeAffinityConfig), _P, _P, _P, _P, _P]),
     'avae_tsne': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeTsneConfig)] + [_P] * 10),
+    'avae_kmeans': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeKmeansConfig)] + [_P] * 8),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),

@@ -19,6 +19,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) L1 probes: the useful dimensions (liblinear) -> VAE.probe_fit_l1(z, labels) / VAE.select_dims(z, labels)
     (new) Ward clustering of latent rows (ARS, V_MSR)  -> VAE.ward(z, groups) / VAE.ward_cut(res, k) / VAE.cluster_eval(z, gold, groups)
     (new) affinity propagation of latent rows          -> VAE.affinity(z, metric, ...) / affinity(vae, z, ...)
+    (new) k-means of latent rows                       -> VAE.kmeans(z, k, metric, ...) / kmeans(vae, z, k, ...)
     (new) exact t-SNE of latent rows                   -> VAE.tsne(z, perplexity, ...) / tsne(vae, z, ...)
 """
 import ctypes as C
@@ -654,6 +655,14 @@ class VAE:
         return tsne.tsne(self, z, perplexity, max_iter, init, seed, learning_rate, early_exaggeration, exaggeration_iter, n_iter_check,
                          n_iter_without_progress, min_grad_norm, p, return_p, return_trace)
 
+    def kmeans(self, z, k, metric='euclidean', n_init=10, max_iter=300, tol=1e-4, seed=0, init='k-means++', return_all=False):
+        """k-means of the rows of z (sklearn's KMeans(algorithm='lloyd'): greedy k-means++ seeding, Lloyd iterations, the relocation of
+        empty clusters) with n_init restarts side by side in ONE device call (include/argsim_vae.h, avae_kmeans).  metric: 'euclidean' or
+        'cosine' (spherical k-means); init: 'k-means++' or the centres, (k, dim) or (n_init, k, dim)
+        -> dict(labels, centers, inertia, n_iter, stop, best, inertias, relocations) (argsim_amd/kmeans.py)"""
+        from . import kmeans
+        return kmeans.kmeans(self, z, k, metric, n_init, max_iter, tol, seed, init, return_all)
+
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}
 
@@ -883,3 +892,14 @@ def tsne(vae, z, perplexity=30.0, max_iter=1000, init='pca', seed=0, learning_ra
     """functional form of VAE.tsne"""
     return vae.tsne(z, perplexity, max_iter, init, seed, learning_rate, early_exaggeration, exaggeration_iter, n_iter_check,
                     n_iter_without_progress, min_grad_norm, p, return_p, return_trace)
+
+
+def _check_kmeans_args(z, k, metric='euclidean', n_init=10, max_iter=300, tol=1e-4, seed=0, init='k-means++'):
+    """the argument rules of VAE.kmeans, checked before anything touches the device (ValueError)"""
+    from . import kmeans as _km
+    return _km._check_kmeans_args(z, k, metric, n_init, max_iter, tol, seed, init)
+
+
+def kmeans(vae, z, k, metric='euclidean', n_init=10, max_iter=300, tol=1e-4, seed=0, init='k-means++', return_all=False):
+    """functional form of VAE.kmeans"""
+    return vae.kmeans(z, k, metric, n_init, max_iter, tol, seed, init, return_all)

@@ -635,6 +635,63 @@ int  avae_tsne(avae_handle h, const float* x /* (N, dim) device, or null with p_
                double* p_out /* (N, N), optional */, double* beta_out /* (N), optional */, double* trace /* (2, max_iter), optional */,
                float* grad /* (N, 2), optional */, float* ug /* (2, N, 2) */, double* prog /* (4), both or neither */);
 
+/* ---- k-means of latent rows ----------------------------------------------------------------------------------------------------
+ * scikit-learn's KMeans(algorithm='lloyd') of N rows into k clusters, n_init restarts side by side, in ONE call: everything is enqueued
+ * on the handle's stream without a synchronisation; each restart decides its stop on the device and a launch that finds the stop
+ * decided returns at once.  Every pointer is device memory.  All arithmetic that a decision or an output depends on is double; the rows
+ * are fp32.  (The float64 restatement of this contract is tests/kmeans_ref.py.)
+ *   tolerance  tol_abs = tol x the mean over the dim columns of the population variance of the rows.
+ *   iteration  from centres c: (1) label_i = argmin_c sum_j (x_ij - c_cj)^2, the FIRST minimum; (2) counts and sums of the member rows;
+ *              (3) the empty clusters in ascending order: the e-th takes the row with the e-th largest distance to its own centre (ties:
+ *              the smaller row), which leaves its old cluster's sum and count -- a relocation; (4) new centres = sums / counts;
+ *              (5) shift = sum |c_new - c|^2; (6) stop "converged" (0) if the labels equal the previous iteration's; (7) else stop
+ *              "tol" (1) if shift <= tol_abs; (8) else go on, to max_iter (2).  After a stop that was not "converged" the labels are
+ *              assigned once more against the final centres.  inertia = sum_i |x_i - c_label_i|^2 over the final labels and centres.
+ *              Iterations count from 1.  The best restart is the first one with the smallest inertia.
+ *   cosine     metric 1 is the same algorithm on the rows divided by their norms (a zero row stays zero); every new centre is divided
+ *              by its norm (a zero centre stays zero): spherical k-means, inertia = sum 2 (1 - cos).
+ *   seeding    init 0 is sklearn's greedy k-means++ with this library's generator: u = uniform01(seed, stream 7, ((r 2^20) + c) 2^20 + t)
+ *              for restart r, centre c, trial t.  Centre 0 is row floor(u N).  Every further centre draws T = 2 + floor(ln k) candidates:
+ *              a candidate is the first row whose inclusive cumulative sum of the current closest squared distances, in ascending row
+ *              order, reaches u x the total, clipped to N - 1; chosen is the candidate with the smallest new potential
+ *              sum_i min(closest_i, d(i, candidate)), the first of equals.  Restart r does not depend on n_init.  init 1 reads the start
+ *              of every restart from centers_in (for the cosine they are taken as given).
+ *   outputs    label (N) and centers (k, dim; the double values rounded once) of the best restart; stat (4) = best restart, its
+ *              iterations, how it stopped, its relocations; inertia (n_init).  Optional: label_all (n_init, N), centers_all (n_init, k,
+ *              dim) double, stat_all (n_init, 4) = iterations, stop, relocations, 0.
+ *   range      1 <= N <= 2^22; 1 <= k <= min(N, 4096); dim a multiple of 4 in [4, 1024]; x and centers_in 16-byte aligned.
+ *   not finite inputs are NOT checked.  The result is then unspecified but complete; never a hang.  A row without a nearest centre
+ *              takes cluster 0.
+ *   bits       no float atomics; every sum has an order fixed by the shape: the same arguments and option give the
+ *              same bits in every output.
+ *   cost       an iteration is seven launches whether or not a restart has stopped; relocation sweeps the rows once per empty cluster
+ *              in one workgroup per restart.
+ *   workspace  per restart 28 N bytes of labels, distances, sorted rows and part minima (+ 12 N per further centre part, at most 16
+ *              parts, only where there are few row tiles), 8 k dim of centres, 8 (slices + k) dim of member-sum partials (slices =
+ *              ceil(N / 256), from 2^16 rows ceil(N / 1024)), 8 blocks k of histograms (blocks <= 256); with init 0 another
+ *              8 N (1 + T) + 8 T dim; + 256-byte rounding, reserved once per call.
+ * Errors (text through avae_last_error; checked on the host, before any launch): a null kc, x, label, centers, stat or inertia; N or dim
+ * out of range; x or centers_in not 16-byte aligned; k outside [1, min(N, 4096)]; n_init outside [1, 64]; max_iter outside [1, 10000];
+ * metric or init outside 0 .. 1; init 1 without centers_in; tol negative or NaN; reserved != 0; a workspace the device cannot give (the
+ * text names its size).
+ * Option kmeans_chunk (avae_set_option; a test aid): caps the centres of a part and the rows of a tile, a slice and a sort block, so that
+ * small tests run several parts and their merges; 0 lets the planner decide.  Another kmeans_chunk sums in another order.            */
+typedef struct avae_kmeans_config {
+    int32_t k;          /* clusters, 1 <= k <= min(N, 4096) */
+    int32_t n_init;     /* restarts run side by side in the one call, 1 .. 64 */
+    int32_t max_iter;   /* Lloyd iterations per restart, 1 .. 10000 (sklearn: 300) */
+    int32_t metric;     /* 0 euclidean; 1 cosine = spherical k-means */
+    int32_t init;       /* 0: greedy k-means++ from `seed`; 1: the centres in `centers_in` */
+    int32_t reserved;   /* 0 */
+    double  tol;        /* >= 0, relative as sklearn's (1e-4): scaled by the mean column variance */
+    uint64_t seed;
+} avae_kmeans_config;
+int  avae_kmeans(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_kmeans_config* kc,
+                 const float* centers_in /* (n_init, k, dim) device, init = 1 only */,
+                 int32_t* label /* (N) */, float* centers /* (k, dim) */, int32_t* stat /* (4) */, double* inertia /* (n_init) */,
+                 int32_t* label_all /* optional (n_init, N) */, double* centers_all /* optional (n_init, k, dim) */,
+                 int32_t* stat_all /* optional (n_init, 4) */);
+
 #ifdef __cplusplus
 }
 #endif
