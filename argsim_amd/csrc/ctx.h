@@ -343,6 +343,8 @@ template <class F> int place_ws(avae_ctx* h, const char* what, F lay, size_t fro
     return 0;
 }
 
+// ---- generate.cpp: which loop a decoding call runs (0 one launch, 1 per token by option or batch, 2 per token: geometry refused)
+int decode_route(bool persistent, int b, bool sampled, int top_k, bool nucleus, int D, int V, int L, int G, int lds_max, DecodePlan* plan);
 // ---- generate.cpp: avae_sample_config / avae_sample_p_config -> what the kernels take
 bool sample_params(avae_ctx* h, const avae_sample_config* sc, int V, SampleParams* sp);
 bool sample_params_p(avae_ctx* h, const avae_sample_p_config* sc, int V, SampleParams* sp, float* top_p);

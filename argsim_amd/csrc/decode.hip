@@ -451,32 +451,62 @@ __global__ __launch_bounds__(kDecThreads) void decode_kernel(DecodeArgs a)
     if (w == 0 && tid == 0) *a.kept = kept;
 }
 
-int decode_workgroups()
+// what the current device offers the launch: one workgroup per CU, and the LDS one workgroup may own
+hipError_t decode_device(int* G, int* lds_max)
 {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    return cus;
+    int dev = 0, cus = 0, lds = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    if (e != hipSuccess) return e;
+    if (lds < 160 * 1024) lds = 160 * 1024;                    // gfx950: one workgroup may own the CU's whole LDS
+    *G = cus; *lds_max = lds;
+    return hipSuccess;
+}
+
+// the kMode a call runs in: 0 greedy, else decode_sample's routing -- 3 with the nucleus, 1 where top-k keeps everything
+// (top_k 0 or >= V), else 2; -1 where the row's owner cannot hold the row (top-k or the nucleus with V > kSelMax * kDecThreads)
+int decode_mode(bool sampled, int V, int top_k, bool nucleus)
+{
+    if (!sampled) return 0;
+    if (nucleus) return V > kSelMax * kDecThreads ? -1 : 3;
+    if (top_k == 0 || top_k >= V) return 1;
+    return V > kSelMax * kDecThreads ? -1 : 2;
+}
+
+// the geometry of one launch (the LDS map is the kernel's): host arithmetic only, and the ONLY place that decides it --
+// decode_launch launches what this returns, avae_debug_decode_plan reports it.  The budget: 4 bytes x (L x nu x 6 x D gate rows +
+// nu x D columns of the out affine), 64 bytes to spare, and the select scratch of kMode 2 / 3 (kSelWords / kSelWordsP words: 2048 /
+// 3584 bytes); the workgroup's vp x D embedding rows join them (cache_e) where 1 KB of the LDS stays free with them.  Refused:
+// more than 2 units per workgroup, L > 8, D > 512 or no multiple of 4, or the sum without the embedding rows above lds_max
+DecodePlan decode_plan(int mode, int D, int V, int L, int G, int lds_max)
+{
+    DecodePlan p{0, mode, 0, 0, 0, 0, G, lds_max};
+    if (mode < 0 || mode > 3 || G < 1) return p;
+    const int nu = (D + G - 1) / G, vp = (V + G - 1) / G;
+    p.nu = nu; p.vp = vp;
+    if (nu > 2 || L > 8 || (D & 3) || D > 512) return p;
+    size_t floats = (size_t)L * nu * 6 * D + (size_t)nu * D;
+    const size_t with_e = floats + (size_t)vp * D;
+    const size_t extra = mode == 2 ? kSelWords * 4 : mode == 3 ? kSelWordsP * 4 : 0;
+    p.cache_e = with_e * 4 + 64 + extra <= (size_t)lds_max - 1024 ? 1 : 0;
+    if (p.cache_e) floats = with_e;
+    const size_t bytes = floats * 4 + 64 + extra;
+    p.lds_bytes = (int)bytes;
+    p.ok = bytes <= (size_t)lds_max;            // (the weights alone may exceed the LDS)
+    return p;
 }
 
 template <int kMode>
 static hipError_t decode_launch(hipStream_t st, DecodeArgs a, int* grid_out)
 {
-    int dev = 0, cus = 0, lds_max = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    int G = 0, lds_max = 0;
+    hipError_t e = decode_device(&G, &lds_max);
     if (e != hipSuccess) return e;
-    if (lds_max < 160 * 1024) lds_max = 160 * 1024;            // gfx950: one workgroup may own the CU's whole LDS
-    const int G = cus;
-    const int nu = (a.D + G - 1) / G, vp = (a.V + G - 1) / G;
-    if (nu > 2 || a.L > 8 || (a.D & 3) || a.D > 512) return hipErrorInvalidValue;
-    size_t floats = (size_t)a.L * nu * 6 * a.D + (size_t)nu * a.D;
-    const size_t with_e = floats + (size_t)vp * a.D;
-    const size_t extra = kMode == 2 ? kSelWords * 4 : kMode == 3 ? kSelWordsP * 4 : 0;
-    a.cache_e = with_e * 4 + 64 + extra <= (size_t)lds_max - 1024 ? 1 : 0;
-    if (a.cache_e) floats = with_e;
-    const int lds_bytes = (int)(floats * 4 + 64 + extra);
-    if ((size_t)lds_bytes > (size_t)lds_max) return hipErrorInvalidValue;
+    const DecodePlan p = decode_plan(kMode, a.D, a.V, a.L, G, lds_max);
+    if (!p.ok) return hipErrorInvalidValue;
+    a.cache_e = p.cache_e;
+    const int lds_bytes = p.lds_bytes;
     static int attr_set = 0;
     if (attr_set < lds_bytes) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel<kMode>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
@@ -497,14 +527,13 @@ hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out) { return d
 hipError_t decode_sample(hipStream_t st, DecodeArgs a, int* grid_out)
 {
     if (a.V > (1 << 20) || a.steps > (1 << 20) || a.sp.top_k < 0) return hipErrorInvalidValue;
-    if (a.top_p > 0.f) {                // the nucleus is on (the caller routes top_p 0 or >= 1 and the noiseless forms here with top_p 0)
-        if (!(a.top_p < 1.f) || !a.sp.noise || a.V > kSelMax * kDecThreads || !a.logits) return hipErrorInvalidValue;
-        if (a.sp.top_k >= a.V) a.sp.top_k = 0;
-        return decode_launch<3>(st, a, grid_out);
-    }
-    if (a.sp.top_k == 0 || a.sp.top_k >= a.V) { a.sp.top_k = 0; return decode_launch<1>(st, a, grid_out); }
-    if (a.V > kSelMax * kDecThreads || !a.logits) return hipErrorInvalidValue;
-    return decode_launch<2>(st, a, grid_out);
+    const bool nucleus = a.top_p > 0.f;         // (the caller routes top_p 0 or >= 1 and the noiseless forms here with top_p 0)
+    if (nucleus && (!(a.top_p < 1.f) || !a.sp.noise)) return hipErrorInvalidValue;
+    const int mode = decode_mode(true, a.V, a.sp.top_k, nucleus);
+    if (mode < 0 || (mode >= 2 && !a.logits)) return hipErrorInvalidValue;
+    if (mode == 1 || a.sp.top_k >= a.V) a.sp.top_k = 0;
+    if (mode == 3) return decode_launch<3>(st, a, grid_out);
+    return mode == 1 ? decode_launch<1>(st, a, grid_out) : decode_launch<2>(st, a, grid_out);
 }
 
 }  // namespace avae

@@ -175,6 +175,31 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
     return check_gru_err(h);
 }
 
+}  // extern "C"
+
+// Which loop a decoding call of b rows runs (decode_loop below goes by this and by nothing else; avae_debug_decode_plan reports it):
+// 0 the one persistent launch of *plan, 1 one launch sequence per token by option "persistent" 0 or by batch, 2 the same because
+// decode_plan refuses the geometry; -1: no HIP device to ask.  G or lds_max 0: the current device's (asked only where the answer
+// depends on them).  top_k as SampleParams holds it, nucleus: top_p > 0.
+// Measured at D = 512, V = 8192, steps = 512 (scripts/decode_bench.py, profiles/r03_decode_bench.txt): the persistent launch
+// takes 42 / 74 / 145 us per token at b = 1 / 16 / 64, the launch-per-token loop 116-130 us at any b <= 128 (its
+// GEMMs are far from full): one launch up to 32 rows, the per-token loop above
+int avae::host::decode_route(bool persistent, int b, bool sampled, int top_k, bool nucleus, int D, int V, int L, int G, int lds_max, DecodePlan* plan)
+{
+    *plan = DecodePlan{0, decode_mode(sampled, V, top_k, nucleus), 0, 0, 0, 0, G, lds_max};
+    if (!persistent || b > 32) return 1;
+    if (G < 1 || lds_max < 1) {
+        int dg = 0, dl = 0;
+        if (decode_device(&dg, &dl) != hipSuccess || dg < 1) return -1;
+        if (G < 1) G = dg;
+        if (lds_max < 1) lds_max = dl;
+    }
+    *plan = decode_plan(plan->mode, D, V, L, G, lds_max);
+    return plan->ok ? 0 : 2;
+}
+
+extern "C" {
+
 // the greedy (sp null) or sampled loop: one persistent launch where it serves, else the launch-per-token loop.  top_p > 0: the
 // nucleus is on (0 < top_p < 1, sp->noise), nkept_out optional
 static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, const SampleParams* sp, int32_t* out_ids, float* logp_out, int32_t* n_steps,
@@ -184,14 +209,13 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     AV_TRY(check_bound(h));
     if (b < 1 || steps < 1) return fail(h, "empty batch");
     AV_CHECK(hipSetDevice(h->device));
-    // measured at D = 512, V = 8192, steps = 512 (scripts/decode_bench.py, profiles/r03_decode_bench.txt): the persistent launch
-    // takes 42 / 74 / 145 us per token at b = 1 / 16 / 64, the launch-per-token loop 116-130 us at any b <= 128 (its
-    // GEMMs are far from full): one launch up to 32 rows, the per-token loop above
-    if (!h->persistent || b > 32) return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps, top_p, nkept_out);
-    // the whole loop in ONE persistent launch (decode.hip); state, partial maxima and the id log live in the scratch buffer
     const int D = h->cfg.dim_emb, V = h->cfg.dim_tgt, L = h->cfg.rnn_layers;
-    const int G = decode_workgroups();
-    if (G < 1) return fail(h, "no HIP device");
+    DecodePlan plan;
+    const int route = decode_route(h->persistent != 0, b, sp != nullptr, sp ? sp->top_k : 0, top_p > 0.f, D, V, L, 0, 0, &plan);
+    if (route < 0) return fail(h, "no HIP device");
+    if (route != 0) return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps, top_p, nkept_out);      // same results, more launches
+    // the whole loop in ONE persistent launch (decode.hip); state, partial maxima and the id log live in the scratch buffer
+    const int G = plan.G;
     const bool topk = sp && (sp->top_k > 0 || top_p > 0.f);          // the owner of a row reads its logits from the scratch
     const bool want_nk = top_p > 0.f && nkept_out;
     DecodeArgs a{};
@@ -212,10 +236,6 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     AV_CHECK(hipMemsetAsync(a.bar, 0, sizeof(unsigned), h->stream));
     int grid = 0;
     hipError_t e = sp ? decode_sample(h->stream, a, &grid) : decode_greedy(h->stream, a, &grid);
-    if (e == hipErrorInvalidValue) {                       // geometry outside the persistent kernel: same results, more launches
-        AV_CHECK(hipStreamSynchronize(h->stream));           // (bos.data() is still being read)
-        return decode_stepwise(h, z, b, steps, sp, out_ids, logp_out, n_steps, top_p, nkept_out);
-    }
     if (e == hipErrorCooperativeLaunchTooLarge) return fail(h, "persistent decode kernel: one workgroup per CU does not fit this device");
     AV_CHECK(e);
     int kept = 0;

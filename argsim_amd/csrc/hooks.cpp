@@ -85,6 +85,23 @@ int avae_debug_gemm_f32_form(int a_mc, int b_nc, int M, int N, int K, int lda, i
     std::copy(v, v + 8, out);
     return 0;
 }
+// test hook: what a decoding call runs (decode_route and, through it, decode_mode / decode_plan: the functions decode_loop and the launchers
+// themselves decide with).  in = sampled (0: avae_decode_greedy), D, V, L, b, top_k, nucleus (top_p > 0), persistent (the option), G, lds_max -- G or
+// lds_max 0: the current device's; out = route (0 one launch, 1 per token by option or batch, 2 per token because the geometry is refused), kMode
+// (-1: top-k or nucleus beyond 8192 ids), ok, nu, vp, cache_e, lds_bytes, the G and lds_max planned for.  Host arithmetic only where G and lds_max
+// are given: callable without a GPU.
+int avae_debug_decode_plan(const int64_t in[10], int64_t out[9])
+{
+    if (!in || !out) return 1;
+    for (int i = 1; i < 5; ++i) if (in[i] < 1 || in[i] > INT32_MAX) return 1;
+    if (in[5] < 0 || in[5] > INT32_MAX || in[8] < 0 || in[8] > INT32_MAX || in[9] < 0 || in[9] > INT32_MAX) return 1;
+    DecodePlan p;
+    const int route = decode_route(in[7] != 0, (int)in[4], in[0] != 0, (int)in[5], in[6] != 0, (int)in[1], (int)in[2], (int)in[3], (int)in[8], (int)in[9], &p);
+    if (route < 0) return 1;
+    const int64_t v[9] = {route, p.mode, p.ok, p.nu, p.vp, p.cache_e, p.lds_bytes, p.G, p.lds_max};
+    std::copy(v, v + 9, out);
+    return 0;
+}
 // test hook: the decoder batches of the last avae_score / avae_score_z (score_plan): out = N, rc, kc, batches that ran the shared
 // first-layer projection of the non-table path (lead_rows + GruJob::gi_rows)
 int avae_debug_score_plan(avae_handle h, int32_t out[4])

@@ -566,12 +566,21 @@ struct DecodeArgs {
     int32_t* nkept_tm;                              // (steps, b) time-major sizes of the kept sets, or null
     int32_t* nkept_out;                             // (b, steps) result, 0 where the row had finished, or null
 };
-// returns hipErrorInvalidValue where the geometry does not fit (D / CUs > 2 units per workgroup, LDS), the caller
-// then falls back to one launch sequence per token; *grid_out = workgroups launched
+// The geometry of one launch of kMode `mode` over G workgroups with lds_max bytes of LDS each: nu = hidden units and vp = vocabulary
+// rows per workgroup, cache_e = the workgroup's embedding rows lie in LDS behind the weights (else the logits phase reads E from
+// global memory), lds_bytes = the dynamic LDS of the launch.  ok = 0: the launchers refuse (D / G > 2 units per workgroup, L > 8,
+// D > 512 or no multiple of 4, the weights alone exceed lds_max, mode < 0).  Host arithmetic only.
+struct DecodePlan { int ok, mode, nu, vp, cache_e, lds_bytes, G, lds_max; };      // (G, lds_max: what it was planned for)
+DecodePlan decode_plan(int mode, int D, int V, int L, int G, int lds_max);
+// the kMode of a call: 0 greedy; sampled: 1 every logit kept (top_k 0 or >= V), 2 top-k, 3 nucleus; -1: top-k or nucleus with V > 8192
+int decode_mode(bool sampled, int V, int top_k, bool nucleus);
+// G (the CU count: the size of part_val / part_idx rows) and lds_max of the current device as the launchers take them
+hipError_t decode_device(int* G, int* lds_max);
+// returns hipErrorInvalidValue where decode_plan refuses, the caller runs one launch sequence per token instead (it asks
+// decode_plan first); *grid_out = workgroups launched
 hipError_t decode_greedy(hipStream_t st, DecodeArgs a, int* grid_out);
 // the sampled loop in the same persistent form (a.sp; finished rows emit eos).  Also refuses top_k > 0 or top_p > 0 with V > 8192
 hipError_t decode_sample(hipStream_t st, DecodeArgs a, int* grid_out);
-int decode_workgroups();                            // CU count of the current device (size of part_val / part_idx rows)
 
 // natural <-> G16 row permutation of a (3D, cols) matrix (cols = 1 for biases)
 hipError_t g16_permute(hipStream_t st, float* dst, const float* src, int D, int cols, bool to_g16);

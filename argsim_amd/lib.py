@@ -161,6 +161,7 @@ SIGNATURES = {
                                          _P, _P, _P, _P]),
     'avae_debug_gemm_f32_form': (C.c_int, [C.c_int] * 14 + [C.POINTER(C.c_int32)]),
     'avae_debug_gru_plan': (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    'avae_debug_decode_plan': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'avae_debug_gru': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     'avae_bucket_count': (C.c_int, [_P]),
     'avae_bucket_info': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -84,9 +84,12 @@ def judge(p, nkept, tok):
     """a device's (nkept, token) at the position p = position(...) with the nucleus on -> dict: viol (inf: nkept is no prefix of whole
     tie groups; the other figures are then over the reference's set), same (the device's set is the reference's), logp (float64,
     of the device token over the device's set), win / margin (the Gumbel winner over the device's set and its top-2 margin),
-    deficit (best score over that set - the device token's; inf outside the set)"""
+    deficit (best score over that set - the device token's; inf outside the set), tie (the device's prefix ends BEHIND the reference's
+    group: how far its last value lies under the reference's last one, in l / T -- two logits that are one tie group in fp32 and two in
+    float64 make the device keep the second with the first; inf where the prefix ends elsewhere)"""
     nu, top_p = p['nucleus'], p['top_p']
     hit = np.flatnonzero(nu['sizes'] == nkept)
+    tie = np.inf
     if len(hit) == 0:
         o, viol, same = p, np.inf, False
     else:
@@ -94,9 +97,11 @@ def judge(p, nkept, tok):
         o = over(p, p['k0'] & (p['l'] >= nu['values'][jd]))
         viol = float(max(top_p - nu['cum'][jd], (nu['cum'][jd - 1] if jd else 0.0) - top_p, 0.0))
         same = jd == nu['j']
+        if jd > nu['j']:
+            tie = float(p['x'][p['l'] == nu['values'][nu['j']]][0] - p['x'][p['l'] == nu['values'][jd]][0])
     with np.errstate(invalid='ignore'):
         deficit = float(o['scores'][o['token']] - o['scores'][tok]) if o['kept'][tok] else np.inf
-    return dict(viol=viol, same=same, logp=float(o['logp'][tok]), win=o['token'], margin=o['margin'], deficit=deficit)
+    return dict(viol=viol, same=same, logp=float(o['logp'][tok]), win=o['token'], margin=o['margin'], deficit=deficit, tie=tie)
 
 
 @contextlib.contextmanager
@@ -110,12 +115,12 @@ def _position_of(fn):
         sr.position = old
 
 
-FIELDS = ('bmargin', 'nkept_ref', 'viol', 'same', 'logp_set', 'win', 'margin_set', 'deficit_set')
+FIELDS = ('bmargin', 'nkept_ref', 'viol', 'same', 'logp_set', 'win', 'margin_set', 'deficit_set', 'tie')
 
 
 def sample(P, cfg, z, steps, T=1.0, top_k=0, top_p=0.0, seed=0, replay=None, nkept=None):
     """sampling_ref.sample with the nucleus (its dict, over the reference's set), plus (b, n_pos) arrays: bmargin, nkept_ref, and
-    with replay and the device's nkept (b, >= n_pos) the figures of judge(): viol, same, logp_set, win, margin_set, deficit_set"""
+    with replay and the device's nkept (b, >= n_pos) the figures of judge(): viol, same, logp_set, win, margin_set, deficit_set, tie"""
     on = nucleus_on(T, top_k, top_p)
     rec = {}
 
@@ -125,7 +130,7 @@ def sample(P, cfg, z, steps, T=1.0, top_k=0, top_p=0.0, seed=0, replay=None, nke
         if replay is not None and nkept is not None and on:
             tok = int(replay[r, t]) if t < replay.shape[1] else cfg['eos']
             jd = judge(p, int(nkept[r, t]), tok)
-            d.update(viol=jd['viol'], same=jd['same'], logp_set=jd['logp'], win=jd['win'], margin_set=jd['margin'], deficit_set=jd['deficit'])
+            d.update(viol=jd['viol'], same=jd['same'], logp_set=jd['logp'], win=jd['win'], margin_set=jd['margin'], deficit_set=jd['deficit'], tie=jd['tie'])
         rec[(r, t)] = d
         return p
 
@@ -139,4 +144,5 @@ def sample(P, cfg, z, steps, T=1.0, top_k=0, top_p=0.0, seed=0, replay=None, nke
                 a[r, t] = d[k]
         res[k] = a
     res['bmargin'][~res['live']] = np.inf
+    res['tie'][~res['live']] = np.inf
     return res
