@@ -292,6 +292,7 @@ inline int reserve_named(avae_ctx* h, size_t need, const char* what)
 }
 int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train);
 int gemm(avae_ctx* h, const GemmCall& c);
+int gemm_bf16_pre(avae_ctx* h, const GemmCall& c);
 int gemm_tn16(avae_ctx* h, const GemmCall& c);
 // batch groups per job and rows per group (a multiple of 16) of a GRU launch over B rows: at most 512 workgroups, at most 16 groups
 void gru_geometry(int D, int njobs, int B, int* G, int* rpg);

@@ -462,16 +462,45 @@ __global__ __launch_bounds__(512) void gemm_bf16_tn256_kernel(GemmBf16Args g)
 
 static int big_tile_count(const GemmArgs& g) { return ((g.M + T2 - 1) / T2) * ((g.N + T2 - 1) / T2); }
 
+// what gemm_bf16_nt (tn false) / gemm_bf16_tn (tn true) do with a problem, from the arguments alone: both launch from this value
+GemmBf16Form gemm_bf16_form(bool tn, int lda, int ldb, const GemmArgs& g)
+{
+    GemmBf16Form f{kBf16None, 1, 1, false, hipSuccess};
+    const GemmBf16Form refuse{kBf16None, 1, 1, false, hipErrorInvalidValue};
+    if (g.M <= 0 || g.N <= 0) return f;
+    if (tn) {
+        if ((lda | ldb | g.M | g.N) & 7 || g.dyn_kind == 1 || g.bias) return refuse;
+    } else {
+        if ((lda | ldb) & 7) return refuse;
+        if (g.dyn_kind == 2 && g.split_k > 1 && g.bias) return refuse;      // (a slice beyond a device-side depth returns before its epilogue: slice 0 of a zero depth would drop the bias)
+        if (g.c16 && !gemm_bf16_c16_ok(g, lda, ldb)) return refuse;      // (only the phased kernel writes the 2-byte panel: the caller asks first)
+    }
+    // large tiles where they fill the chip, by themselves or through the K split (re-derived for them: gemm_bf16_slices)
+    const int big_tiles = big_tile_count(g);
+    f.s2 = f.slices = gemm_bf16_slices(g.split_k, big_tiles, g.K, BKH);
+    if (tn) {
+        f.kernel = gemm_bf16_p8_tn_ok(g, lda, ldb) ? kBf16P8Tn : kBf16Tn256;
+        if (f.kernel == kBf16P8Tn) { f.slices = gemm_bf16_p8_tn_slices(g, f.s2); f.slab = gemm_bf16_p8_tn_slab(g, f.slices); }
+    } else if (gemm_bf16_big_fills(g.M, g.N, big_tiles, f.s2)) {
+        f.kernel = gemm_bf16_p8_ok(g, lda, ldb) ? kBf16P8Nt : kBf16Nt256;
+        if (f.kernel == kBf16P8Nt) f.slices = gemm_bf16_p8_slices(g.K, f.s2);
+    } else {
+        f.kernel = kBf16Nt128;
+        f.slices = g.split_k > 1 ? g.split_k : 1;
+    }
+    return f;
+}
+
 // C (M x N) = alpha * A^T B (+ C): A [K][lda], B [K][ldb] bf16 row-major as their producers wrote them.  K split over
 // ~2 rounds of one workgroup per CU with float atomics INTO C (which must hold the value to add onto: the zero-filled
 // gradient) when g.split_k > 1, as gemm_bf16_nt re-derives it; g.dyn / dyn_kind 2: device-side K.
 hipError_t gemm_bf16_tn(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g)
 {
-    if (g.M <= 0 || g.N <= 0) return hipSuccess;
-    if ((lda | ldb | g.M | g.N) & 7 || g.dyn_kind == 1 || g.bias) return hipErrorInvalidValue;
+    const GemmBf16Form f = gemm_bf16_form(true, lda, ldb, g);
+    if (f.kernel == kBf16None) return f.err;
     GemmBf16Args a{A, B, g.C, nullptr, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, g.split_k, g.dyn, g.dyn_kind};
-    const int big_tiles = big_tile_count(g), s2 = gemm_bf16_slices(g.split_k, big_tiles, g.K, BKH);
-    if (gemm_bf16_p8_tn_ok(g, lda, ldb)) return gemm_bf16_p8_tn(st, A, lda, B, ldb, g, s2);
+    const int big_tiles = big_tile_count(g), s2 = f.s2;
+    if (f.kernel == kBf16P8Tn) return gemm_bf16_p8_tn(st, A, lda, B, ldb, g, s2);
     static bool attr_done = false;
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_tn256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kTnLds);
@@ -500,15 +529,12 @@ bool gemm_bf16_c16_takes(int M, int N, int K, const int* rows, int nt8)
 // operands already converted: A [M][lda] bf16, B [N][ldb] bf16, lda/ldb multiples of 8
 hipError_t gemm_bf16_nt(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g)
 {
-    if (g.M <= 0 || g.N <= 0) return hipSuccess;
-    if ((lda | ldb) & 7) return hipErrorInvalidValue;
-    if (g.dyn_kind == 2 && g.split_k > 1 && g.bias) return hipErrorInvalidValue;      // (a slice beyond a device-side depth returns before its epilogue: slice 0 of a zero depth would drop the bias)
-    if (g.c16 && !gemm_bf16_c16_ok(g, lda, ldb)) return hipErrorInvalidValue;      // (only the phased kernel writes the 2-byte panel: the caller asks first)
+    const GemmBf16Form f = gemm_bf16_form(false, lda, ldb, g);
+    if (f.kernel == kBf16None) return f.err;
     GemmBf16Args a{A, B, g.C, g.bias, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, g.split_k, g.dyn, g.dyn_kind};
-    // large tiles where they fill the chip, by themselves or through the K split (re-derived for them: gemm_bf16_slices)
-    const int big_tiles = big_tile_count(g), s2 = gemm_bf16_slices(g.split_k, big_tiles, g.K, BKH);
-    if (gemm_bf16_big_fills(g.M, g.N, big_tiles, s2)) {
-        if (gemm_bf16_p8_ok(g, lda, ldb)) return gemm_bf16_p8(st, A, lda, B, ldb, g, s2);
+    const int big_tiles = big_tile_count(g), s2 = f.s2;
+    if (f.kernel != kBf16Nt128) {
+        if (f.kernel == kBf16P8Nt) return gemm_bf16_p8(st, A, lda, B, ldb, g, s2);
         static bool attr_done = false;
         if (!attr_done) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_nt256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kBigLds);
@@ -522,7 +548,7 @@ hipError_t gemm_bf16_nt(hipStream_t st, const unsigned short* A, int lda, const 
         return hipGetLastError();
     }
     int tiles = ((g.M + 127) / 128) * ((g.N + 127) / 128);
-    dim3 grid(tiles, 1, g.split_k > 1 ? g.split_k : 1);
+    dim3 grid(tiles, 1, f.slices);
     hipLaunchKernelGGL(gemm_bf16_nt_kernel, grid, dim3(256), 0, st, a);
     return hipGetLastError();
 }

@@ -468,27 +468,15 @@ static hipError_t p8_attrs()
     return e;
 }
 
-// s2: the K split (>= 1) as gemm_bf16_nt derived it; the caller's g.split_k > 1 says C holds the value to add onto
-hipError_t gemm_bf16_p8(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g, int s2)
+// the slices gemm_bf16_p8 launches for a split s2: every slice holds two K tiles or more
+int gemm_bf16_p8_slices(int K, int s2)
 {
-    P8Args a{A, B, g.C, g.bias, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, s2, g.dyn, g.dyn_kind, g.c16, nullptr};
-    if (g.c16 && (g.bias || g.accumulate || g.split_k > 1 || s2 > 1)) return hipErrorInvalidValue;
-    if (g.split_k > 1 && s2 == 1) a.accumulate = 1;       // the caller's slices were going to ADD into C
-    const int nkt = g.K / kP8K;
-    if (2 * s2 > nkt) a.split_k = s2 = std::max(1, nkt / 2);       // (every slice holds two K tiles or more)
-    hipError_t e = p8_attrs();
-    if (e != hipSuccess) return e;
-    const int tiles = ((g.M + kP8Tile - 1) / kP8Tile) * ((g.N + kP8Tile - 1) / kP8Tile);
-    const int grid = std::min(tiles * s2, 256);
-    if (g.c16) hipLaunchKernelGGL((gemm_bf16_p8_kernel<false, false, true>), dim3(grid), dim3(512), kP8Lds, st, a);
-    else if (g.bias) hipLaunchKernelGGL((gemm_bf16_p8_kernel<true, false>), dim3(grid), dim3(512), kP8Lds, st, a);
-    else hipLaunchKernelGGL((gemm_bf16_p8_kernel<false, false>), dim3(grid), dim3(512), kP8Lds, st, a);
-    return hipGetLastError();
+    const int nkt = K / kP8K;
+    if (2 * s2 > nkt) s2 = std::max(1, nkt / 2);
+    return s2;
 }
-
-// C (M x N) = alpha * A^T B (+ C): A [K][lda], B [K][ldb] bf16 row-major.  s2 > 1: K slices added into C with float atomics (C holds
-// the value to add onto); the device shrinks the split when a device-side K leaves fewer than two K tiles per slice
-hipError_t gemm_bf16_p8_tn(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g, int s2)
+// the slices gemm_bf16_p8_tn launches: without a caller's split, s2 as it stands
+int gemm_bf16_p8_tn_slices(const GemmArgs& g, int s2)
 {
     const int tiles = ((g.M + kP8Tile - 1) / kP8Tile) * ((g.N + kP8Tile - 1) / kP8Tile);
     if (g.split_k > 1) {
@@ -504,9 +492,41 @@ hipError_t gemm_bf16_p8_tn(hipStream_t st, const unsigned short* A, int lda, con
         }
         s2 = best;
     }
+    return s2;
+}
+// do the slices' partial tiles go to the slab (summed by p8_slab_reduce_kernel) instead of float atomics into C?
+bool gemm_bf16_p8_tn_slab(const GemmArgs& g, int s2)
+{
+    const int tiles = ((g.M + kP8Tile - 1) / kP8Tile) * ((g.N + kP8Tile - 1) / kP8Tile);
+    return s2 > 1 && g.slab && (size_t)tiles * s2 * (kP8Tile * kP8Tile) <= g.slab_floats;
+}
+
+// s2: the K split (>= 1) as gemm_bf16_nt derived it; the caller's g.split_k > 1 says C holds the value to add onto
+hipError_t gemm_bf16_p8(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g, int s2)
+{
+    P8Args a{A, B, g.C, g.bias, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, g.accumulate, s2, g.dyn, g.dyn_kind, g.c16, nullptr};
+    if (g.c16 && (g.bias || g.accumulate || g.split_k > 1 || s2 > 1)) return hipErrorInvalidValue;
+    if (g.split_k > 1 && s2 == 1) a.accumulate = 1;       // the caller's slices were going to ADD into C
+    a.split_k = s2 = gemm_bf16_p8_slices(g.K, s2);
+    hipError_t e = p8_attrs();
+    if (e != hipSuccess) return e;
+    const int tiles = ((g.M + kP8Tile - 1) / kP8Tile) * ((g.N + kP8Tile - 1) / kP8Tile);
+    const int grid = std::min(tiles * s2, 256);
+    if (g.c16) hipLaunchKernelGGL((gemm_bf16_p8_kernel<false, false, true>), dim3(grid), dim3(512), kP8Lds, st, a);
+    else if (g.bias) hipLaunchKernelGGL((gemm_bf16_p8_kernel<true, false>), dim3(grid), dim3(512), kP8Lds, st, a);
+    else hipLaunchKernelGGL((gemm_bf16_p8_kernel<false, false>), dim3(grid), dim3(512), kP8Lds, st, a);
+    return hipGetLastError();
+}
+
+// C (M x N) = alpha * A^T B (+ C): A [K][lda], B [K][ldb] bf16 row-major.  s2 > 1: K slices added into C with float atomics (C holds
+// the value to add onto); the device shrinks the split when a device-side K leaves fewer than two K tiles per slice
+hipError_t gemm_bf16_p8_tn(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g, int s2)
+{
+    const int tiles = ((g.M + kP8Tile - 1) / kP8Tile) * ((g.N + kP8Tile - 1) / kP8Tile);
+    s2 = gemm_bf16_p8_tn_slices(g, s2);
     // (a caller's split says C holds the value to add onto -- also when the device shrinks the split to one slice)
     const int add = g.accumulate || g.split_k > 1;
-    const bool use_slab = s2 > 1 && g.slab && (size_t)tiles * s2 * (kP8Tile * kP8Tile) <= g.slab_floats;
+    const bool use_slab = gemm_bf16_p8_tn_slab(g, s2);
     P8Args a{A, B, g.C, nullptr, g.M, g.N, g.K, lda, ldb, g.ldc, g.alpha, add, s2, g.dyn, g.dyn_kind, nullptr, use_slab ? g.slab : nullptr};
     hipError_t e = p8_attrs();
     if (e != hipSuccess) return e;

@@ -198,6 +198,53 @@ int avae_debug_gemm_tn16(avae_handle h, const float* A, const float* Bm, float* 
     if (!h) return 1;
     return gemm_tn16(h, tn_grad(A, lda, Bm, ldb, Cm, ldc, M, N, K).scaled(alpha));
 }
+// test hook (compute_dtype 1): one product whose operands a producer wrote as bf16, through the functions the step calls.  route 0: gemm_bf16_pre --
+// A16 row-major with lda, the A panel itself (a_mc 0: (M, lda)) or transposed once from the 2-byte source (a_mc 1: (K, lda)); B fp32 in layout b_nc.
+// route 1: gemm_tn16 -- C += alpha A^T B, A (K, lda) and B (K, ldb) row-major, each as bf16 (A16 / B16) or, where that is null, as fp32 (A / Bm).
+// wgrad: the call is a weight gradient (tn_grad: the K split comes from the plan and C holds the value to add onto); route 1 always is.  count /
+// dyn_kind / expect as in avae_debug_gemm_forced.  The plan, the slab and the options are the product's; a refusal comes back as in the product.
+int avae_debug_gemm16(avae_handle h, int route, int a_mc, int b_nc, int wgrad, const unsigned short* A16, const unsigned short* B16, const float* A,
+                      const float* Bm, float* Cm, const float* bias, int M, int N, int K, int lda, int ldb, int ldc, float alpha, int accumulate,
+                      const int* count, int dyn_kind, int expect)
+{
+    if (!h) return 1;
+    if (h->cfg.compute_dtype != 1) return fail(h, "avae_debug_gemm16: 16-bit operands exist in compute_dtype 1 only");
+    if (route < 0 || route > 1 || dyn_kind < 0 || dyn_kind > 2 || (dyn_kind != 0) != (count != nullptr))
+        return fail(h, "avae_debug_gemm16: route in 0..1, dyn_kind in 0..2 with a count exactly where it is not 0");
+    if (route == 0 && (!A16 || B16)) return fail(h, "avae_debug_gemm16: gemm_bf16_pre takes A16 and an fp32 B");
+    GemmCall c = route == 1 ? tn_grad(A, lda, Bm, ldb, Cm, ldc, M, N, K) : GemmCall{nullptr, lda, a_mc != 0, Bm, ldb, b_nc != 0, Cm, ldc, M, N, K};
+    c.alpha = alpha; c.bias = bias; c.accumulate = accumulate; c.A16 = A16; c.B16 = B16;
+    if (route == 0) c.wgrad = wgrad != 0;
+    if (dyn_kind == 2) c.depth(count); else c.rows(count);
+    const int* const was_ptr = h->expect_ptr[0]; const int was_val = h->expect_val[0];
+    h->expect_ptr[0] = count; h->expect_val[0] = expect;
+    const int r = route == 1 ? gemm_tn16(h, c) : gemm_bf16_pre(h, c);
+    h->expect_ptr[0] = was_ptr; h->expect_val[0] = was_val;
+    return r;
+}
+// test hook: what gemm_bf16_nt (tn 0) / gemm_bf16_tn (tn 1) launch for a problem whose panels have the leading dimensions lda / ldb
+// (gemm_bf16_form: the function both launch from).  wgrad: the K split is the plan's for a weight gradient of the shape (bf16_launch: gemm_plan) and,
+// as in gemm_tn16, the slab of slab_floats floats is offered where nt8 is on and that split is above 1; else split_k and the slab as given.
+// out = kernel (GemmBf16Kernel: 0 128x128 NT, 1 256x256 NT, 2 phased NT, 3 256x256 TN, 4 phased TN, -1 nothing), the slices it is launched
+// with, slab used, refused, the split the caller's was re-derived to, the split asked of the launcher.  Host arithmetic only: callable without a GPU.
+int avae_debug_gemm_bf16_form(int tn, int wgrad, int M, int N, int K, int lda, int ldb, int ldc, int split_k, int dyn_kind, int bias, int nt8,
+                              int64_t slab_floats, int32_t out[6])
+{
+    if (!out || slab_floats < 0 || (wgrad && (M < 1 || N < 1))) return 1;      // (the plan of a weight gradient divides by its tile count)
+    alignas(16) static float other[4] = {0.f, 0.f, 0.f, 0.f};      // (the form looks at whether there is a bias and a slab, never at what they hold)
+    if (wgrad) {
+        const GemmShape s{true, true, M, N, K, ldc, 0, 0, -1, dyn_kind, 0, false, false, false, true, 1, true, true, true};
+        split_k = gemm_plan(s).launch[0].split_k;
+    }
+    GemmArgs g{nullptr, nullptr, nullptr, bias ? other : nullptr, M, N, K, lda, ldb, ldc, 1.f, 0, split_k, dyn_kind ? reinterpret_cast<const int*>(other) : nullptr,
+               dyn_kind, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    g.nt8 = nt8;
+    if (slab_floats > 0 && (!wgrad || (nt8 && split_k > 1))) { g.slab = other; g.slab_floats = (size_t)slab_floats; }
+    const GemmBf16Form f = gemm_bf16_form(tn != 0, lda, ldb, g);
+    const int32_t v[6] = {f.kernel, f.slices, f.slab, f.err != hipSuccess, f.s2, split_k};
+    std::copy(v, v + 6, out);
+    return 0;
+}
 // test hook: softmax_ce (ops.hip) on caller buffers, enqueued on the handle's stream.  logits (n_max x V fp32) and panel (n_max x V,
 // 2-byte) as CeArgs::logits / grad16: with write_grad the gradient goes to panel as bf16 when panel is given, else over the logits;
 // logits16 reads the logits from panel as fp16.  *form_out = softmax_ce_form (0 register, 1 fp16 panel, 2 streaming, -1 refused).

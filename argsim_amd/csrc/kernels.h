@@ -73,6 +73,17 @@ hipError_t gemm_bf16_p8_tn(hipStream_t st, const unsigned short* A, int lda, con
 // C = alpha * A^T B (+C): A [K][lda] (m contiguous), B [K][ldb] (n contiguous) bf16, read with transposing LDS loads -- no
 // transposed copy of either operand (M, N, lda, ldb multiples of 8; split_k > 1: float atomics into C)
 hipError_t gemm_bf16_tn(hipStream_t st, const unsigned short* A, int lda, const unsigned short* B, int ldb, const GemmArgs& g);
+// the slices the phased launchers run for a split s2 as gemm_bf16_nt / gemm_bf16_tn derived it (NT: two K tiles or more per slice; TN: the
+// split that fills whole rounds of the persistent grid, where the caller asked for one), and whether the TN slices go through GemmArgs::slab
+int gemm_bf16_p8_slices(int K, int s2);
+int gemm_bf16_p8_tn_slices(const GemmArgs& g, int s2);
+bool gemm_bf16_p8_tn_slab(const GemmArgs& g, int s2);
+// what gemm_bf16_nt (tn false) / gemm_bf16_tn (tn true) launch for a problem, decided from the arguments alone (host arithmetic, no device):
+// the kernel (kBf16None: nothing to launch, or with err the refusal returned instead), s2: the split re-derived for 256x256 tiles, slices: what
+// the kernel is launched with, slab: the slices' partial tiles go through GemmArgs::slab and p8_slab_reduce_kernel
+enum GemmBf16Kernel { kBf16None = -1, kBf16Nt128 = 0, kBf16Nt256 = 1, kBf16P8Nt = 2, kBf16Tn256 = 3, kBf16P8Tn = 4 };
+struct GemmBf16Form { int kernel, s2, slices; bool slab; hipError_t err; };
+GemmBf16Form gemm_bf16_form(bool tn, int lda, int ldb, const GemmArgs& g);
 // bf16 [K][X] (row stride ld) -> bf16 [X][ldk] (ldk = K rounded up to 8, pad zero-filled)
 hipError_t transpose_bf16(hipStream_t st, const unsigned short* src, int ld, int K, int X, unsigned short* dst, int ldk);
 

@@ -229,7 +229,7 @@ int gemm(avae_ctx* h, const GemmCall& c)
 
 // bf16 mode, A already bf16 and row-major (c.A16: (rows, lda), written by the producer -- the softmax gradient, a layer's h): as the A
 // panel itself (a_mc = false: k-contiguous) or transposed once from the 2-byte source (a_mc = true); B converted as usual.
-static int gemm_bf16_pre(avae_ctx* h, const GemmCall& c)
+int gemm_bf16_pre(avae_ctx* h, const GemmCall& c)
 {
     const GemmLaunch l = bf16_launch(h, c);
     const int M = c.M, N = c.N, K = c.K;
@@ -256,7 +256,7 @@ int gemm_tn16(avae_ctx* h, const GemmCall& c)
 {
     const GemmLaunch l = bf16_launch(h, c);
     const int M = c.M, N = c.N, K = c.K;
-    GemmArgs g{nullptr, nullptr, c.C, nullptr, M, N, K, c.lda, c.ldb, c.ldc, c.alpha, l.accumulate, l.split_k, c.dyn, c.dyn_kind, 0, 0, nullptr, nullptr, nullptr, nullptr};
+    GemmArgs g{nullptr, nullptr, c.C, c.bias, M, N, K, c.lda, c.ldb, c.ldc, c.alpha, l.accumulate, l.split_k, c.dyn, c.dyn_kind, 0, 0, nullptr, nullptr, nullptr, nullptr};      // (a bias: gemm_bf16_tn refuses it)
     Timed t(h, 0, 2.0 * M * N * K, c.dyn, c.dyn ? K : 0);
     const unsigned short* A16 = c.A16; const unsigned short* B16 = c.B16;
     int la = c.lda, lb = c.ldb;

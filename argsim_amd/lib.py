@@ -160,6 +160,8 @@ SIGNATURES = {
     'avae_debug_gemm_forced': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int,
                                          _P, _P, _P, _P]),
     'avae_debug_gemm_f32_form': (C.c_int, [C.c_int] * 14 + [C.POINTER(C.c_int32)]),
+    'avae_debug_gemm16': (C.c_int, [_P] + [C.c_int] * 4 + [_P] * 6 + [C.c_int] * 6 + [C.c_float, C.c_int, _P, C.c_int, C.c_int]),
+    'avae_debug_gemm_bf16_form': (C.c_int, [C.c_int] * 12 + [C.c_int64, C.POINTER(C.c_int32)]),
     'avae_debug_gru_plan': (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     'avae_debug_decode_plan': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'avae_debug_gru': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),

@@ -48,6 +48,13 @@ class Case:
     reach: tuple = None       # (tile, fast, db, persist) the case claims of gemm_f32_form; None: another kernel family
     dtype: int = 0            # compute_dtype of the handle it runs on
     seed: int = 0
+    # ---- 16-bit operands (bf16 mode): see operand16()
+    route: int = -1           # avae_debug_gemm16's route (0 gemm_bf16_pre, 1 gemm_tn16); -1: fp32 operands through the other hooks
+    ops16: str = ''           # which operands go over as bf16 the way a producer wrote them: 'a', 'b' or 'ab'
+    wgrad: int = 0            # route 0: the call is a weight gradient (the plan's K split, C holds the value to add onto)
+    nt8: int = 1              # the handle's option bf16_nt8 the case runs with
+    round16: bool = False     # the draws are rounded to bf16 (RNE) on the host: both operand forms then hold the same values
+    reach16: tuple = None     # (kernel, slices, slab) the case claims of avae_debug_gemm_bf16_form
 
     @property
     def M_eff(self):
@@ -68,6 +75,20 @@ class Case:
     @property
     def ldc(self):
         return self.N + (0 if self.plain_out else PAD)
+
+    @property
+    def lda16(self):
+        """leading dimension of A as a producer's bf16 array: [k][m] twice the logical width (route 1: the logical columns are the SECOND half, as one
+        direction's dgh16 out of the 6 D wide array; route 0: + 8), k-contiguous (the panel itself) twice K"""
+        return (2 * self.M if self.route == 1 else self.M + PAD) if self.a_mc else 2 * self.K
+
+    @property
+    def off16(self):
+        return self.M if self.a_mc and self.route == 1 else 0
+
+    @property
+    def ldb16(self):
+        return self.N + PAD
 
     @property
     def id(self):
@@ -133,6 +154,8 @@ def build(c):
     out = []
     for _ in range(2 if c.pair else 1):
         a, b = _draw(rng, (c.M, c.K), c.data), _draw(rng, (c.K, c.N), c.data)
+        if c.round16:
+            a, b = bf16_round(a), bf16_round(b)
         A, B = _operand(a, c.a_mc), _operand(b.T, c.b_nc)
         if c.dyn_kind == 1:
             if c.a_mc:
@@ -211,6 +234,41 @@ def bf16_round(x):
     u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
     u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
     return u.astype(np.uint32).view(np.float32).astype(np.float64)
+
+
+NAN16 = np.uint16(0x7FC1)     # a bf16 NaN: what a 16-bit operand buffer holds wherever a correct kernel does not read
+
+
+def bf16_bits(x):
+    """values -> their bf16 bit patterns (RNE) as uint16"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+
+
+def operand16(rows, ld, off=0, valid=None):
+    """rows: the (R, X) array as a producer wrote it row-major (a [k][x] operand: R = K; the k-contiguous panel: R = M).  -> the uint16 buffer
+    (R + OP_GUARD_ROWS, ld) holding bf16(rows) in the columns from off on, NAN16 in every other column, in the guard rows and in the rows from
+    `valid` on (the rows behind a device-side count)"""
+    R, X = rows.shape
+    assert off + X <= ld
+    buf = np.full((R + OP_GUARD_ROWS, ld), NAN16, np.uint16)
+    v = R if valid is None else min(R, valid)
+    buf[:v, off:off + X] = bf16_bits(rows[:v])
+    return buf
+
+
+def operands16(c, p):
+    """-> (A16, B16) of a case with Case.ops16, None where the operand goes over as fp32; the count cuts the rows as in build()"""
+    a16 = b16 = None
+    if 'a' in c.ops16:
+        if c.a_mc:
+            a16 = operand16(p.a.T, c.lda16, c.off16, c.K_eff if c.dyn_kind == 2 else None)
+        else:
+            a16 = operand16(p.a, c.lda16, c.off16, c.M_eff if c.dyn_kind == 1 else None)
+    if 'b' in c.ops16:
+        assert c.b_nc
+        b16 = operand16(p.b, c.ldb16, 0, c.K_eff if c.dyn_kind == 2 else None)
+    return a16, b16
 
 
 def bound(c, p, family):

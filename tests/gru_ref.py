@@ -19,7 +19,10 @@ through dgh R and the carry dH u.  Bias sums: ops_ref.sum_bound.
 2^-9 |x| everywhere: bf16 keeps 8 significant bits, so half an ulp is 2^-9 |x| only at the top of a binade and 2^-8 |x| at its bottom (1 + 2^-8
 + 2^-20 rounds to 1 + 2^-7: an error of 0.996 * 2^-8 |x|); a correctly rounded value misses 2^-9 |x| for about half of all inputs
 (tests/test_gru_ref.py test_half_ulp_of_bf16).  The stronger statement is checked beside it: a 16-bit array is, bit for bit, the
-round-to-nearest-even bf16 of the fp32 array the same launch gives without it."""
+round-to-nearest-even bf16 of the fp32 array the same launch gives without it.
+
+16-bit inputs (Case.in16): the backward's drawn sv / hp are rounded to bf16 and packed as uint16 beside the fp32 arrays of the same values, NAN16
+wherever no step reads (read_mask); the launch that reads them must give the bits of the launch that reads the fp32 arrays."""
 import dataclasses
 
 import numpy as np
@@ -160,6 +163,8 @@ class Case:
     dgh16_only: bool = False        # backward: dgh16 alone, dgi stays fp32 (a table-fed layer)
     table: bool = False             # forward: gi is a per-id table of TABLE_ROWS rows read through gi_rows
     by_pos: bool = False            # backward, with cmp: dgi keeps the padded (pos * B + row) layout, zeros at padding (dgi_by_pos)
+    in16: str = ''                  # backward, bf16 team forms: 'sv' the saved gates (GruArgs::sv16), 'hp' h_prev (GruJob::hp16) or 'sv+hp' are READ as bf16, as
+                                    # the bf16 forward leaves them; the drawn sv / hp are rounded to bf16 on the host, so the fp32 arrays hold the same values
     seed: int = 0
 
     @property
@@ -234,6 +239,19 @@ def make_rows(c, T=0, cpj=0):
     return Rows(lens, plen, steps, rowmap, nrows, perm, slens, map_dev)
 
 
+NAN16 = np.uint16(0x7FC1)         # a bf16 NaN: what a 16-bit INPUT holds wherever no launch may read
+
+
+def read_mask(c, rows, reverse):
+    """(S, rows): the positions whose saved state a backward launch reads -- position pos_map(p) of every step p the row's team runs, where it has a row"""
+    pos = pos_table(c.S, rows.plen, reverse)
+    read = np.zeros((c.S, c.rows), bool)
+    for p in range(c.S):
+        sel = np.flatnonzero(rows.steps > p)
+        read[pos[p, sel], sel] = True
+    return read & (rows.rowmap >= 0)
+
+
 def nan32(shape):
     return np.full(shape, np.nan, np.float32)
 
@@ -289,6 +307,14 @@ def make_inputs(c, rows):
             sv[..., 3] = 0.5 * rng.standard_normal((S, B, D))
             L['sv'] = sv
             L['hp'] = rng.uniform(-1, 1, (S, B, D)).astype(np.float32)
+            if c.in16:
+                L['sv'], L['hp'] = bf16_rne(L['sv'])[1], bf16_rne(L['hp'])[1]
+                # the 16-bit arrays: NAN16 wherever no step of the launch reads -- guard rows, and in the padded layout the positions behind a row's steps
+                read = read_mask(c, rows, k == 1)
+                for nm, w in (('sv', 4 * D), ('hp', D)):
+                    b['%s16_%d' % (nm, k)] = np.full((n + GUARD_ROWS, w), NAN16, np.uint16)
+                    b['%s16_%d' % (nm, k)][rows.rowmap[read]] = bf16_rne(L[nm].reshape(S, B, w)[read])[0]
+                sv = L['sv']
             L['dh_out'] = rng.standard_normal((S, B, D)).astype(np.float32)
             L['dh_out'][np.arange(S)[:, None] >= rows.lens[None, :]] = 0          # zero at padding, as the model guarantees
             L['dbW0'] = rng.standard_normal(3 * D).astype(np.float32)
@@ -428,12 +454,23 @@ def run_backward(c, rows, inp, out, dtype=np.float32, defect=''):
                 for p in range(int(rows.steps[bi]), S):
                     out['dgi'][rows.rowmap[p, bi], cols] = 0
                     out['dgh'][rows.rowmap[p, bi], cols] = 0
+        Lsv, Lhp = L['sv'], L['hp']
+        if c.in16:
+            # the saved state as a kernel gets it: out of the 16-bit buffers, widened.  Defects: 'sv16_index' -- the gates fetched at the fp32
+            # element index (twice the halfword offset; beyond the buffer a buffer load gives zeros); 'hp16_next' -- h_prev of position p from p + 1
+            flat = widen16(inp['sv16_%d' % k]).ravel()
+            at = (np.arange(flat.size) * (2 if defect == 'sv16_index' else 1))
+            sv_rows = np.where(at < flat.size, flat[np.minimum(at, flat.size - 1)], 0).astype(np.float32).reshape(-1, 4 * D)
+            Lsv = logical(sv_rows, rows, 0, 4 * D).reshape(S, B, D, 4)
+            Lhp = logical(inp['hp16_%d' % k], rows, 0, D)
+            if defect == 'hp16_next':
+                Lhp = Lhp[np.minimum(np.arange(S) + 1, S - 1)]
         for p in range(S - 1, -2, -1):
             act = rows.steps > max(p, 0)
             nxt = rows.steps > p + 1
             q = pos[max(p, 0)], np.arange(B)
             ok = real[q] & act
-            sv, hp, do = (np.where(ok.reshape((B,) + (1,) * (x.ndim - 2)), x[q], 0) for x in (L['sv'], L['hp'], L['dh_out']))
+            sv, hp, do = (np.where(ok.reshape((B,) + (1,) * (x.ndim - 2)), x[q], 0) for x in (Lsv, Lhp, L['dh_out']))
             cin = np.where(nxt[:, None], carry, 0)
             if defect == 'carry':
                 cin = cin * 0
@@ -716,5 +753,36 @@ def team16_cases():
     return o
 
 
+def team_in16_cases():
+    """backward launches of the bf16 team forms READING their saved gates / h_prev as bf16 (the default bf16 configuration of a step: bf16_sv, bf16_act):
+    T = 2 / 4, with and without PIPE, one and two jobs; then the layouts and outputs that change the load's row index or what the step writes; then
+    each 16-bit input without the other (a table-fed layer keeps h_prev fp32; bf16_sv = 0 keeps the gates fp32)"""
+    o = []
+    for njobs, B in SMALL_TEAM:
+        o.append(_team('team-in16', False, njobs, B, 5 if B >= 384 else 6, bf16=1, in16='sv+hp'))
+    o.append(_team('team-in16-skip', False, 2, 64, bf16=1, in16='sv+hp', skip='sorted'))
+    o.append(_team('team-in16-cmp', False, 2, 64, bf16=1, in16='sv+hp', skip='sorted', cmp=True))
+    o.append(_team('team-in16-phantom', False, 1, 32, bf16=1, in16='sv+hp', skip='sorted', cmp=True, Breal=20))
+    o.append(_team('team-in16-dgh16', False, 2, 64, bf16=1, in16='sv+hp', dgh16_only=True))
+    o.append(_team('team-in16-16', False, 2, 512, 5, bf16=1, in16='sv+hp', out16=True))
+    o.append(_team('team-in16-16-cmp', False, 2, 64, bf16=1, in16='sv+hp', out16=True, skip='sorted', cmp=True))
+    for njobs, B in ((1, 32), (2, 512)):
+        o.append(_team('team-in16-sv', False, njobs, B, 5, bf16=1, in16='sv'))
+        o.append(_team('team-in16-hp', False, njobs, B, 5, bf16=1, in16='hp'))
+    return o
+
+
+# every form gru_plan can give a backward launch that asks for bf16 operands (GruArgs::bf16) or is handed 16-bit inputs, and what check_operands
+# (gru.hip) does with sv16 / hp16 there: only the bf16 team kernels read them; everything else refuses the launch -- none ignores them
+IN16_TABLE = [
+    (_team('in16', False, 2, 64, bf16=1), 'reached'),
+    (_team('in16-pipe', False, 2, 512, 5, bf16=1), 'reached'),
+    (_team('in16-fp32', False, 2, 64), 'refused'),                           # the fp32 team kernels
+    (_team('in16-rs', False, 2, 64, bwd_rs=1), 'refused'),                   # the reduce-scatter kernel: fp32 only (bf16 = 1 plans the team form instead)
+    (_reg('in16-reg', False, 2, 16, 64, bf16=1), 'refused'),                 # register forms take bf16 OPERANDS of the recurrent product, no 16-bit arrays
+    (_reg('in16-step', False, 2, 16, 64, bf16=1, persistent=0), 'refused'),
+]
+
+
 def all_cases():
-    return register_cases() + item_cases() + team_cases() + team16_cases()
+    return register_cases() + item_cases() + team_cases() + team16_cases() + team_in16_cases()

@@ -85,10 +85,10 @@ def test_exactness_condition_holds_for_every_gpu_case():
 
 def test_hooks_are_exported_and_typed():
     lib, l = _lib()
-    for name in ('avae_debug_gemm_forced', 'avae_debug_gemm_f32_form'):
-        assert name in lib.SIGNATURES and hasattr(l, name)
     header = open(lib.CSRC + '/../../include/argsim_vae.h').read()
-    assert 'avae_debug_gemm_forced' not in header and 'avae_debug_gemm_f32_form' not in header
+    for name in ('avae_debug_gemm_forced', 'avae_debug_gemm_f32_form', 'avae_debug_gemm16', 'avae_debug_gemm_bf16_form'):
+        assert name in lib.SIGNATURES and hasattr(l, name)
+        assert name not in header
 
 
 def form(l, c, **kw):
@@ -119,6 +119,64 @@ def test_every_fp32_case_reaches_the_form_it_claims():
     for reach, lays in ((G.FAST, G.L4), (G.SKINNY, ((0, 0), (0, 1))), (G.DB_FAST, ((0, 1),)), (G.DB_PRED, ((0, 0), (1, 1))), (G.PERSIST, ((0, 0), (0, 1)))):
         for lay in lays:
             assert reach + lay in seen, (reach, lay)
+
+
+def test_16bit_operand_buffers_hold_nan_wherever_a_kernel_must_not_read():
+    c = R.case('o16', (1, 1), 16, 24, 10, dtype=1, route=1, ops16='ab', round16=True, data='rounding', dyn_kind=2, count=7)
+    p = R.build(c)[0]
+    assert np.array_equal(R.bf16_round(p.a), p.a) and np.array_equal(R.bf16_round(p.b), p.b)          # the draws are bf16 values already
+    a16, b16 = R.operands16(c, p)
+    assert (c.lda16, c.off16, c.ldb16) == (32, 16, 32) and a16.shape == (10 + R.OP_GUARD_ROWS, 32) and b16.shape == (10 + R.OP_GUARD_ROWS, 32)
+    widen = lambda u: (u.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    assert np.array_equal(widen(a16[:7, 16:]), p.a.T[:7]) and np.array_equal(widen(b16[:7, :24]), p.b[:7])
+    for buf, logical in ((a16, 7 * 16), (b16, 7 * 24)):
+        assert (buf == R.NAN16).sum() == buf.size - logical and np.isnan(widen(buf)).sum() == buf.size - logical
+    # a rows count cuts the k-contiguous panel's rows
+    c = R.case('o16', (0, 0), 9, 8, 16, dtype=1, route=0, ops16='a', round16=True, dyn_kind=1, count=4)
+    a16, b16 = R.operands16(c, R.build(c)[0])
+    assert b16 is None and c.lda16 == 32 and (a16[4:] == R.NAN16).all() and (a16[:4, 16:] == R.NAN16).all() and (a16[:4, :16] != R.NAN16).all()
+    assert R.bf16_bits(np.array([1.0, 1.00390625, 1.01171875, -3.0], np.float32)).tolist() == [0x3F80, 0x3F80, 0x3F82, 0xC040]
+
+
+def test_every_16bit_case_reaches_the_form_it_claims():
+    """the proof for the bf16-mode cases: avae_debug_gemm_bf16_form returns gemm_bf16_form, the value gemm_bf16_nt / gemm_bf16_tn launch from"""
+    lib, l = _lib()
+    seen = set()
+    for c in G.CASES16:
+        kernel, slices, slab, refused, s2, asked = G.form16(l, c)
+        assert (kernel, slices, slab) == c.reach16 and refused == 0, (c.id, kernel, slices, slab, refused)
+        seen.add((c.route, kernel, slices > 1, slab, c.dyn_kind))
+    for want in ((1, G.P8TN, False, 0, 0), (1, G.TN256, False, 0, 0), (1, G.P8TN, True, 1, 0), (1, G.TN256, True, 0, 0), (1, G.P8TN, True, 1, 2),
+                 (1, G.TN256, True, 0, 2), (1, G.P8TN, False, 0, 2), (0, G.NT128, False, 0, 0), (0, G.NT128, False, 0, 1), (0, G.NT128, True, 0, 0),
+                 (0, G.NT128, True, 0, 2), (-1, G.P8NT, True, 0, 0), (-1, G.NT256, True, 0, 0), (-1, G.P8NT, False, 0, 0), (-1, G.NT256, False, 0, 0)):
+        assert want in seen, want
+    # the cases that claim a re-derived split say which: 3 asked -> 6, and -> 1 (the launch then accumulates)
+    for c in G.NT_SPLIT_CASES:
+        assert G.form16(l, c)[4:] == [c.reach16[1], 3], c.id
+    # a slab too small for the slices' tiles: float atomics instead
+    c = [c for c in G.TN16_CASES if c.reach16 == (G.P8TN, 2, 1)][0]
+    assert G.form16(l, c, slab_floats=(8 << 16) - 1)[:3] == [G.P8TN, 2, 0] and G.form16(l, c, slab_floats=8 << 16)[:3] == [G.P8TN, 2, 1]
+
+
+def test_bf16_form_refusals_and_the_unreachable_clamp():
+    lib, l = _lib()
+    c = [c for c in G.TN16_CASES if c.reach16 == (G.P8TN, 1, 0)][0]
+    assert G.form16(l, c)[3] == 0
+    assert G.form16(l, c, dyn_kind=1)[3] == 1 and G.form16(l, c, bias=1)[3] == 1 and G.form16(l, c, lda=c.lda16 - 4)[3] == 1 and G.form16(l, c, M=c.M - 4)[3] == 1
+    p = G.PRE_CASES[0]
+    assert G.form16(l, p, M=0)[:4] == [-1, 1, 0, 0] and G.form16(l, c, wgrad=0, split_k=2, M=0)[:4] == [-1, 1, 0, 0]
+    assert G.form16(l, p, lda=p.lda16 - 4)[3] == 1 and G.form16(l, p, dyn_kind=2, split_k=3)[3] == 1 and G.form16(l, p, dyn_kind=2, split_k=3, bias=0)[3] == 0
+    # gemm_bf16_p8 clamps its split to two K tiles per slice; gemm_bf16_slices has left four already, so the phased NT kernel always runs the
+    # re-derived split as it stands (no case can reach the clamp), and a device-side depth keeps the phased NT kernel out
+    for M, N in ((1300, 1300), (5000, 2500), (4100, 4100)):
+        for K in range(128, 4097, 64):
+            for split in (1, 2, 3, 8, 40):
+                kernel, slices, slab, refused, s2, asked = G.form16(l, dataclasses.replace(G.NT_SPLIT_CASES[0], M=M, N=N, K=K, split_k=split))
+                if kernel == G.NT128:                   # (the caller's split as it stands)
+                    assert refused == 0 and slices == split and s2 * -(-M // 256) * -(-N // 256) < 200, (M, N, K, split)
+                else:
+                    assert refused == 0 and kernel == G.P8NT and slices == s2, (M, N, K, split)
+    assert G.form16(l, dataclasses.replace(G.NT_SPLIT_CASES[0], dyn_kind=2, bias=False))[0] == G.NT256
 
 
 def test_form_refusals_and_empty_problems():

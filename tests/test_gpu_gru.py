@@ -22,10 +22,12 @@ Largest error / yardstick seen on MI355X per kernel form (the RATIO lines these 
     one-step kernels (gru_first_step_fwd / bwd)                                   0.89 (n) / 0.42 (dgi)
 (the compact layout, phantom rows, a table-fed gi, dgi by position, spec, stagger and the slow path change no figure beyond the second digit.)
 Every 16-bit output was, bit for bit, the round-to-nearest-even bf16 of the fp32 output of the same launch.
+    team backward READING sv16 / hp16 (Case.in16), T = 2 / 4 / 2 PIPE / 4 PIPE               0.20 / 0.15 / 0.20 / 0.19 (dgh, dgi)
+Every such launch gave, bit for bit, the dgi / dgh / dh0 (dgi16 / dgh16) of the launch reading the same bf16 values as fp32 arrays; the fp32 team,
+reduce-scatter and register forms refuse the 16-bit inputs (gru_ref.IN16_TABLE) and leave every buffer as it was.
 
 Not reached by these hooks and left to the whole-step tests: njobs = 3, partial persistent launches (p_begin > 0), the ablation / stamp
-instantiations of the diagnostic build, the backward reading its saved gates / h_prev as bf16 (sv16 / hp16 as INPUTS), and the GRU cell inside
-decode.hip.
+instantiations of the diagnostic build, and the GRU cell inside decode.hip.
 
 Safety: one handle for the module, one launch per hook call; the kernels' spins are bounded (2 s) and the hook reports a time-out as a non-zero
 return.  The first unexpected non-zero return or failed synchronise sets a module latch, and every later case fails at once without launching."""
@@ -169,6 +171,13 @@ class Launch:
                     j[6], j[7] = out['sv%d' % k].data_ptr(), out['hp%d' % k].data_ptr()
             else:
                 j[6], j[7] = self.din['sv%d' % k].data_ptr(), self.din['hp%d' % k].data_ptr()
+                if 'sv' in c.in16:              # (GruArgs::sv16: the sv pointer itself holds bf16)
+                    j[6] = self.din['sv16_%d' % k].data_ptr()
+                if 'hp' in c.in16:              # the fp32 h_prev: not given (one job) or all NaN, to come back as it went (two jobs)
+                    j[9] = self.din['hp16_%d' % k].data_ptr()
+                    if c.njobs == 2:
+                        scratch['hp-nan%d' % k] = dev(G.nan32((self.rows.nrows + G.GUARD_ROWS, D)))
+                    j[7] = scratch['hp-nan%d' % k].data_ptr() if c.njobs == 2 else None
                 j[10] = self.din['dh_out'].data_ptr() + k * D * fb
                 j[11], j[12] = out['dgi'].data_ptr() + k * 3 * D * fb, out['dgh'].data_ptr() + k * 3 * D * fb
                 j[13] = out['dgi16'].data_ptr() + k * 3 * D * 2 if c.out16 else None
@@ -183,7 +192,7 @@ class Launch:
         r = self.drows
         shared = [r['lens'].data_ptr(), r['slens'].data_ptr() if c.skip else None, r['perm'].data_ptr() if c.skip else None,
                   r['map'].data_ptr() if c.cmp else None, scratch['xbuf'].data_ptr() if c.xbuf else None]
-        ints = c.shape_ints(self.rs_floats) + [c.stagger, c.force_slow, int(c.fwd and c.out16 and c.save), c.spec]
+        ints = c.shape_ints(self.rs_floats) + [c.stagger, c.force_slow, int((c.fwd and c.out16 and c.save) or (not c.fwd and 'sv' in c.in16)), c.spec]
         ints += [v for k in range(c.njobs) for v in (int(k == 1), int(c.by_pos))]
         for k, v in raw.items():
             kind, idx = k
@@ -208,6 +217,9 @@ class Launch:
         got = {k: v.cpu().numpy() for k, v in out.items()}
         left = {k: v.cpu().numpy() for k, v in scratch.items()}
         for k, v in left.items():           # scratch: whatever the launch leaves inside, nothing behind it
+            if k.startswith('hp-nan'):
+                assert np.array_equal(v.view(np.int32), G.nan32(v.shape).view(np.int32)), (c.id, '%s: an input was written' % k)
+                continue
             tail = v[nx:] if k == 'xbuf' else v[c.B:]
             assert (tail.view(np.int32) == G.SENT).all(), (c.id, '%s: written beyond its extent' % k)
         return got
@@ -292,6 +304,33 @@ def test_team_forms_16bit_outputs(gpu, c):
             assert np.array_equal(got[nm + '16'][m], G.bf16_rne(comp[nm][m])[0]), (c.id, '%s16 is not the bf16 rounding of the fp32 output' % nm)
         if c.dgh16_only:
             assert not bits_equal(got, comp, ['dgi'])
+
+
+@pytest.mark.parametrize('c', G.team_in16_cases(), ids=_ids)
+def test_team_backward_reads_16bit_saved_state(gpu, c):
+    """sv16 / hp16 as INPUTS (gru_team.hip: the 8-byte gate load at the halfword index, the 2-byte h_prev load).  Against the float64 recurrence on the
+    rounded values at the usual margin, and bit for bit the launch that gets the same values as fp32 arrays: widening bf16 is a shift, so everything
+    behind the load is the same arithmetic (the bias sums keep their bound: their LDS atomic order is free)"""
+    L = Launch(gpu, c)
+    got = L.run()
+    L.check(got)
+    plain = L.run(in16='')
+    L.check(plain, dataclasses.replace(c, in16=''))
+    assert not bits_equal(got, plain), (c.id, 'the launch reading bf16 sv / hp and the one reading the same values as fp32 differ in', bits_equal(got, plain))
+
+
+@pytest.mark.parametrize('in16', ['sv', 'hp'])
+@pytest.mark.parametrize('c,what', G.IN16_TABLE, ids=lambda v: v.id if isinstance(v, G.Case) else v)
+def test_which_backward_forms_take_16bit_saved_state(gpu, c, what, in16):
+    """every form a backward plan can have (gru_ref.IN16_TABLE): the bf16 team kernels read the 16-bit arrays, every other form refuses the launch and
+    leaves every buffer as it was -- none runs on and ignores them"""
+    L = Launch(gpu, dataclasses.replace(c, in16='sv+hp'))
+    if what == 'reached':
+        L.check(L.run(in16=in16), dataclasses.replace(c, in16=in16))
+    else:
+        got = L.run(expect_refusal=True, in16=in16)
+        assert not bits_equal(got, {k: L.before[k] for k in got}), (c.id, in16)
+        assert not [k for k in got if k.startswith('db') and not np.array_equal(got[k].view(np.int32), L.before[k].view(np.int32))], (c.id, in16)
 
 
 @pytest.mark.parametrize('fwd', [True, False], ids=['fwd', 'bwd'])

@@ -277,6 +277,50 @@ def test_forward_comparison_has_teeth(defect, kind, bf16):
             G.check_forward(c, rows, inp, before, got)
 
 
+@pytest.mark.parametrize('cmp', [False, True], ids=['padded', 'compact'])
+@pytest.mark.parametrize('defect', ['', 'sv16_index', 'hp16_next'])
+def test_backward_comparison_has_teeth_for_16bit_inputs(defect, cmp):
+    """Case.in16: the restatement reads its saved gates / h_prev out of the 16-bit buffers.  Clean, it passes and gives the bits of the same restatement on
+    the fp32 arrays (which hold the same rounded values); the gates fetched at the fp32 index, or h_prev of position p taken from p + 1, must fail"""
+    c = dataclasses.replace(G._team('teeth', False, 2, 64, skip='sorted', cmp=cmp, bf16=1, in16='sv+hp'), D=16, reach=None)
+    rows = G.make_rows(c, 4, 1)
+    inp = G.make_inputs(c, rows)
+    for k in range(c.njobs):
+        L = inp['log'][k]
+        assert np.array_equal(G.bf16_rne(L['sv'])[1], L['sv']) and np.array_equal(G.bf16_rne(L['hp'])[1], L['hp'])
+        read = G.read_mask(c, rows, k == 1)
+        for nm, w in (('sv', 4 * c.D), ('hp', c.D)):
+            buf = inp['%s16_%d' % (nm, k)]
+            assert np.array_equal(G.widen16(buf[rows.rowmap[read]]), L[nm].reshape(c.S, c.rows, w)[read])
+            assert (buf == G.NAN16).sum() == buf.size - int(read.sum()) * w            # NaN in the guard rows and wherever no step reads
+        assert cmp or not read.all()                    # the padded layout under a row order has positions no step reads
+    before = G.make_outputs(c, rows, inp)
+    got = G.run_backward(c, rows, inp, {k: v.copy() for k, v in before.items()}, defect=defect)
+    if not defect:
+        G.check_backward(c, rows, inp, before, got)
+        plain = G.run_backward(dataclasses.replace(c, in16=''), rows, inp, {k: v.copy() for k, v in before.items()})
+        assert all(G.same_bits(got[k], plain[k]) for k in got)
+    else:
+        with pytest.raises(AssertionError):
+            G.check_backward(c, rows, inp, before, got)
+
+
+def test_which_backward_forms_take_16bit_inputs():
+    """IN16_TABLE against the plan: 'reached' is the bf16 team form and nothing else (check_operands: the 16-bit operands need a team form that asked for
+    bf16); tests/test_gpu_gru.py launches every row of the table and holds the refused ones to 'nothing written'"""
+    seen = set()
+    for c, what in G.IN16_TABLE:
+        p = plan(c)
+        assert (p['form'], p['T'], p['C'], p['pipe']) == c.reach, (c.id, p)
+        assert (what == 'reached') == (p['form'] == 'team' and c.bf16 == 1), (c.id, p['form'])
+        seen.add((p['form'], c.bf16))
+    # every (form, bf16) a backward plan can have: team_rs is fp32 only (bf16 plans the team form), the item form is forward only
+    assert seen == {('team', 1), ('team', 0), ('team_rs', 0), ('persistent', 1), ('stepwise', 1)}
+    assert plan(dataclasses.replace(G._team('x', False, 2, 64, bwd_rs=1), bf16=1))['form'] == 'team'
+    for c in G.team_in16_cases():
+        assert c.bf16 == 1 and not c.fwd and c.reach[0] == 'team' and c.in16 in ('sv', 'hp', 'sv+hp')
+
+
 @pytest.mark.parametrize('bf16', [0, 1])
 @pytest.mark.parametrize('defect,kind', TEETH_BWD)
 def test_backward_comparison_has_teeth(defect, kind, bf16):
