@@ -109,6 +109,11 @@ struct avae_ctx {
     // arrived is read; it only ever decides the LAYOUT, never a value) and the padded positions of the call that issued the copy
     int32_t* hint_dev = nullptr; volatile int32_t* hint_host = nullptr;
     const int32_t *cnt_src = nullptr, *cnt_tgt = nullptr;     // present-id counts of the last forward (table-fed layers), device
+    // The route of the last avae_forward_backward (avae_debug_step_route), noted by the step where it decides (note_gru, model.cpp): the first
+    // layers table-fed (use_table), Ws::compact / compact_d / Bx, the BPTT form rs_pick gave, whether the top encoder layer ran its one-job
+    // launch + the one-step kernels (top_one_step), and per kind of GRU launch (RouteGru) the plan it ran as form, T, C, pipe, ring (form -1:
+    // no such launch).  live: a step is being enqueued -- the other callers of the same pieces (encode, eval, score) note nothing.
+    struct Route { bool live = false; int tab_src = -1, tab_tgt = -1, compact = -1, compact_d = -1, Bx = -1, rs = -1, top1 = -1; int gru[6][5] = {}; } route;
 };
 
 #pragma GCC visibility push(hidden)
@@ -310,6 +315,18 @@ inline PrepArgs prep_from_ws(const Ws& w)
     p.src_tm = w.src_tm; p.lens_src = w.lens_src; p.lens_tgt = w.lens_tgt; p.lead = w.lead; p.gold = w.gold;
     p.rank = w.rank; p.cidx = w.cidx; p.ntok = w.ntok; p.chunk_counts = w.ntok + 4;
     return p;
+}
+
+// the kinds of GRU launch a step makes (avae_ctx::Route::gru): the encoder's two-direction launches, the top encoder layer's one-job
+// launches (top_one_step), the decoder's
+enum RouteGru { kRouteEncFwd, kRouteEncBwd, kRouteTopFwd, kRouteTopBwd, kRouteDecFwd, kRouteDecBwd };
+// notes the plan of the launch the step is about to make: gru_plan on the very arguments gru_forward / gru_backward get
+inline void note_gru(avae_ctx* h, int kind, const GruArgs& a, bool fwd)
+{
+    if (!h->route.live) return;
+    const GruPlan p = gru_plan(a, fwd, h->persistent != 0);
+    const int v[5] = {(int)p.form, p.T, p.C, p.pipe ? 1 : 0, p.ring};
+    std::copy(v, v + 5, h->route.gru[kind]);
 }
 
 // ---- handle.cpp

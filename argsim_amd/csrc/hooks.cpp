@@ -121,6 +121,22 @@ int avae_debug_present_ids(avae_handle h, int32_t out[2])
     if (h->cnt_tgt) AV_CHECK(hipMemcpy(&out[1], h->cnt_tgt, sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
+// test hook: the route the LAST avae_forward_backward took, as the step noted it where it decided (avae_ctx::Route; every value -1 where no
+// step has run).  out = source first layer table-fed, target first layer table-fed (use_table), Ws::compact, Ws::compact_d, Ws::Bx, the BPTT
+// form taken (rs_pick: 0 gather, 1 reduce-scatter -- with bwd_rs = 2 the automatic choice), the top encoder layer as one-job launches + the
+// one-step kernels (top_one_step); then form, T, C, pipe, ring (gru_plan on the arguments that were launched; form -1: no such launch) for the
+// encoder's two-direction forward and backward, the top encoder layer's one-job forward and backward, the decoder's forward and backward.
+// Reads host memory only: no launch, no synchronisation.
+int avae_debug_step_route(avae_handle h, int32_t out[37])
+{
+    if (!h || !out) return 1;
+    const avae_ctx::Route& r = h->route;
+    const int32_t v[7] = {r.tab_src, r.tab_tgt, r.compact, r.compact_d, r.Bx, r.rs, r.top1};
+    std::copy(v, v + 7, out);
+    for (int k = 0; k < 6; ++k)
+        for (int f = 0; f < 5; ++f) out[7 + 5 * k + f] = r.tab_src < 0 ? -1 : r.gru[k][f];
+    return 0;
+}
 // test hook: the per-token cross-entropy (model.py:180 loss_gen_samp) of the LAST avae_forward_backward / avae_train_step -- the
 // TRAIN forward, word dropout and the latent draw live -- copied to out (device memory, max_n floats); *n_out = its token count.
 // (The workspace layout is a pure function of the call geometry, so the array is found again without keeping a pointer.)

@@ -522,6 +522,7 @@ static int run_encoder(avae_ctx* h, Ws& w, int B, int Ss, bool save)
         attach_order(h, w, a, true, top1 ? 1 : 0);
         a.rowmap = cmap;
         a.spec = spec_pick(h);
+        note_gru(h, top1 ? kRouteTopFwd : kRouteEncFwd, a, true);
         { Timed t(h, 1, 2.0 * a.njobs * Ss * (double)B * D * 3 * D);
           DeviceTurn turn(h);
           AV_GRU(gru_forward(h->stream, a, h->persistent != 0)); }
@@ -603,6 +604,7 @@ int run_decoder_rnn(avae_ctx* h, Ws& w, int B, int T, const float* state_in, int
         if (T > 1) attach_order(h, w, a, true, 2);
         a.rowmap = cmap;
         a.spec = spec_pick(h);
+        note_gru(h, kRouteDecFwd, a, true);
         { Timed t(h, 1, 2.0 * T * (double)B * D * 3 * D);
           DeviceTurn turn(h);
           AV_GRU(gru_forward(h->stream, a, h->persistent != 0)); }
@@ -623,10 +625,15 @@ static int forward(avae_ctx* h, Ws& w, const int32_t* src, const int32_t* tgt, i
     AV_CHECK(prep_ids(h->stream, p));
     AV_TRY(build_row_orders(h, w, B, Ss, T, true));
     AV_TRY(build_compact(h, w, B, Ss, T, train));
+    const bool tab_t = use_table(h, rt, B);
+    if (h->route.live) {
+        avae_ctx::Route& r = h->route;
+        r.tab_src = use_table(h, Ss * B, B); r.tab_tgt = tab_t; r.compact = w.compact; r.compact_d = w.compact_d; r.Bx = w.Bx; r.top1 = top_one_step(h);
+    }
     AV_TRY(run_encoder(h, w, B, Ss, train));
     AV_TRY(run_latent(h, w, B, train, seed, eps));
     AV_TRY(gemm(h, nn(w.z, R, h->P + h->oWex, D, w.h0, D, B, D, R).biased(h->P + h->oBex).batch_rows()));
-    if (use_table(h, rt, B)) AV_TRY(run_decoder_rnn(h, w, B, T, w.h0, 0, train, w.lead, w.compact_d));
+    if (tab_t) AV_TRY(run_decoder_rnn(h, w, B, T, w.h0, 0, train, w.lead, w.compact_d));
     else {
         AV_CHECK(embed_gather(h->stream, h->P + h->oE, w.lead, w.emb_tgt, rt, D, V));
         AV_TRY(run_decoder_rnn(h, w, B, T, w.h0, 0, train));
@@ -742,6 +749,8 @@ static int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
         a.rowmap = dmap;
         if (dmap && i == 0) j.dgi_by_pos = 1;       // (table-fed: its gate gradients are summed by token id)
         a.bwd_rs = rs_pick(h); a.spec = spec_pick(h);
+        if (h->route.live) h->route.rs = a.bwd_rs;
+        note_gru(h, kRouteDecBwd, a, false);
         hook_fence(h);
         { Timed t(h, 2, 2.0 * T * (double)B * D * 3 * D);
           DeviceTurn turn(h);
@@ -836,6 +845,7 @@ static int backward(avae_ctx* h, Ws& w, int B, int Ss, int St, float b_global)
         a.rowmap = cmap;
         if (cmap && i == 0) for (int d = 0; d < a.njobs; ++d) a.job[d].dgi_by_pos = 1;      // (table-fed: its gate gradients are summed by token id)
         a.bwd_rs = rs_pick(h); a.spec = spec_pick(h);
+        note_gru(h, top1 ? kRouteTopBwd : kRouteEncBwd, a, false);
         hook_fence(h);
         { Timed t(h, 2, 2.0 * a.njobs * (Ss - 1) * (double)B * D * 3 * D);
           DeviceTurn turn(h);
@@ -952,6 +962,10 @@ int avae_forward_backward(avae_handle h, const int32_t* src, const int32_t* tgt,
     Ws w;
     AV_TRY(get_ws(h, w, B, Ss, St, true));
     h->B = B; h->Ss = Ss; h->St = St;
+    h->route = avae_ctx::Route{};
+    for (auto& g : h->route.gru) g[0] = -1;
+    struct Noting { avae_ctx* h; ~Noting() { h->route.live = false; } } noting{h};      // (the route is noted while THIS call enqueues, whichever way it returns)
+    h->route.live = true;
     AV_TRY(forward(h, w, src, tgt, B, Ss, St, true, seed, keep_mask, eps, n_tok_global > 0.f ? 1.f / n_tok_global : 0.f));
     AV_TRY(backward(h, w, B, Ss, St, b_global));
     if (h->persistent && !h->first_step_checked) {

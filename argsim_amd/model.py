@@ -201,6 +201,15 @@ class VAE:
         self._ck(self._l.avae_debug_present_ids(self._h, out))
         return int(out[0]), int(out[1])
 
+    def step_route(self):
+        """the route the last forward_backward / train_step took, as the step noted it (test hook avae_debug_step_route) -> dict:
+        table (src, tgt) first layers table-fed, compact (encoder, decoder), Bx, bwd_rs (the BPTT form taken: 0 gather, 1
+        reduce-scatter), top1 (the top encoder layer as one-job launches + the one-step kernels) and, per kind of GRU launch
+        (ROUTE_GRU), the plan it ran as (form, T, C, pipe, ring) or None where the step makes no such launch"""
+        out = (C.c_int32 * ROUTE_INTS)()
+        self._ck(self._l.avae_debug_step_route(self._h, out))
+        return route_dict(list(out))
+
     def train_ce(self, max_n=1 << 22):
         """per-token cross-entropy (loss_gen_samp, model.py:180) of the last forward_backward / train_step: the TRAIN forward,
         dropout and the latent draw live (test hook)"""
@@ -662,6 +671,23 @@ class VAE:
         -> dict(labels, centers, inertia, n_iter, stop, best, inertias, relocations) (argsim_amd/kmeans.py)"""
         from . import kmeans
         return kmeans.kmeans(self, z, k, metric, n_init, max_iter, tol, seed, init, return_all)
+
+
+# avae_debug_step_route: seven scalars, then (form, T, C, pipe, ring) per kind of GRU launch, in this order
+ROUTE_GRU = ('enc_fwd', 'enc_bwd', 'top_fwd', 'top_bwd', 'dec_fwd', 'dec_bwd')
+ROUTE_INTS = 7 + 5 * len(ROUTE_GRU)
+
+
+def route_dict(v):
+    """the ints of avae_debug_step_route as VAE.step_route() returns them (no device needed)"""
+    if len(v) != ROUTE_INTS:
+        raise ValueError("a step route is %d ints, got %d" % (ROUTE_INTS, len(v)))
+    v = [int(x) for x in v]
+    r = dict(table=(v[0], v[1]), compact=(v[2], v[3]), Bx=v[4], bwd_rs=v[5], top1=v[6])
+    for i, k in enumerate(ROUTE_GRU):
+        g = tuple(v[7 + 5 * i:12 + 5 * i])
+        r[k] = None if g[0] < 0 else g
+    return r
 
 
 KNN_METRICS = {'dot': 0, 'cos': 1, 'euc': 2}

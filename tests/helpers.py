@@ -51,6 +51,11 @@ def big_extras(name):
 
 def make_case(name, seed=0, pad=2, bias_scale=0.1):
     kw, B, S, lens = (CASES.get(name) or PROD_CASES.get(name) or BIG_CASES[name][:4])
+    return make_batch(kw, B, S, lens, seed, pad, bias_scale)
+
+
+def make_batch(kw, B, S, lens, seed=0, pad=2, bias_scale=0.1):
+    """the batch of make_case for a geometry that is in none of the tables above (tests/step_routes.py)"""
     cfg = vn.make_cfg(**kw)
     rng = np.random.default_rng(seed + 17)
     V, R = cfg['dim_tgt'], cfg['dim_rep']
@@ -87,6 +92,48 @@ def rel_l2(a, b):
     b = np.asarray(b, np.float64).ravel()
     d = np.linalg.norm(b)
     return np.linalg.norm(a - b) / (d if d > 0 else 1.0)
+
+
+def grad_blocks(got, want, tol, rows=16):
+    """the per-block gradient criterion: a variable flattened to (shape[0], -1) and cut into blocks of `rows` leading rows (16 rows = one
+    hidden tile of one gate in the natural layout get_grads() returns; a bias vector: 16 elements) -> (err, bound) per block,
+    err = |got_blk - want_blk|, bound = tol * max(|want_blk|, |want| * sqrt(blk.size / want.size)): the tolerance relative to the block's
+    own norm or to its fair share of the variable's norm, whichever is larger.  Where the reference is exactly zero the bound is zero."""
+    got = np.asarray(got, np.float64)
+    want = np.asarray(want, np.float64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    got, want = got.reshape(want.shape[0], -1), want.reshape(want.shape[0], -1)
+    edges = np.arange(0, want.shape[0], rows)
+    err = np.sqrt(np.add.reduceat(((got - want) ** 2).sum(1), edges))
+    blk = np.sqrt(np.add.reduceat((want ** 2).sum(1), edges))
+    size = np.diff(np.append(edges, want.shape[0])) * want.shape[1]
+    return err, tol * np.maximum(blk, np.linalg.norm(want) * np.sqrt(size / want.size))
+
+
+def grad_blocks_bad(got, want, tol, rows=16):
+    """-> [(block index, err, bound)] of the blocks of grad_blocks that miss their bound (a non-finite error misses it)"""
+    err, bound = grad_blocks(got, want, tol, rows)
+    return [(int(i), float(err[i]), float(bound[i])) for i in np.flatnonzero(~(err <= bound))]
+
+
+def grad_blocks_ratio(got, want, tol, rows=16):
+    """the worst err / bound over the blocks of grad_blocks (0 / 0 = 0, x / 0 = inf: an exact zero of the reference must be an exact zero)"""
+    err, bound = grad_blocks(got, want, tol, rows)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        r = np.where(err == 0, 0.0, err / bound)
+    return float(np.max(np.where(np.isnan(r), np.inf, r)))
+
+
+def grads_bad(got, want, tol):
+    """every variable of a gradient set through grad_blocks_bad: 16-row blocks, and single rows (one token id each) for the embedding
+    -> {(name, rows): [(block, err, bound)]} of the variables with a bad block"""
+    bad = {}
+    for k in want:
+        for rows in ((16, 1) if k == 'embed/embedding' else (16,)):
+            b = grad_blocks_bad(got[k], want[k], tol, rows)
+            if b:
+                bad[(k, rows)] = b[:8]
+    return bad
 
 
 def ce_scale(inv_n, n_dev, n_max):
