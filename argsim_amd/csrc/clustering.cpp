@@ -1,6 +1,6 @@
 // clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
 // (kernels: ward.hip), of avae_affinity (kernels: affinity.hip), of avae_tsne (kernels: tsne.hip, the distances affinity.hip's) and of
-// avae_kmeans (kernels: kmeans.hip).
+// avae_kmeans (kernels: kmeans.hip), and of avae_silhouette (kernels: silhouette.hip).
 // Contract: include/argsim_vae.h.
 #include "ctx.h"
 
@@ -269,6 +269,63 @@ int avae_kmeans(avae_handle h, const float* x, int32_t N, int32_t dim, const ava
     // every iteration is enqueued; a launch that finds the restart's stop decided returns at once.  Never a synchronisation
     for (int it = 0; it < kc->max_iter; ++it) AV_CHECK(km_iteration(h->stream, a, it));
     AV_CHECK(km_finish(h->stream, a, label, centers, stat, inertia, label_all, centers_all, stat_all));
+    return 0;
+}
+
+int avae_silhouette(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_silhouette_config* sc, const int32_t* label, const int32_t* K,
+                    double* score, double* sil, double* ab, int32_t* nearest, int32_t* count, double* cluster_mean, double* index)
+{
+    if (!h) return 1;
+    if (!sc) return fail(h, "silhouette config is null");
+    if (!x) return fail(h, "silhouette: x is null");
+    if (!label) return fail(h, "silhouette: label is null");
+    if (!K) return fail(h, "silhouette: K is null");
+    if (!score) return fail(h, "silhouette: score is null");
+    if (N < 2 || N > kSilMaxN) return fail(h, "silhouette: N must be in [2, 2^18]");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "silhouette: dim must be a multiple of 4 in [4, 1024]");
+    if (sc->L < 1 || sc->L > kSilMaxL) return fail(h, "silhouette: L must be in [1, 64]");
+    for (int l = 0; l < sc->L; ++l)
+        if (K[l] < 1 || K[l] > kSilMaxK) return fail(h, "silhouette: K[" + std::to_string(l) + "] must be in [1, 4096]");
+    if (sc->metric < 0 || sc->metric > 2) return fail(h, "silhouette: metric must be 0 (euclidean), 1 (cosine) or 2 (squared euclidean)");
+    if ((uintptr_t)x & 15) return fail(h, "silhouette: x must be 16-byte aligned");
+    if (sc->reserved != 0 || sc->reserved2 != 0) return fail(h, "silhouette: the reserved fields must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    int cus = 0, lds = 0;
+    AV_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    AV_CHECK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+    if (lds < kSilLds) return fail(h, "silhouette: the device gives a workgroup less than the 160 KiB of LDS the pair pass is planned for");
+    // Workspace, every buffer on a 256-byte boundary: K and its prefix sums (2 L + 1) int, the member counts (sum K) int, with
+    // the cosine the row norms (N), the silhouette values (L, N) unless the caller gives sil; with index the member sums (sum K, dim), the
+    // labelled rows' mean (L, dim), a row's squared distance to its cluster's mean and the root (L, N) each, S_c and the largest R (sum K)
+    // each, (L, 4) traces and counts
+    const size_t n = (size_t)N, L = (size_t)sc->L, d = (size_t)dim;
+    std::vector<int> meta(2 * L + 1);
+    int kmax = 0;
+    meta[L] = 0;
+    for (size_t l = 0; l < L; ++l) { meta[l] = K[l]; meta[L + l + 1] = meta[L + l] + K[l]; kmax = std::max(kmax, (int)K[l]); }
+    const size_t sumk = (size_t)meta[2 * L];
+    SilArgs a{};
+    a.x = x; a.label = label; a.N = N; a.dim = dim; a.L = sc->L; a.metric = sc->metric; a.Kmax = kmax; a.ab = ab; a.nearest = nearest;
+    int* dmeta = nullptr; double* rnorm = nullptr;
+    AV_TRY(place_ws(h, "silhouette", [&](Bump& b) {
+        dmeta = b.take<int>(2 * L + 1);
+        a.cnt = b.take<int>(sumk);
+        rnorm = b.opt<double>(sc->metric == 1, n);
+        a.s = sil ? sil : b.take<double>(L * n);
+        if (index) {
+            a.msum = b.take<double>(sumk * d); a.gmean = b.take<double>(L * d);
+            a.e = b.take<double>(L * n); a.r = b.take<double>(L * n);
+            a.Sc = b.take<double>(sumk); a.dbp = b.take<double>(sumk); a.tr = b.take<double>(4 * L);
+        }
+    }));
+    a.meta = dmeta; a.rnorm = rnorm;
+    const SilPlan plan = sil_plan(N, dim, sc->L, K, h->sil_chunk, cus);
+    AV_CHECK(hipMemcpyAsync(dmeta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    AV_CHECK(hipMemsetAsync(a.cnt, 0, sumk * sizeof(int), h->stream));
+    AV_CHECK(sil_prepare(h->stream, a));
+    AV_CHECK(sil_pairs(h->stream, a, plan));
+    AV_CHECK(sil_scores(h->stream, a, score, count, cluster_mean));
+    if (index) AV_CHECK(sil_indices(h->stream, a, index));
     return 0;
 }
 

@@ -486,4 +486,17 @@ int avae_debug_latent_plan(int kind, int64_t n, int64_t N, int k_or_P, int dim, 
     return 0;
 }
 
+// test hook: sil_plan(N, dim, L, K, chunk_opt, cus) of avae_silhouette; out = TI, TJ, the number of passes, the LDS limit, the staging
+// bytes of the first pass, then per pass its first labeling and its LDS bytes (2 L + 5 values at most).  Host arithmetic only: callable
+// without a GPU.
+int avae_debug_sil_plan(int32_t N, int32_t dim, int32_t L, const int32_t* K, int32_t chunk_opt, int32_t cus, int32_t* out)
+{
+    if (!K || !out || N < 2 || N > kSilMaxN || L < 1 || L > kSilMaxL || chunk_opt < 0 || cus < 1) return 1;
+    for (int l = 0; l < L; ++l) if (K[l] < 1 || K[l] > kSilMaxK) return 1;
+    const SilPlan p = sil_plan(N, dim, L, K, chunk_opt, cus);
+    out[0] = p.TI; out[1] = p.TJ; out[2] = p.npass; out[3] = kSilLds; out[4] = (int32_t)sil_staging(p.TI, p.begin[1] - p.begin[0]);
+    for (int q = 0; q < p.npass; ++q) { out[5 + 2 * q] = p.begin[q]; out[6 + 2 * q] = p.bytes[q]; }
+    return 0;
+}
+
 }  // extern "C"

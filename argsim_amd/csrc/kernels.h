@@ -551,6 +551,37 @@ hipError_t km_iteration(hipStream_t st, const KmArgs& a, int it);        // seve
 hipError_t km_finish(hipStream_t st, const KmArgs& a, int32_t* label, float* centers, int32_t* stat, double* inertia, int32_t* label_all,
                      double* centers_all, int32_t* stat_all);
 
+// ---------------------------------------------------------------- cluster-quality scores of latent rows (silhouette.hip)
+// One set of N rows and L labelings per call (contract: include/argsim_vae.h, avae_silhouette).  Every buffer is workspace laid out by
+// the caller (clustering.cpp) or the caller's own output; the counts are zero-filled before the first launch.
+constexpr int kSilMaxN = 1 << 18, kSilMaxK = 4096, kSilMaxL = 64;
+constexpr int kSilLds = 160 * 1024;   // the LDS one workgroup may take on gfx950
+constexpr int kSilTJ = 64;            // columns of a tile of the pair pass
+constexpr int kSilDK = 32;            // row elements per LDS stage
+// TI rows x TJ columns per tile; the labelings [begin[p], begin[p + 1]) form pass p, whose launch takes bytes[p] of LDS
+struct SilPlan { int TI, TJ, npass; int begin[kSilMaxL + 1]; int bytes[kSilMaxL]; };
+struct SilArgs {
+    const float* x; const double* rnorm;      // rows; their norms (cosine) or null
+    const int32_t* label;             // (L, N)
+    const int* meta;                  // K (L), then the prefix sums of K (L + 1): where a labeling's clusters start in the (sum K) buffers
+    int N, dim, L, metric, Kmax;
+    int* cnt;                         // (sum K) members
+    double* s;                        // (L, N) silhouette values: the caller's sil, or workspace
+    double* ab; int32_t* nearest;     // (L, N, 2), (L, N) or null
+    // CH and DB only
+    double *msum, *gmean;             // (sum K, dim) member sums, then means; (L, dim) the mean of the labelled rows
+    double *e, *r;                    // (L, N) squared distance of a row to its cluster's mean, and its root
+    double *Sc, *dbp;                 // (sum K) mean distance to the mean; the largest R of a cluster
+    double* tr;                       // (L, 4) trW, trB, non-empty clusters, labelled rows
+};
+// staging bytes of a pass of nl labelings at TI rows (the bins come on top: TI x sum K x 8)
+size_t sil_staging(int TI, int nl);
+SilPlan sil_plan(int N, int dim, int L, const int32_t* K, int chunk_opt, int cus);
+hipError_t sil_prepare(hipStream_t st, const SilArgs& a);                  // row norms (cosine), the counts
+hipError_t sil_pairs(hipStream_t st, const SilArgs& a, const SilPlan& p);  // one launch per pass: s, ab, nearest
+hipError_t sil_scores(hipStream_t st, const SilArgs& a, double* score, int32_t* count, double* cluster_mean);
+hipError_t sil_indices(hipStream_t st, const SilArgs& a, double* index);   // six launches: CH and DB
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

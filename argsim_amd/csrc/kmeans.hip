@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "reduce_dev.h"
 #include "row_parts.h"
+#include "rows_dev.h"
 
 #include <algorithm>
 
@@ -28,24 +29,8 @@ namespace {
 
 constexpr int kDK = 32;            // columns per LDS stage
 
-__device__ __forceinline__ double row_value(float v, double rn) { return rn < 0.0 ? (double)v : (rn > 0.0 ? (double)v / rn : 0.0); }
 // the norm of row i, or -1 where the rows are taken as they are
 __device__ __forceinline__ double row_norm(const KmArgs& a, long long i) { return a.rnorm ? a.rnorm[i] : -1.0; }
-
-// the sum of one double per thread over the NW waves of the workgroup, in every thread: the xor butterfly of a wave, then the waves in
-// ascending order.  sh: NW doubles; ends in a barrier
-template <int NW>
-__device__ __forceinline__ double block_sum(double v, double* sh)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = sh[0];
-    for (int w = 1; w < NW; ++w) s += sh[w];
-    __syncthreads();
-    return s;
-}
 
 // exclusive prefix of one value per thread in thread order, and the total: a shuffle scan per wave, then the waves before this one in
 // ascending order.  sh: NW values; ends in a barrier
@@ -78,20 +63,13 @@ __device__ __forceinline__ int block_min_int(int v, int* sh, int nw)
     return s;
 }
 
-// one wave per row: the double sum of squares, lane l over elements 4 l .. 4 l + 3, 256 + 4 l .. in index order, then the xor butterfly
+// one wave per row: its norm (rows_dev.h)
 __global__ __launch_bounds__(256) void km_rownorm_kernel(const float* __restrict__ x, int N, int dim, double* __restrict__ rn)
 {
-    const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= N) return;
-    double s = 0.0;
-    for (int c = lane * 4; c < dim; c += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(x + row * dim + c);
-        s += (double)v.x * v.x; s += (double)v.y * v.y; s += (double)v.z * v.z; s += (double)v.w * v.w;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if (lane == 0) rn[row] = sqrt(s);
+    const double v = wave_row_norm(x, row, dim);
+    if ((threadIdx.x & 63) == 0) rn[row] = v;
 }
 
 // column sums over a run of rows: mode 0 of the values, mode 1 of their squared deviation from mean; thread t owns columns t, t + 256 ..

@@ -7,6 +7,7 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
     python -m argsim_amd.eval_explore --inputs data/test_data_emb.npy --labels data/test_labels.npy \\
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
         [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]] [--kmeans K [--kmeans-init 10]]
+        [--quality] [--sweep LO:HI[:STEP]]
 
 With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
 device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
@@ -15,7 +16,12 @@ The labels are eval_cluster's topic-stance-reason strings; the topics are listed
 topic, then share|members|cluster for the clusters of which at least half the members (and at least two) belong to the topic.
 
 With --kmeans K the same runs follow with k-means into K clusters (VAE.kmeans: k-means++ seeding, the best of --kmeans-init restarts, ONE
-device call each), the same lines per run and the columns cls_km_* / dist_km_* in the CSV.  Without it nothing changes."""
+device call each), the same lines per run and the columns cls_km_* / dist_km_* in the CSV.  Without it nothing changes.
+
+With --quality every run that was made is followed by one line "silhouette %.4f  CH %.2f  DB %.4f": the silhouette score, the
+Calinski-Harabasz and the Davies-Bouldin index of its clusters on its own metric (VAE.silhouette, ONE device call).  With --sweep LO:HI[:STEP]
+the table "k silhouette CH DB" of k-means for every k of the range follows per input and metric (VAE.sweep_k: one k-means call per k, ONE
+silhouette call over all of them), the k with the largest silhouette marked with *.  Without the two flags the output is what it was."""
 import argparse
 import csv
 
@@ -37,9 +43,28 @@ def purity_lines(pred, topics, order):
     return lines + ["%d clusters" % len(set(np.asarray(pred).tolist()))]
 
 
-def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10):
+def quality_line(vae, x, pred, metric):
+    """the line of --quality for one run; a run with one cluster, or with as many as rows, has no scores"""
+    try:
+        q = vae.silhouette(x, np.asarray(pred, np.int64), metric)
+    except ValueError:
+        return "silhouette n/a (%d clusters)" % len(set(np.asarray(pred).tolist()))
+    return "silhouette %.4f  CH %.2f  DB %.4f" % (q['score'], q['ch'], q['db'])
+
+
+def sweep_lines(vae, x, name, metric, ks, n_init, seed):
+    """the table of --sweep for one input and metric"""
+    t = vae.sweep_k(x, ks, metric, n_init=n_init, seed=seed)
+    lines = ["sweep %s" % name, "k silhouette CH DB"]
+    for k, s, ch, db in zip(t['k'], t['score'], t['ch'], t['db']):
+        lines.append("%d %.4f %.2f %.4f%s" % (k, s, ch, db, " *" if k == t['best'] else ""))
+    return lines
+
+
+def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10, quality=False, sweep=None):
     """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed.  kmeans = k adds the
-    same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*"""
+    same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*.  quality: a line of scores behind
+    every run; sweep = [k ..]: the k-means quality table per input and metric"""
     from . import affinity
     from .eval_cluster import split_labels
     topics = np.array([p[0] for p in split_labels(labels)])
@@ -53,6 +78,8 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_ini
         if not res['converged']:
             lines.append("%s: did not converge in %d iterations" % (name, res['n_iter']))
         lines += purity_lines(res['labels'], topics, order)
+        if quality:
+            lines.append(quality_line(vae, x, res['labels'], metric))
         cols['cls_' + name] = res['labels']
         cols['dist_' + name] = affinity.dist_to_centroids(x, res['labels'], dist)
     for name, metric, dist, sampled in RUNS if kmeans else ():
@@ -63,8 +90,14 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_ini
         if res['stop'] == 'max_iter':
             lines.append("km_%s: stopped after %d iterations" % (name, res['n_iter']))
         lines += purity_lines(res['labels'], topics, order)
+        if quality:
+            lines.append(quality_line(vae, x, res['labels'], metric))
         cols['cls_km_' + name] = res['labels']
         cols['dist_km_' + name] = affinity.dist_to_centroids(x, res['labels'], dist)
+    for name, metric, dist, sampled in RUNS if sweep else ():
+        x = z_sp if sampled else z
+        if x is not None:
+            lines += sweep_lines(vae, x, name, metric, sweep, kmeans_init, seed)
     return cols, lines
 
 
@@ -97,6 +130,20 @@ def _positive(text):
     return v
 
 
+def _sweep(text):
+    """LO:HI[:STEP] -> [LO, LO + STEP .. <= HI]"""
+    try:
+        parts = [int(v) for v in text.split(':')]
+    except ValueError:
+        parts = []
+    if len(parts) not in (2, 3) or parts[0] < 2 or parts[1] < parts[0] or (len(parts) == 3 and parts[2] < 1):
+        raise argparse.ArgumentTypeError("must be LO:HI[:STEP] with 2 <= LO <= HI and STEP >= 1, got %r" % (text,))
+    ks = list(range(parts[0], parts[1] + 1, parts[2] if len(parts) == 3 else 1))
+    if len(ks) > 64:
+        raise argparse.ArgumentTypeError("at most 64 values of k per sweep, got %d" % len(ks))
+    return ks
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--inputs', required=True, help=".npy (n, dim) float32 embeddings (eval_embed's output)")
@@ -111,6 +158,8 @@ def build_parser():
     ap.add_argument('--tsne-iter', type=int, default=20000)
     ap.add_argument('--kmeans', type=_positive, default=None, help="also cluster with k-means into this many clusters (VAE.kmeans)")
     ap.add_argument('--kmeans-init', type=_positive, default=10, help="with --kmeans: restarts, the best of which is listed")
+    ap.add_argument('--quality', action='store_true', help="a line of silhouette, CH and DB behind every run (VAE.silhouette)")
+    ap.add_argument('--sweep', type=_sweep, default=None, help="LO:HI[:STEP]: the k-means quality table for these k per input and metric (VAE.sweep_k)")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -129,7 +178,7 @@ def main(argv=None):
     vae = make_vae(A.device)
     if A.tsne:
         print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
-    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init)
+    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init, A.quality, A.sweep)
     for line in lines:
         print(line)
     if A.csv:

@@ -90,6 +90,9 @@ class AvaeKmeansConfig(C.Structure):
     _fields_ = [('k', C.c_int32), ('n_init', C.c_int32), ('max_iter', C.c_int32), ('metric', C.c_int32), ('init', C.c_int32),
                 ('reserved', C.c_int32), ('tol', C.c_double), ('seed', C.c_uint64)]
 
+class AvaeSilhouetteConfig(C.Structure):
+    _fields_ = [('metric', C.c_int32), ('L', C.c_int32), ('reserved', C.c_int32), ('reserved2', C.c_int32)]
+
 
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
@@ -135,6 +138,7 @@ SIGNATURES = {
     'avae_affinity': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeAffinityConfig), _P, _P, _P, _P, _P]),
     'avae_tsne': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeTsneConfig)] + [_P] * 10),
     'avae_kmeans': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeKmeansConfig)] + [_P] * 8),
+    'avae_silhouette': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSilhouetteConfig), _P, C.POINTER(C.c_int32)] + [_P] * 7),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),
@@ -166,6 +170,7 @@ SIGNATURES = {
     'avae_debug_gru_plan': (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     'avae_debug_decode_plan': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'avae_debug_gru': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
+    'avae_debug_sil_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     'avae_bucket_count': (C.c_int, [_P]),
     'avae_bucket_info': (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }

@@ -21,6 +21,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) affinity propagation of latent rows          -> VAE.affinity(z, metric, ...) / affinity(vae, z, ...)
     (new) k-means of latent rows                       -> VAE.kmeans(z, k, metric, ...) / kmeans(vae, z, k, ...)
     (new) exact t-SNE of latent rows                   -> VAE.tsne(z, perplexity, ...) / tsne(vae, z, ...)
+    (new) silhouette, CH and DB of many labelings      -> VAE.silhouette(z, labels, metric) / VAE.sweep_k(z, ks) / silhouette(vae, z, ...)
 """
 import ctypes as C
 
@@ -672,6 +673,19 @@ class VAE:
         from . import kmeans
         return kmeans.kmeans(self, z, k, metric, n_init, max_iter, tol, seed, init, return_all)
 
+    def silhouette(self, z, labels, metric='euclidean', return_samples=False):
+        """sklearn's silhouette_score, calinski_harabasz_score and davies_bouldin_score of the rows of z for every labeling in labels,
+        (N,) or (L, N) integers with negative = left out, in ONE device call that forms every pair distance once (include/argsim_vae.h,
+        avae_silhouette).  metric: 'euclidean', 'cosine' or 'sqeuclidean'
+        -> dict(score, ch, db, n_clusters, counts, clusters[, samples, a, b, nearest]) (argsim_amd/silhouette.py)"""
+        from . import silhouette
+        return silhouette.silhouette(self, z, labels, metric, return_samples)
+
+    def sweep_k(self, z, ks, metric='euclidean', n_init=10, seed=0):
+        """one kmeans call per k in ks, then ONE silhouette call over all the labelings -> dict(k, score, ch, db, inertia, labels, best)"""
+        from . import silhouette
+        return silhouette.sweep_k(self, z, ks, metric, n_init, seed)
+
 
 # avae_debug_step_route: seven scalars, then (form, T, C, pipe, ring) per kind of GRU launch, in this order
 ROUTE_GRU = ('enc_fwd', 'enc_bwd', 'top_fwd', 'top_bwd', 'dec_fwd', 'dec_bwd')
@@ -929,3 +943,8 @@ def _check_kmeans_args(z, k, metric='euclidean', n_init=10, max_iter=300, tol=1e
 def kmeans(vae, z, k, metric='euclidean', n_init=10, max_iter=300, tol=1e-4, seed=0, init='k-means++', return_all=False):
     """functional form of VAE.kmeans"""
     return vae.kmeans(z, k, metric, n_init, max_iter, tol, seed, init, return_all)
+
+
+def silhouette(vae, z, labels, metric='euclidean', return_samples=False):
+    """functional form of VAE.silhouette"""
+    return vae.silhouette(z, labels, metric, return_samples)

@@ -692,6 +692,65 @@ int  avae_kmeans(avae_handle h, const float* x /* (N, dim) device */, int32_t N,
                  int32_t* label_all /* optional (n_init, N) */, double* centers_all /* optional (n_init, k, dim) */,
                  int32_t* stat_all /* optional (n_init, 4) */);
 
+/* ---- cluster-quality scores of latent rows ----------------------------------------------------------------------------------------
+ * scikit-learn's silhouette_samples / silhouette_score, calinski_harabasz_score (CH) and davies_bouldin_score (DB) of N rows for L
+ * labelings of the SAME rows in ONE call: every pair distance is formed once per pass and binned for all labelings of the pass; no
+ * (N, N) panel is kept.  Everything is enqueued on the handle's stream without a synchronisation.  Every pointer is device memory
+ * except K, which the host reads.  All arithmetic is double; the rows are fp32.  Kmax = max_l K[l].  (The float64 restatement of this
+ * contract is tests/sil_ref.py.)
+ *   rows       X = double(x); for metric 1 X_i = x_i / sqrt(sum_j x_ij^2), a division in double; a zero row stays zero.
+ *   distance   d(i, k): metric 0 sqrt(sum_j (X_ij - X_kj)^2); metric 2 the same sum without the root; metric 1
+ *              min(max(1 - sum_j X_ij X_kj, 0), 2).  Differences, not the Gram trick: duplicate rows give exactly 0 under metrics 0
+ *              and 2.  A pair's sum runs over j in ascending order.
+ *   labeling   row i of labeling l is labelled c = label[l, i] if 0 <= c < K[l]; otherwise it is unlabelled in l: it belongs to no
+ *              cluster, its values enter none of l's sums (a NaN row unlabelled in l leaves l's outputs finite), its sil and ab are 0,
+ *              its nearest is -1 and it is left out of score.  (One labeling per topic with the other topics' rows at -1 gives
+ *              per-topic scores in the same call.)
+ *   silhouette n_c = members of cluster c; S_i(c) = sum of d(i, k) over the k labelled c, k != i, in ascending k.
+ *              a_i = S_i(c_i) / (n_{c_i} - 1), 0 for a singleton; b_i = min over c != c_i with n_c > 0 of S_i(c) / n_c, 0 if there is
+ *              none; nearest_i = the first c attaining it, -1 if there is none.  s_i = 0 if n_{c_i} = 1, if no other cluster is
+ *              non-empty or if max(a_i, b_i) = 0; otherwise (b_i - a_i) / max(a_i, b_i): sklearn's values, its 0 for singletons and
+ *              its nan_to_num included.  score[l] = the mean of s_i over the labelled rows (thread t of 256 the rows t, t + 256 ..,
+ *              then the wave butterfly and the four waves ascending), 0 if there are none.  cluster_mean[l, c] = the mean of s_i over
+ *              the members of c in ascending i, 0 where c is empty; count[l, c] = n_c; both are 0 at c >= K[l].
+ *   CH, DB     on the rows X above (metric 2: those of metric 0).  k' = non-empty clusters, n' = labelled rows, m_c the member means
+ *              (sums in ascending i), m = the mean of the labelled rows (the clusters' sums in ascending c, / n').  trW = sum_i |X_i -
+ *              m_{c_i}|^2, trB = sum_c n_c |m_c - m|^2.  CH = (trB / (k' - 1)) / (trW / (n' - k')); NaN if k' < 2 or n' = k';
+ *              otherwise 1.0 if trW = 0 (sklearn).  S_c = the mean Euclidean distance of the members to m_c, M_cc' = |m_c - m_c'|,
+ *              R_cc' = (S_c + S_c') / M_cc', 0 where M = 0; DB = the mean over the non-empty c of max_{c' != c} R_cc'; NaN if k' < 2.
+ *              index (L, 2) = CH, DB.
+ *   outputs    score (L).  Optional: sil (L, N) = s; ab (L, N, 2) = a, b; nearest (L, N); count (L, Kmax); cluster_mean (L, Kmax);
+ *              index (L, 2).
+ *   range      2 <= N <= 2^18; dim a multiple of 4 in [4, 1024]; x 16-byte aligned; 1 <= K[l] <= 4096; 1 <= L <= 64.
+ *   not finite values in labelled rows are NOT checked.  The result is then unspecified but complete; never a hang, never a write outside
+ *              the outputs.  A label never indexes outside the bins.
+ *   bits       no float atomics.  sil, ab and nearest are a function of the arguments alone: they do not depend on how the planner
+ *              tiles the rows or groups the labelings (option sil_chunk).  Every other output has an order fixed by the shape.
+ *   plan       a workgroup owns TI in {4, 8, 16, 32, 64} rows and walks all N columns in ascending tiles of 64; the bins of a pass
+ *              (TI x sum K x 8 bytes) and the staging lie in the workgroup's LDS (160 KiB).  The planner takes the largest TI that
+ *              needs no more passes over the labelings than TI = 4 does, then halves it while there are fewer row tiles than CUs; a
+ *              pass forms the distances once for its labelings.  K = 4096 alone is one pass at TI = 4.
+ *   workspace  4 (2 L + 1 + sum K) bytes of counts, 8 N of norms for the cosine, 8 L N unless sil is given; with index another
+ *              8 (sum K)(dim + 2) + 8 L (2 N + dim + 4); + 256-byte rounding, reserved once per call.  Nothing is
+ *              proportional to N^2 or N K.
+ * Errors (text through avae_last_error; checked on the host, before any launch; each with its own text): a null sc, x, label, K or
+ * score; N, dim, L, a K[l] or metric out of range; x not 16-byte aligned; a reserved field != 0; a device whose workgroups get less
+ * than 160 KiB of LDS; a workspace the device cannot give (the text names its size).
+ * Option sil_chunk (avae_set_option; a test aid): a value > 0 caps TI (the largest allowed value within it, at least 4; the CU
+ * preference is then off), the columns of a tile and the bin columns of a pass (a labeling alone is always taken), so that small tests
+ * run ragged tiles and several passes; 0 lets the planner decide.  sil, ab and nearest are the same bits for every value.            */
+typedef struct avae_silhouette_config {
+    int32_t metric;    /* 0 euclidean, 1 cosine, 2 squared euclidean */
+    int32_t L;         /* labelings, 1 .. 64 */
+    int32_t reserved;  /* 0 */
+    int32_t reserved2; /* 0 */
+} avae_silhouette_config;
+int  avae_silhouette(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_silhouette_config* sc,
+                     const int32_t* label /* (L, N) device */, const int32_t* K /* (L) HOST */,
+                     double* score /* (L) */, double* sil /* optional (L, N) */, double* ab /* optional (L, N, 2) */,
+                     int32_t* nearest /* optional (L, N) */, int32_t* count /* optional (L, Kmax) */,
+                     double* cluster_mean /* optional (L, Kmax) */, double* index /* optional (L, 2): CH, DB */);
+
 #ifdef __cplusplus
 }
 #endif
