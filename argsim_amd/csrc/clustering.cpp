@@ -1,6 +1,6 @@
 // clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
 // (kernels: ward.hip), of avae_affinity (kernels: affinity.hip), of avae_tsne (kernels: tsne.hip, the distances affinity.hip's) and of
-// avae_kmeans (kernels: kmeans.hip), and of avae_silhouette (kernels: silhouette.hip).
+// avae_kmeans (kernels: kmeans.hip), of avae_gmm_fit and avae_gmm_score (kernels: gmm.hip), and of avae_silhouette (kernels: silhouette.hip).
 // Contract: include/argsim_vae.h.
 #include "ctx.h"
 
@@ -269,6 +269,81 @@ int avae_kmeans(avae_handle h, const float* x, int32_t N, int32_t dim, const ava
     // every iteration is enqueued; a launch that finds the restart's stop decided returns at once.  Never a synchronisation
     for (int it = 0; it < kc->max_iter; ++it) AV_CHECK(km_iteration(h->stream, a, it));
     AV_CHECK(km_finish(h->stream, a, label, centers, stat, inertia, label_all, centers_all, stat_all));
+    return 0;
+}
+
+// the buffers of a mixture call, every one on a 256-byte boundary, R restarts: the state (R), weights, n_c, half log determinants,
+// t_ic constants and bad flags (R, k) each, means, variances and precisions (R, k, dim) each, the parts' (max, sum, first maximum, its
+// component) (R, parts, N) 28 bytes a row, lse (R, N), the bound's partials (R, ceil(N / 256)), the M-step's partials (R, slices, k, 2 dim + 1)
+static void gmm_layout(Bump& b, GmArgs& a)
+{
+    const size_t n = (size_t)a.N, R = (size_t)a.R, k = (size_t)a.k, d = (size_t)a.dim;
+    a.st = b.take<GmState>(R); a.best = b.take<int>(1);
+    a.W = b.take<double>(R * k); a.NC = b.take<double>(R * k); a.HLD = b.take<double>(R * k); a.LC = b.take<double>(R * k); a.bad = b.take<int>(R * k);
+    a.MU = b.take<double>(R * k * d); a.COV = b.take<double>(R * k * d); a.PREC = b.take<double>(R * k * d);
+    a.pm = b.take<double>(R * a.p.parts * n); a.ps = b.take<double>(R * a.p.parts * n); a.pt = b.take<double>(R * a.p.parts * n);
+    a.pi = b.take<int>(R * a.p.parts * n);
+    a.lse = b.take<double>(R * n); a.bpart = b.take<double>(R * a.p.blks);
+    a.mpart = b.take<double>(R * a.p.slices * k * (2 * d + 1));
+}
+
+int avae_gmm_fit(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_gmm_config* gc, const int32_t* label_in, const double* w_in,
+                 const double* mu_in, const double* cov_in, double* weights, double* means, double* covars, int32_t* label, int32_t* stat,
+                 double* lower, double* logp, double* resp, double* weights_all, double* means_all, double* covars_all, int32_t* stat_all,
+                 double* trace)
+{
+    if (!h) return 1;
+    if (!gc) return fail(h, "gmm config is null");
+    if (!x || !weights || !means || !covars || !label || !stat || !lower)
+        return fail(h, "gmm: x, weights, means, covars, label, stat and lower must be given");
+    if (N < 2 || N > kGmMaxN) return fail(h, "gmm: N must be in [2, 2^22]");
+    AV_TRY(check_rows(h, "gmm", dim, "x", {x}));
+    if (gc->k < 1 || gc->k > std::min(N, kGmMaxK)) return fail(h, "gmm: k must be in [1, min(N, 1024)]");
+    if (gc->n_init < 1 || gc->n_init > kGmMaxInit) return fail(h, "gmm: n_init must be in [1, 16]");
+    if (gc->max_iter < 0 || gc->max_iter > 10000) return fail(h, "gmm: max_iter must be in [0, 10000]");
+    if (gc->covariance < 0 || gc->covariance > 1) return fail(h, "gmm: covariance must be 0 (diag) or 1 (spherical)");
+    if (gc->init < 0 || gc->init > 1) return fail(h, "gmm: init must be 0 (label_in) or 1 (w_in, mu_in, cov_in)");
+    if (gc->init == 0 && !label_in) return fail(h, "gmm: init 0 reads label_in, which is not given");
+    if (gc->init == 1 && (!w_in || !mu_in || !cov_in)) return fail(h, "gmm: init 1 reads w_in, mu_in and cov_in, which are not all given");
+    if ((weights_all != nullptr) != (means_all != nullptr) || (weights_all != nullptr) != (covars_all != nullptr))
+        return fail(h, "gmm: weights_all, means_all and covars_all are given together or not at all");
+    if (!(gc->tol >= 0.0)) return fail(h, "gmm: tol must be >= 0");
+    if (!(gc->reg_covar >= 0.0)) return fail(h, "gmm: reg_covar must be >= 0");
+    if (gc->reserved != 0) return fail(h, "gmm: the reserved field must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    GmArgs a{};
+    a.x = x; a.N = N; a.dim = dim; a.k = gc->k; a.R = gc->n_init; a.max_iter = gc->max_iter; a.spherical = gc->covariance;
+    a.tol = gc->tol; a.reg = gc->reg_covar; a.trace = trace; a.dreal = dim - h->gmm_pad;
+    a.p = gm_plan(N, gc->k, gc->n_init, h->gmm_chunk);
+    AV_TRY(place_ws(h, "gmm", [&](Bump& b) { gmm_layout(b, a); }));
+    AV_CHECK(hipMemsetAsync(a.st, 0, (size_t)a.R * sizeof(GmState), h->stream));
+    if (gc->init == 1) AV_CHECK(gm_load(h->stream, a, w_in, mu_in, cov_in, 1));
+    else AV_CHECK(gm_start_labels(h->stream, a, label_in));
+    // every iteration is enqueued; a launch that finds the restart's stop decided returns at once.  Never a synchronisation
+    for (int it = 0; it < gc->max_iter; ++it) AV_CHECK(gm_iteration(h->stream, a, it));
+    AV_CHECK(gm_pick(h->stream, a, stat, lower, stat_all));
+    AV_CHECK(gm_final(h->stream, a, logp, label, resp));
+    AV_CHECK(gm_copy(h->stream, a, weights, means, covars, weights_all, means_all, covars_all));
+    return 0;
+}
+
+int avae_gmm_score(avae_handle h, const float* x, int32_t n, int32_t dim, int32_t k, const double* weights, const double* means,
+                   const double* covars, double* logp, int32_t* label, double* resp)
+{
+    if (!h) return 1;
+    if (!x || !weights || !means || !covars || !logp) return fail(h, "gmm score: x, weights, means, covars and logp must be given");
+    if (n < 1 || n > kGmMaxN) return fail(h, "gmm score: n must be in [1, 2^22]");
+    AV_TRY(check_rows(h, "gmm score", dim, "x", {x}));
+    if (k < 1 || k > kGmMaxK) return fail(h, "gmm score: k must be in [1, 1024]");
+    AV_CHECK(hipSetDevice(h->device));
+    GmArgs a{};
+    a.x = x; a.N = n; a.dim = dim; a.k = k; a.R = 1; a.dreal = dim - h->gmm_pad;
+    a.p = gm_plan(n, k, 1, h->gmm_chunk);
+    AV_TRY(place_ws(h, "gmm score", [&](Bump& b) { gmm_layout(b, a); }));
+    AV_CHECK(hipMemsetAsync(a.st, 0, sizeof(GmState), h->stream));
+    AV_CHECK(hipMemsetAsync(a.best, 0, sizeof(int), h->stream));
+    AV_CHECK(gm_load(h->stream, a, weights, means, covars, 0));
+    AV_CHECK(gm_final(h->stream, a, logp, label, resp));
     return 0;
 }
 

@@ -551,6 +551,46 @@ hipError_t km_iteration(hipStream_t st, const KmArgs& a, int it);        // seve
 hipError_t km_finish(hipStream_t st, const KmArgs& a, int32_t* label, float* centers, int32_t* stat, double* inertia, int32_t* label_all,
                      double* centers_all, int32_t* stat_all);
 
+// ---------------------------------------------------------------- Gaussian mixture of latent rows (gmm.hip)
+// One set of N rows and R = n_init restarts side by side per call (contract: include/argsim_vae.h, avae_gmm_fit).  Every buffer is
+// workspace laid out by the caller (clustering.cpp); the state is zero-filled before the first launch.
+constexpr int kGmMaxN = 1 << 22, kGmMaxK = 1024, kGmMaxInit = 16, kGmMaxParts = 16, kGmMaxSlices = 256;
+constexpr int kGmTile = 64;           // rows of a tile of the E and M kernels
+constexpr int kGmMB = 16;             // components of a workgroup of the M kernel
+struct GmState {
+    int done, iters, how, pad;        // done: a launch of a later iteration returns at once; how: 0 converged, 1 max_iter, 2 degenerate
+    double prev, lower;               // the previous iteration's bound; the last one's (-inf for a degenerate restart)
+};
+// tile x parts: the E kernel's grid (chunk components per part); slice rows per workgroup of the M kernel
+struct GmPlan { int tile, tiles, parts, chunk, slice, slices, blks; };
+struct GmArgs {
+    const float* x;
+    int N, dim, k, R, max_iter, spherical;
+    int dreal;                        // dim less the padding columns (option gmm_pad): those have variance 1 and no share in the constants
+    double tol, reg;
+    GmPlan p;
+    GmState* st;                      // (R)
+    double *W, *MU, *COV;             // (R, k), (R, k, dim) x 2: the parameters, updated in place
+    double *PREC, *HLD, *LC;          // (R, k, dim) 1 / cov; (R, k) half the sum of log cov; (R, k) the constant of t_ic
+    double* NC; int* bad;             // (R, k) n_c; a variance of the component is <= 0 or not finite
+    double *pm, *ps, *pt; int* pi;    // (R, parts, N) a part's running (max, sum), its first maximum of t
+    double* lse;                      // (R, N)
+    double* bpart;                    // (R, blks) the bound's partials over blocks of 256 rows
+    double* mpart;                    // (R, slices, k, 2 dim + 1) the M-step's partials: sum r, sum r x (dim), sum r x^2 (dim)
+    int* best;                        // (1) the best restart
+    double* trace;                    // (R, max_iter) the caller's, or null
+};
+GmPlan gm_plan(int N, int k, int R, int chunk_opt);
+// the given parameters into restart slots 0 .. R - 1 with what the E-step derives from them; check: a bad variance ends the restart
+hipError_t gm_load(hipStream_t st, const GmArgs& a, const double* w, const double* mu, const double* cov, int check);
+hipError_t gm_start_labels(hipStream_t st, const GmArgs& a, const int32_t* label_in);      // init 0: one-hot responsibilities, one M-step
+hipError_t gm_iteration(hipStream_t st, const GmArgs& a, int it);        // five launches: E, merge, M, parameters, decide
+hipError_t gm_pick(hipStream_t st, const GmArgs& a, int32_t* stat, double* lower, int32_t* stat_all);
+// the E-step of restart *a.best (all: of slot 0) under its parameters -> logp, label, resp (each may be null)
+hipError_t gm_final(hipStream_t st, const GmArgs& a, double* logp, int32_t* label, double* resp);
+hipError_t gm_copy(hipStream_t st, const GmArgs& a, double* weights, double* means, double* covars, double* weights_all, double* means_all,
+                   double* covars_all);
+
 // ---------------------------------------------------------------- cluster-quality scores of latent rows (silhouette.hip)
 // One set of N rows and L labelings per call (contract: include/argsim_vae.h, avae_silhouette).  Every buffer is workspace laid out by
 // the caller (clustering.cpp) or the caller's own output; the counts are zero-filled before the first launch.

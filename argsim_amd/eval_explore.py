@@ -7,7 +7,7 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
     python -m argsim_amd.eval_explore --inputs data/test_data_emb.npy --labels data/test_labels.npy \\
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
         [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]] [--kmeans K [--kmeans-init 10]]
-        [--quality] [--sweep LO:HI[:STEP]]
+        [--quality] [--sweep LO:HI[:STEP]] [--gmm K [--gmm-cov diag|spherical] [--gmm-init R]] [--gmm-sweep LO:HI[:STEP]]
 
 With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
 device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
@@ -21,7 +21,13 @@ device call each), the same lines per run and the columns cls_km_* / dist_km_* i
 With --quality every run that was made is followed by one line "silhouette %.4f  CH %.2f  DB %.4f": the silhouette score, the
 Calinski-Harabasz and the Davies-Bouldin index of its clusters on its own metric (VAE.silhouette, ONE device call).  With --sweep LO:HI[:STEP]
 the table "k silhouette CH DB" of k-means for every k of the range follows per input and metric (VAE.sweep_k: one k-means call per k, ONE
-silhouette call over all of them), the k with the largest silhouette marked with *.  Without the two flags the output is what it was."""
+silhouette call over all of them), the k with the largest silhouette marked with *.  Without the two flags the output is what it was.
+
+With --gmm K a Gaussian mixture with K components is fitted to the embeddings and, where given, to those of the sampled segmentation
+(VAE.gmm: --gmm-cov covariances, the best of --gmm-init restarts from k-means labels, ONE device call each after the k-means calls): the
+same lines per run for its hard labels, and the columns cls_gmm_* / logp_gmm_* (a row's component and its log-density) in the CSV.  With
+--gmm-sweep LO:HI[:STEP] the table "k BIC AIC lower_bound" follows per input (VAE.sweep_gmm), the k with the smallest BIC marked with *.
+Without these flags the output is what it was."""
 import argparse
 import csv
 
@@ -31,6 +37,8 @@ RUNS = (('euc', 'euclidean', 'sqeuclidean', False), ('euc_sp', 'euclidean', 'sqe
         ('cos_sp', 'cosine', 'cosine', True))
 COLUMNS = "post topic labels cls_euc dist_euc cls_euc_sp dist_euc_sp cls_cos dist_cos cls_cos_sp dist_cos_sp".split()
 KM_COLUMNS = "cls_km_euc dist_km_euc cls_km_euc_sp dist_km_euc_sp cls_km_cos dist_km_cos cls_km_cos_sp dist_km_cos_sp".split()      # with --kmeans
+GMM_RUNS = (('z', False), ('z_sp', True))
+GMM_COLUMNS = "cls_gmm_z logp_gmm_z cls_gmm_z_sp logp_gmm_z_sp".split()      # with --gmm
 
 
 def purity_lines(pred, topics, order):
@@ -61,10 +69,21 @@ def sweep_lines(vae, x, name, metric, ks, n_init, seed):
     return lines
 
 
-def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10, quality=False, sweep=None):
+def gmm_sweep_lines(vae, x, name, ks, covariance, n_init, seed):
+    """the table of --gmm-sweep for one input"""
+    t = vae.sweep_gmm(x, ks, covariance=covariance, n_init=n_init, seed=seed)
+    lines = ["gmm sweep %s" % name, "k BIC AIC lower_bound"]
+    for k, bic, aic, lb in zip(t['k'], t['bic'], t['aic'], t['lower_bound']):
+        lines.append("%d %.2f %.2f %.6f%s" % (k, bic, aic, lb, " *" if k == t['best'] else ""))
+    return lines
+
+
+def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10, quality=False, sweep=None, gmm=None, gmm_cov='diag',
+             gmm_init=1, gmm_sweep=None):
     """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed.  kmeans = k adds the
     same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*.  quality: a line of scores behind
-    every run; sweep = [k ..]: the k-means quality table per input and metric"""
+    every run; sweep = [k ..]: the k-means quality table per input and metric.  gmm = k adds a mixture with k components per input
+    (VAE.gmm, gmm_cov covariances, gmm_init restarts): cls_gmm_* / logp_gmm_*; gmm_sweep = [k ..]: the BIC / AIC table per input"""
     from . import affinity
     from .eval_cluster import split_labels
     topics = np.array([p[0] for p in split_labels(labels)])
@@ -98,6 +117,21 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_ini
         x = z_sp if sampled else z
         if x is not None:
             lines += sweep_lines(vae, x, name, metric, sweep, kmeans_init, seed)
+    for name, sampled in GMM_RUNS if gmm else ():
+        x = z_sp if sampled else z
+        if x is None:
+            continue
+        res = vae.gmm(x, gmm, covariance=gmm_cov, n_init=gmm_init, seed=seed)
+        if not res['converged']:
+            lines.append("gmm_%s: stopped after %d iterations" % (name, res['n_iter']))
+        lines += purity_lines(res['labels'], topics, order)
+        lines.append("gmm_%s: lower bound %.6f  BIC %.2f  AIC %.2f" % (name, res['lower_bound'], res['bic'], res['aic']))
+        cols['cls_gmm_' + name] = res['labels']
+        cols['logp_gmm_' + name] = res['logp']
+    for name, sampled in GMM_RUNS if gmm_sweep else ():
+        x = z_sp if sampled else z
+        if x is not None:
+            lines += gmm_sweep_lines(vae, x, name, gmm_sweep, gmm_cov, gmm_init, seed)
     return cols, lines
 
 
@@ -114,7 +148,7 @@ def embed(vae, z, labels, out, plot=None, perplexity=40.0, max_iter=20000, seed=
 
 def write_csv(path, posts, topics, labels, cols):
     """eval_clustering_explorative.py:121-132: the id, then the columns in the reference's order (those of absent runs left out)"""
-    names = [c for c in COLUMNS + KM_COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
+    names = [c for c in COLUMNS + KM_COLUMNS + GMM_COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
     data = dict(cols, post=posts, topic=topics, labels=labels)
     with open(path, 'w', newline='') as f:
         w = csv.writer(f)
@@ -160,6 +194,10 @@ def build_parser():
     ap.add_argument('--kmeans-init', type=_positive, default=10, help="with --kmeans: restarts, the best of which is listed")
     ap.add_argument('--quality', action='store_true', help="a line of silhouette, CH and DB behind every run (VAE.silhouette)")
     ap.add_argument('--sweep', type=_sweep, default=None, help="LO:HI[:STEP]: the k-means quality table for these k per input and metric (VAE.sweep_k)")
+    ap.add_argument('--gmm', type=_positive, default=None, help="also fit a Gaussian mixture with this many components (VAE.gmm)")
+    ap.add_argument('--gmm-cov', choices=('diag', 'spherical'), default='diag', help="with --gmm / --gmm-sweep: the covariances")
+    ap.add_argument('--gmm-init', type=_positive, default=1, help="with --gmm / --gmm-sweep: restarts, the best of which is listed")
+    ap.add_argument('--gmm-sweep', type=_sweep, default=None, help="LO:HI[:STEP]: the BIC / AIC table of mixtures for these k per input (VAE.sweep_gmm)")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -178,7 +216,8 @@ def main(argv=None):
     vae = make_vae(A.device)
     if A.tsne:
         print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
-    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init, A.quality, A.sweep)
+    cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init, A.quality, A.sweep, A.gmm, A.gmm_cov, A.gmm_init,
+                           A.gmm_sweep)
     for line in lines:
         print(line)
     if A.csv:

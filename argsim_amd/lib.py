@@ -90,6 +90,11 @@ class AvaeKmeansConfig(C.Structure):
     _fields_ = [('k', C.c_int32), ('n_init', C.c_int32), ('max_iter', C.c_int32), ('metric', C.c_int32), ('init', C.c_int32),
                 ('reserved', C.c_int32), ('tol', C.c_double), ('seed', C.c_uint64)]
 
+class AvaeGmmConfig(C.Structure):
+    _fields_ = [('k', C.c_int32), ('n_init', C.c_int32), ('max_iter', C.c_int32), ('covariance', C.c_int32), ('init', C.c_int32),
+                ('reserved', C.c_int32), ('tol', C.c_double), ('reg_covar', C.c_double)]
+
+
 class AvaeSilhouetteConfig(C.Structure):
     _fields_ = [('metric', C.c_int32), ('L', C.c_int32), ('reserved', C.c_int32), ('reserved2', C.c_int32)]
 
@@ -138,6 +143,8 @@ SIGNATURES = {
     'avae_affinity': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeAffinityConfig), _P, _P, _P, _P, _P]),
     'avae_tsne': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeTsneConfig)] + [_P] * 10),
     'avae_kmeans': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeKmeansConfig)] + [_P] * 8),
+    'avae_gmm_fit': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeGmmConfig)] + [_P] * 17),
+    'avae_gmm_score': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32] + [_P] * 6),
     'avae_silhouette': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeSilhouetteConfig), _P, C.POINTER(C.c_int32)] + [_P] * 7),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),

@@ -20,6 +20,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) Ward clustering of latent rows (ARS, V_MSR)  -> VAE.ward(z, groups) / VAE.ward_cut(res, k) / VAE.cluster_eval(z, gold, groups)
     (new) affinity propagation of latent rows          -> VAE.affinity(z, metric, ...) / affinity(vae, z, ...)
     (new) k-means of latent rows                       -> VAE.kmeans(z, k, metric, ...) / kmeans(vae, z, k, ...)
+    (new) Gaussian mixture of latent rows (BIC, AIC)   -> VAE.gmm(z, k, ...) / VAE.gmm_score(z, model) / VAE.sweep_gmm(z, ks) / generate(prior=)
     (new) exact t-SNE of latent rows                   -> VAE.tsne(z, perplexity, ...) / tsne(vae, z, ...)
     (new) silhouette, CH and DB of many labelings      -> VAE.silhouette(z, labels, metric) / VAE.sweep_k(z, ks) / silhouette(vae, z, ...)
 """
@@ -410,14 +411,25 @@ class VAE:
         return dict(ids=out[:, :, :n].cpu().numpy(), score=score.cpu().numpy(), cum=cum.cpu().numpy(), len=ln.cpu().numpy(), n=n,
                     lat_parent=lp[:n].cpu().numpy(), lat_token=lt[:n].cpu().numpy(), lat_cum=lc[:n].cpu().numpy())
 
-    def generate(self, n, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False, top_p=0.0):
-        """n sentences from the prior: z ~ N(0, I) drawn on the host with np.random.default_rng(seed), then sample() with the same seed"""
+    def generate(self, n, steps=256, temperature=1.0, top_k=0, seed=0, return_logp=False, top_p=0.0, prior=None):
+        """n sentences from the prior: z ~ N(0, I) drawn on the host with np.random.default_rng(seed), then sample() with the same seed.
+        prior: a mixture model of VAE.gmm over the codes -- z is then drawn from it (gmm.sample: the component by choice(p=weights),
+        then mean + sqrt(cov) * standard_normal, from the same generator)"""
         if int(n) != n or n < 1:
             raise ValueError("n must be an integer >= 1, got %r" % (n,))
         _check_sample_args(steps, temperature, top_k, seed)
         _check_top_p(top_p)
-        z = np.random.default_rng(seed).standard_normal((int(n), self.cfg['dim_rep'])).astype(np.float32)
+        z = self.prior_draw(n, seed, prior)
         return self.sample(z, steps, temperature, top_k, seed, return_logp, top_p)
+
+    def prior_draw(self, n, seed=0, prior=None):
+        """the z (n, dim_rep) float32 that generate() decodes: N(0, I), or rows of the mixture model `prior`"""
+        if prior is None:
+            return np.random.default_rng(seed).standard_normal((int(n), self.cfg['dim_rep'])).astype(np.float32)
+        from . import gmm
+        if np.shape(prior.get('means', ()))[1:] != (self.cfg['dim_rep'],):
+            raise ValueError("prior must be a mixture model over dim_rep = %d columns (VAE.gmm)" % self.cfg['dim_rep'])
+        return gmm.sample(prior, n, seed)[0]
 
 
     # ------------------------------------------------------------------ likelihood
@@ -686,6 +698,25 @@ class VAE:
         from . import silhouette
         return silhouette.sweep_k(self, z, ks, metric, n_init, seed)
 
+    def gmm(self, z, k, covariance='diag', n_init=1, max_iter=100, tol=1e-3, reg_covar=1e-6, seed=0, init='kmeans', return_resp=False,
+            return_all=False):
+        """Gaussian mixture of the rows of z (sklearn's GaussianMixture with 'diag' or 'spherical' covariances: EM from k-means labels,
+        given labels or given parameters) with n_init restarts side by side in ONE device call (include/argsim_vae.h, avae_gmm_fit)
+        -> dict(weights, means, covariances, labels, logp, lower_bound, lower_bounds, n_iter, stop, converged, best, n_parameters, bic,
+        aic[, resp, *_all, trace]) (argsim_amd/gmm.py)"""
+        from . import gmm
+        return gmm.gmm(self, z, k, covariance, n_init, max_iter, tol, reg_covar, seed, init, return_resp, return_all)
+
+    def gmm_score(self, z, model, return_resp=False):
+        """log p(z_i) of the rows of z under a mixture model of VAE.gmm -> dict(logp, labels[, resp]) (avae_gmm_score)"""
+        from . import gmm
+        return gmm.gmm_score(self, z, model, return_resp)
+
+    def sweep_gmm(self, z, ks, **kw):
+        """one gmm call per k in ks -> dict(k, bic, aic, lower_bound, models, best): best is the k with the smallest BIC"""
+        from . import gmm
+        return gmm.sweep_gmm(self, z, ks, **kw)
+
 
 # avae_debug_step_route: seven scalars, then (form, T, C, pipe, ring) per kind of GRU launch, in this order
 ROUTE_GRU = ('enc_fwd', 'enc_bwd', 'top_fwd', 'top_bwd', 'dec_fwd', 'dec_bwd')
@@ -948,3 +979,25 @@ def kmeans(vae, z, k, metric='euclidean', n_init=10, max_iter=300, tol=1e-4, see
 def silhouette(vae, z, labels, metric='euclidean', return_samples=False):
     """functional form of VAE.silhouette"""
     return vae.silhouette(z, labels, metric, return_samples)
+
+
+def _check_gmm_args(z, k, covariance='diag', n_init=1, max_iter=100, tol=1e-3, reg_covar=1e-6, seed=0, init='kmeans'):
+    """the argument rules of VAE.gmm, checked before anything touches the device (ValueError)"""
+    from . import gmm as _gm
+    return _gm._check_gmm_args(z, k, covariance, n_init, max_iter, tol, reg_covar, seed, init)
+
+
+def gmm(vae, z, k, covariance='diag', n_init=1, max_iter=100, tol=1e-3, reg_covar=1e-6, seed=0, init='kmeans', return_resp=False,
+        return_all=False):
+    """functional form of VAE.gmm"""
+    return vae.gmm(z, k, covariance, n_init, max_iter, tol, reg_covar, seed, init, return_resp, return_all)
+
+
+def gmm_score(vae, z, model, return_resp=False):
+    """functional form of VAE.gmm_score"""
+    return vae.gmm_score(z, model, return_resp)
+
+
+def sweep_gmm(vae, z, ks, **kw):
+    """functional form of VAE.sweep_gmm"""
+    return vae.sweep_gmm(z, ks, **kw)

@@ -692,6 +692,77 @@ int  avae_kmeans(avae_handle h, const float* x /* (N, dim) device */, int32_t N,
                  int32_t* label_all /* optional (n_init, N) */, double* centers_all /* optional (n_init, k, dim) */,
                  int32_t* stat_all /* optional (n_init, 4) */);
 
+/* ---- Gaussian mixture of latent rows -----------------------------------------------------------------------------------------------
+ * scikit-learn 1.7.2's GaussianMixture(covariance_type = 'diag' | 'spherical') of N rows with k components, n_init restarts side by side,
+ * in ONE call: everything is enqueued on the handle's stream without a synchronisation; each restart decides its stop on the device and a
+ * launch that finds the stop decided returns at once.  Every pointer is device memory.  The rows are fp32; everything else is double.
+ * (The float64 restatement of this contract is tests/gmm_ref.py.)
+ *   E-step     p_cj = 1 / cov_cj.  q_ic = sum_j (x_ij - mu_cj)^2 p_cj: the difference is formed before the square, j runs in ascending
+ *              order as one chain q <- fma(d d, p, q); a term depends on the row and the component only, never on tile, part or plan.
+ *              t_ic = ((log w_c - 1/2 sum_j log cov_cj) - (dim / 2) log 2 pi) - 1/2 q_ic.  lse_i = m_i + log sum_c exp(t_ic - m_i) with
+ *              m_i the maximum over c, kept as a running (max, sum) pair: a thread takes its components in ascending order, the 16
+ *              threads of a row are merged by a butterfly, the component parts in ascending order.  r_ic = exp(t_ic - lse_i).  The
+ *              iteration's lower bound is (1 / N) sum_i lse_i (blocks of 256 rows, ascending).
+ *   M-step     n_c = sum_i r_ic + 10 x 2^-52; mu_c = sum_i r_ic x_i / n_c; cov_cj = sum_i r_ic x_ij^2 / n_c - mu_cj^2 + reg_covar
+ *              (sklearn's one-pass form, kept so that results are comparable: it cancels where a variance is small against mu^2).  The
+ *              sums run over the rows of a slice in ascending order, then over the slices in ascending order.  Spherical: every column of
+ *              cov_c is the mean over j of these values, summed in ascending j; the outputs keep the (k, dim) shape with equal columns.
+ *              w_c = n_c / N, then divided by sum_c w_c (ascending c).
+ *   start      init 0: row i of restart r has responsibility 1 for label_in[r, i] if that lies in [0, k) and none otherwise (for the
+ *              start only); one M-step follows.  init 1: the parameters are taken as given (the weights are not normalised).
+ *   loop       lower_prev = -inf; iteration it runs E, then M; change = lower - lower_prev; stop "converged" (0) if |change| < tol, else
+ *              go on to max_iter (stop 1).  Stop "degenerate" (2) if after an M-step -- the start included, and the given variances of
+ *              init 1 -- a variance is <= 0 or not finite, or if the bound is not finite: that restart has lower = -inf and is never the
+ *              best unless all are degenerate, in which case the best is restart 0 and stat[2] = 2.  lower[r] is the last iteration's
+ *              bound, evaluated before the last M-step (sklearn's lower_bound_); -inf with max_iter = 0.  trace[r, it] holds each
+ *              iteration's bound; entries past the stop are -inf.
+ *   result     the best restart is the first one with the largest lower among those not degenerate.  A final E-step under its final
+ *              parameters gives logp (= lse_i), resp and label = the first maximum of t_ic (a row without a number takes component 0).
+ *              avae_gmm_score is that final E-step for any rows and parameters: on the fitted rows, the fit's own bits.
+ *   outputs    weights (k), means and covars (k, dim), label (N) of the best restart; stat (4) = best restart, its iterations, its stop,
+ *              0; lower (n_init).  Optional: logp (N), resp (N, k), weights_all (n_init, k), means_all and covars_all (n_init, k, dim),
+ *              stat_all (n_init, 4) = iterations, stop, 0, 0; trace (n_init, max_iter).
+ *   range      2 <= N <= 2^22 (score: 1 <= n); 1 <= k <= min(N, 1024); dim a multiple of 4 in [4, 1024]; x 16-byte aligned.
+ *   not finite inputs are NOT checked.  The result is then unspecified but complete; never a hang.
+ *   bits       no float atomics; every sum has an order fixed by the plan, and the plan is a function of N, k, dim, n_init and the
+ *              option alone: the same arguments and option give the same bits.
+ *   cost       an iteration is five launches whether or not a restart has stopped.  The M-step forms t_ic again instead of storing
+ *              the (N, k) panel.
+ *   workspace  per restart 36 N bytes of lse and part records (+ 28 N per further component part, at most 16, only where there are few
+ *              row tiles), 24 k dim of means, variances and precisions, 8 slices k (2 dim + 1) of M-step partials (slices <= 64; with
+ *              the option <= 256); + 256-byte rounding, reserved once per call.
+ * Errors (text through avae_last_error; checked on the host, before any launch; the outputs are left untouched): a null gc, x, weights,
+ * means, covars, label, stat or lower; N, dim, k, n_init or max_iter out of range; x not 16-byte aligned; init or covariance outside
+ * 0 .. 1; init 0 without label_in; init 1 without w_in, mu_in and cov_in; only some of weights_all, means_all, covars_all; tol or
+ * reg_covar negative or NaN; reserved != 0; a workspace the device cannot give (the text names its size).
+ * Option gmm_chunk (avae_set_option; a test aid): caps the components of a part and the rows of a tile and of a slice, so that small
+ * tests run several of each and their merges; 0 lets the planner decide.  Another value may change last bits of sums; never a t_ic.
+ * Option gmm_pad (0 .. 3; rows whose real column count is no multiple of 4): the last gmm_pad columns of x are padding.  Whatever they
+ * hold, their variance is 1 (given variances there are not read), they have no share in the spherical mean, and the constant of t_ic
+ * counts dim - gmm_pad columns.  With zeros in them (and zero means with init 1) they add exactly nothing to any q_ic: the other columns'
+ * results are those of the unpadded rows.                                                                                             */
+typedef struct avae_gmm_config {
+    int32_t k;          /* components, 1 <= k <= min(N, 1024) */
+    int32_t n_init;     /* restarts side by side in the one call, 1 .. 16 */
+    int32_t max_iter;   /* EM iterations per restart, 0 .. 10000 (sklearn: 100); 0 = the start's parameters and the final E-step only */
+    int32_t covariance; /* 0 diag, 1 spherical */
+    int32_t init;       /* 0: label_in (n_init, N) -> one-hot responsibilities -> one M-step; 1: the parameters in w_in, mu_in, cov_in */
+    int32_t reserved;   /* 0 */
+    double  tol;        /* >= 0: stop when |change of the lower bound| < tol (sklearn: 1e-3) */
+    double  reg_covar;  /* >= 0, added to every variance (sklearn: 1e-6) */
+} avae_gmm_config;
+int  avae_gmm_fit(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_gmm_config* gc,
+                  const int32_t* label_in /* (n_init, N), init 0 */,
+                  const double* w_in /* (n_init, k) */, const double* mu_in, const double* cov_in /* (n_init, k, dim) each, init 1 */,
+                  double* weights /* (k) */, double* means /* (k, dim) */, double* covars /* (k, dim) */,
+                  int32_t* label /* (N) */, int32_t* stat /* (4) */, double* lower /* (n_init) */,
+                  double* logp /* optional (N) */, double* resp /* optional (N, k) */,
+                  double* weights_all, double* means_all, double* covars_all /* optional, all three or none: (n_init, ..) */,
+                  int32_t* stat_all /* optional (n_init, 4) */, double* trace /* optional (n_init, max_iter) */);
+int  avae_gmm_score(avae_handle h, const float* x /* (n, dim) device */, int32_t n, int32_t dim, int32_t k,
+                    const double* weights, const double* means, const double* covars,
+                    double* logp /* (n) */, int32_t* label /* optional (n) */, double* resp /* optional (n, k) */);
+
 /* ---- cluster-quality scores of latent rows ----------------------------------------------------------------------------------------
  * scikit-learn's silhouette_samples / silhouette_score, calinski_harabasz_score (CH) and davies_bouldin_score (DB) of N rows for L
  * labelings of the SAME rows in ONE call: every pair distance is formed once per pass and binned for all labelings of the pass; no
