@@ -1,6 +1,7 @@
 // clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
 // (kernels: ward.hip), of avae_affinity (kernels: affinity.hip), of avae_tsne (kernels: tsne.hip, the distances affinity.hip's) and of
-// avae_kmeans (kernels: kmeans.hip), of avae_gmm_fit and avae_gmm_score (kernels: gmm.hip), and of avae_silhouette (kernels: silhouette.hip).
+// avae_kmeans (kernels: kmeans.hip), of avae_gmm_fit and avae_gmm_score (kernels: gmm.hip), of avae_silhouette (kernels: silhouette.hip)
+// and of avae_dbscan (kernels: dbscan.hip).
 // Contract: include/argsim_vae.h.
 #include "ctx.h"
 
@@ -401,6 +402,57 @@ int avae_silhouette(avae_handle h, const float* x, int32_t N, int32_t dim, const
     AV_CHECK(sil_pairs(h->stream, a, plan));
     AV_CHECK(sil_scores(h->stream, a, score, count, cluster_mean));
     if (index) AV_CHECK(sil_indices(h->stream, a, index));
+    return 0;
+}
+
+int avae_dbscan(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_dbscan_config* dc, int32_t* label, int32_t* count, int32_t* stat)
+{
+    if (!h) return 1;
+    if (!dc) return fail(h, "dbscan config is null");
+    if (!x) return fail(h, "dbscan: x is null");
+    if (!label) return fail(h, "dbscan: label is null");
+    if (!stat) return fail(h, "dbscan: stat is null");
+    if (N < 1 || N > kDbMaxN) return fail(h, "dbscan: N must be in [1, 2^17]");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "dbscan: dim must be a multiple of 4 in [4, 1024]");
+    if (dc->metric < 0 || dc->metric > 1) return fail(h, "dbscan: metric must be 0 (euclidean) or 1 (cosine)");
+    if (dc->min_samples < 1) return fail(h, "dbscan: min_samples must be >= 1");
+    if (dc->max_rounds < 0 || dc->max_rounds > kDbMaxRounds) return fail(h, "dbscan: max_rounds must be in [0, 4096]");
+    if (!(dc->eps > 0.0) || !std::isfinite(dc->eps)) return fail(h, "dbscan: eps must be > 0 and finite");
+    if ((uintptr_t)x & 15) return fail(h, "dbscan: x must be 16-byte aligned");
+    if (dc->reserved != 0) return fail(h, "dbscan: the reserved field must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    int cus = 0;
+    AV_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    const DbPlan plan = db_plan(N, dim, h->dbscan_chunk, cus);
+    const int rounds = dc->max_rounds > 0 ? dc->max_rounds : plan.rounds;
+    // Workspace, every buffer on a 256-byte boundary: the state, the rounds' flags (rounds + 1) int, the bit matrix
+    // (N, W) of 8-byte words, W = ceil(N / 64), the core mask (W), three parent arrays and the roots' numbers (N) int each, the counts
+    // (N) int unless the caller gives count, with the cosine the row norms (N)
+    const size_t n = (size_t)N, W = (size_t)plan.W;
+    DbArgs a{};
+    a.x = x; a.N = N; a.dim = dim; a.W = plan.W; a.min_samples = dc->min_samples; a.label = label;
+    a.thr = dc->metric == 1 ? 2.0 * dc->eps : dc->eps * dc->eps;
+    double* rnorm = nullptr;
+    AV_TRY(place_ws(h, "dbscan", [&](Bump& b) {
+        a.st = b.take<DbState>(1);
+        a.flag = b.take<int>((size_t)rounds + 1);
+        a.adj = b.take<unsigned long long>(n * W);
+        a.cmask = b.take<unsigned long long>(W);
+        for (int q = 0; q < 3; ++q) a.par[q] = b.take<int>(n);
+        a.num = b.take<int>(n);
+        a.count = count ? count : b.take<int32_t>(n);
+        rnorm = b.opt<double>(dc->metric == 1, n);
+    }));
+    a.rnorm = rnorm;
+    AV_CHECK(hipMemsetAsync(a.st, 0, sizeof(DbState), h->stream));
+    AV_CHECK(hipMemsetAsync(a.flag, 0, ((size_t)rounds + 1) * sizeof(int), h->stream));
+    AV_CHECK(hipMemsetAsync(a.count, 0, n * sizeof(int32_t), h->stream));
+    AV_CHECK(db_prepare(h->stream, a));
+    AV_CHECK(db_pairs(h->stream, a, plan));
+    AV_CHECK(db_core(h->stream, a));
+    // every round is enqueued; a launch that finds the fixed point reached returns at once.  Never a synchronisation
+    for (int t = 0; t < rounds; ++t) AV_CHECK(db_round(h->stream, a, t));
+    AV_CHECK(db_finish(h->stream, a, stat));
     return 0;
 }
 

@@ -83,6 +83,7 @@ struct avae_ctx {
     int gmm_chunk = 0;    // avae_gmm_fit / avae_gmm_score test aid: caps the components of a part and the rows of a tile and of a slice (small tests run several of each); 0: gm_plan decides
     int gmm_pad = 0;      // avae_gmm_fit / avae_gmm_score: the last 0 .. 3 columns of the rows are padding to the multiple of 4 (variance 1, no share in the constants)
     int sil_chunk = 0;  // avae_silhouette test aid: caps the rows and columns of a tile and the bin columns of a pass (small tests run ragged tiles and several passes); 0: sil_plan decides
+    int dbscan_chunk = 0;  // avae_dbscan test aid: the low 8 bits cap the rows of a tile, the bits above give the column tiles of a part (small tests run several tile shapes and parts); 0: db_plan decides
     int gru_bf16 = 1;     // compute_dtype 1 only: the recurrent product of the team kernels takes bf16 operands too (0: fp32 recurrence)
     // offsets
     int64_t oE = 0, oKout = 0, oBout = 0, oWmu = 0, oBmu = 0, oWlv = 0, oBlv = 0, oWex = 0, oBex = 0;

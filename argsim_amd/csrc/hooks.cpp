@@ -499,4 +499,22 @@ int avae_debug_sil_plan(int32_t N, int32_t dim, int32_t L, const int32_t* K, int
     return 0;
 }
 
+// test hook: db_plan(N, dim, chunk_opt, cus) of avae_dbscan; out = TI, row tiles, column parts, column tiles per part, W, the LDS bytes of
+// the pair pass, the default max_rounds, then the workspace bytes of a cosine call without count as two 32-bit halves (low, high).  Host
+// arithmetic only: callable without a GPU.
+int avae_debug_dbscan_plan(int32_t N, int32_t dim, int32_t chunk_opt, int32_t cus, int32_t* out)
+{
+    if (!out || N < 1 || N > kDbMaxN || dim < 4 || dim > 1024 || (dim & 3) || chunk_opt < 0 || cus < 1) return 1;
+    const DbPlan p = db_plan(N, dim, chunk_opt, cus);
+    const int32_t f[7] = {p.TI, p.rtiles, p.parts, p.chunk, p.W, p.lds, p.rounds};
+    std::copy(f, f + 7, out);
+    const size_t n = (size_t)N, W = (size_t)p.W;
+    Bump b{nullptr};
+    b.take<DbState>(1); b.take<int>((size_t)p.rounds + 1); b.take<unsigned long long>(n * W); b.take<unsigned long long>(W);
+    for (int q = 0; q < 4; ++q) b.take<int>(n);
+    b.take<int32_t>(n); b.take<double>(n);
+    out[7] = (int32_t)(b.off & 0xffffffffu); out[8] = (int32_t)(b.off >> 32);
+    return 0;
+}
+
 }  // extern "C"

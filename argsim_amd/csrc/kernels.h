@@ -622,6 +622,40 @@ hipError_t sil_pairs(hipStream_t st, const SilArgs& a, const SilPlan& p);  // on
 hipError_t sil_scores(hipStream_t st, const SilArgs& a, double* score, int32_t* count, double* cluster_mean);
 hipError_t sil_indices(hipStream_t st, const SilArgs& a, double* index);   // six launches: CH and DB
 
+// ---------------------------------------------------------------- density clustering of latent rows (dbscan.hip)
+// One set of N rows per call (contract: include/argsim_vae.h, avae_dbscan).  Every buffer is workspace laid out by the caller
+// (clustering.cpp) or the caller's own output; count, flag and st are zero-filled before the first launch.
+constexpr int kDbMaxN = 1 << 17;      // the bit matrix adj[N][ceil(N / 64)] is 2 GiB there
+constexpr int kDbTJ = 64;             // columns of a tile of the pair pass: one 64-bit word of adjacency per row
+constexpr int kDbDK = 32;             // row elements per LDS stage
+constexpr int kDbMaxParts = 65535;    // column parts of the pair pass (grid.y)
+constexpr int kDbMaxRounds = 4096;    // of hook and jump
+// the default max_rounds is 2 (kDbRoundA ceil(log2 N) + kDbRoundB): twice the fit of tests/dbscan_ref.py's model
+constexpr int kDbRoundA = 1, kDbRoundB = 1;
+// a workgroup owns TI rows and the column tiles [part * chunk, part * chunk + chunk) of the W = ceil(N / 64)
+struct DbPlan { int TI, rtiles, parts, chunk, W, lds, rounds; };
+struct DbState { int rounds, nclusters, bad, pad; };
+struct DbArgs {
+    const float* x; const double* rnorm;      // rows; their norms (cosine) or null
+    int N, dim, W, min_samples;
+    double thr;                               // a pair is within eps iff p <= thr: eps^2, for the cosine 2 eps
+    unsigned long long* adj;                  // (N, W) bit j % 64 of word j / 64 of row i: p(i, j) <= thr
+    unsigned long long* cmask;                // (W) the core rows as bits
+    int32_t* count;                           // (N) rows within eps, the row itself included: the caller's, or workspace
+    int* par[3];                              // (N) each: the parents, and the two arrays the hooks write in turn
+    int* num;                                 // (N) a root's cluster number
+    int* flag;                                // (max_rounds + 1) flag[t]: round t has work (flag[0] is set by db_core)
+    DbState* st;
+    int32_t* label;
+};
+size_t db_pairs_lds(int TI);
+DbPlan db_plan(int N, int dim, int chunk_opt, int cus);
+hipError_t db_prepare(hipStream_t st, const DbArgs& a);                  // row norms (cosine)
+hipError_t db_pairs(hipStream_t st, const DbArgs& a, const DbPlan& p);   // the bit matrix and the counts
+hipError_t db_core(hipStream_t st, const DbArgs& a);                     // the core mask, parent[i] = i
+hipError_t db_round(hipStream_t st, const DbArgs& a, int t);             // two launches: hook, jump
+hipError_t db_finish(hipStream_t st, const DbArgs& a, int32_t* stat);    // verify, number, label, border, stat
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

@@ -1,4 +1,4 @@
-// rows_dev.h -- what the double-precision kernels over latent rows share (kmeans.hip, silhouette.hip): a row element as the double the
+// rows_dev.h -- what the double-precision kernels over latent rows share (kmeans.hip, silhouette.hip, dbscan.hip): a row element as the double the
 // contract names (for the cosine divided by the row's double norm; a zero row stays zero), the norm of a row by one wave, and the
 // workgroup's double sum in its one fixed order.  Internal: not part of the C ABI.
 #pragma once
@@ -8,6 +8,14 @@ namespace avae {
 
 // rn < 0: the rows are taken as they are; rn = 0: a zero row
 __device__ __forceinline__ double row_value(float v, double rn) { return rn < 0.0 ? (double)v : (rn > 0.0 ? (double)v / rn : 0.0); }
+
+// the pair passes (silhouette.hip, dbscan.hip) stage rows in LDS as doubles, [element][row] with `rows` rows to an element: the four
+// elements e0 .. e0 + 3 of row r, zeros where `on` is false
+__device__ __forceinline__ void stage_row4(double* s, int rows, int e0, int r, float4 v, double rn, bool on)
+{
+    s[e0 * rows + r] = on ? row_value(v.x, rn) : 0.0; s[(e0 + 1) * rows + r] = on ? row_value(v.y, rn) : 0.0;
+    s[(e0 + 2) * rows + r] = on ? row_value(v.z, rn) : 0.0; s[(e0 + 3) * rows + r] = on ? row_value(v.w, rn) : 0.0;
+}
 
 // one wave per row: the double sum of squares, lane l over elements 4 l .. 4 l + 3, 256 + 4 l .. in index order, then the xor butterfly;
 // every lane returns the root

@@ -115,16 +115,8 @@ __global__ __launch_bounds__(256) void sil_pass_kernel(SilArgs a, int l0, int nl
             for (int u = 0; u < 2; ++u) {
                 const int rl = cr[u], e0 = ce[u];
                 const bool in = j0 + e0 < dim;
-                if (rl < TI) {
-                    const bool on = in && rl < nrow;
-                    const double rn = rni[rl];
-                    xi[e0 * TI + rl] = on ? row_value(pi[u].x, rn) : 0.0; xi[(e0 + 1) * TI + rl] = on ? row_value(pi[u].y, rn) : 0.0;
-                    xi[(e0 + 2) * TI + rl] = on ? row_value(pi[u].z, rn) : 0.0; xi[(e0 + 3) * TI + rl] = on ? row_value(pi[u].w, rn) : 0.0;
-                }
-                const bool on = in && rl < ncol;
-                const double rn = rnj[rl];
-                xj[e0 * TJ + rl] = on ? row_value(pj[u].x, rn) : 0.0; xj[(e0 + 1) * TJ + rl] = on ? row_value(pj[u].y, rn) : 0.0;
-                xj[(e0 + 2) * TJ + rl] = on ? row_value(pj[u].z, rn) : 0.0; xj[(e0 + 3) * TJ + rl] = on ? row_value(pj[u].w, rn) : 0.0;
+                if (rl < TI) stage_row4(xi, TI, e0, rl, pi[u], rni[rl], in && rl < nrow);
+                stage_row4(xj, TJ, e0, rl, pj[u], rnj[rl], in && rl < ncol);
             }
             __syncthreads();
             if (j0 + DK < dim) fetch(col0, j0 + DK);

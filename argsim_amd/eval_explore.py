@@ -8,6 +8,7 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
         [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]] [--kmeans K [--kmeans-init 10]]
         [--quality] [--sweep LO:HI[:STEP]] [--gmm K [--gmm-cov diag|spherical] [--gmm-init R]] [--gmm-sweep LO:HI[:STEP]]
+        [--dbscan EPS [--dbscan-min M]] [--dbscan-sweep E1,E2,..]
 
 With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
 device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
@@ -27,7 +28,13 @@ With --gmm K a Gaussian mixture with K components is fitted to the embeddings an
 (VAE.gmm: --gmm-cov covariances, the best of --gmm-init restarts from k-means labels, ONE device call each after the k-means calls): the
 same lines per run for its hard labels, and the columns cls_gmm_* / logp_gmm_* (a row's component and its log-density) in the CSV.  With
 --gmm-sweep LO:HI[:STEP] the table "k BIC AIC lower_bound" follows per input (VAE.sweep_gmm), the k with the smallest BIC marked with *.
-Without these flags the output is what it was."""
+Without these flags the output is what it was.
+
+With --dbscan EPS the same runs follow with density clustering (VAE.dbscan: --dbscan-min rows within EPS make a row core, ONE device call
+each; no cluster count, rows of no cluster are noise): the purity lines over the clustered rows, "N clusters, M noise rows", with --quality
+the scores over the clustered rows, and the columns cls_db_* / dist_db_* in the CSV (noise: -1 and nan).  With --dbscan-sweep E1,E2,.. the
+table "eps clusters noise silhouette CH DB" follows per input and metric (VAE.sweep_eps: one dbscan call per eps, ONE silhouette call over
+all that can be scored), the eps with the largest silhouette marked with *.  Without these flags the output is what it was."""
 import argparse
 import csv
 
@@ -37,6 +44,7 @@ RUNS = (('euc', 'euclidean', 'sqeuclidean', False), ('euc_sp', 'euclidean', 'sqe
         ('cos_sp', 'cosine', 'cosine', True))
 COLUMNS = "post topic labels cls_euc dist_euc cls_euc_sp dist_euc_sp cls_cos dist_cos cls_cos_sp dist_cos_sp".split()
 KM_COLUMNS = "cls_km_euc dist_km_euc cls_km_euc_sp dist_km_euc_sp cls_km_cos dist_km_cos cls_km_cos_sp dist_km_cos_sp".split()      # with --kmeans
+DB_COLUMNS = "cls_db_euc dist_db_euc cls_db_euc_sp dist_db_euc_sp cls_db_cos dist_db_cos cls_db_cos_sp dist_db_cos_sp".split()      # with --dbscan
 GMM_RUNS = (('z', False), ('z_sp', True))
 GMM_COLUMNS = "cls_gmm_z logp_gmm_z cls_gmm_z_sp logp_gmm_z_sp".split()      # with --gmm
 
@@ -78,12 +86,30 @@ def gmm_sweep_lines(vae, x, name, ks, covariance, n_init, seed):
     return lines
 
 
+def dbscan_lines(res, topics, order):
+    """the lines of --dbscan for one run: the purity listing over the rows that are in a cluster, then the counts"""
+    on = res['labels'] >= 0
+    lines = purity_lines(res['labels'][on], topics[on], order)[:-1] if on.any() else []
+    return lines + ["%d clusters, %d noise rows" % (res['n_clusters'], res['n_noise'])]
+
+
+def eps_sweep_lines(vae, x, name, metric, eps_list, min_samples):
+    """the table of --dbscan-sweep for one input and metric"""
+    t = vae.sweep_eps(x, eps_list, min_samples, metric)
+    lines = ["dbscan sweep %s" % name, "eps clusters noise silhouette CH DB"]
+    for e, k, n, s, ch, db in zip(t['eps'], t['n_clusters'], t['n_noise'], t['score'], t['ch'], t['db']):
+        lines.append("%g %d %d %.4f %.2f %.4f%s" % (e, k, n, s, ch, db, " *" if t['best'] is not None and e == t['best'] else ""))
+    return lines
+
+
 def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10, quality=False, sweep=None, gmm=None, gmm_cov='diag',
-             gmm_init=1, gmm_sweep=None):
+             gmm_init=1, gmm_sweep=None, dbscan=None, dbscan_min=5, dbscan_sweep=None):
     """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed.  kmeans = k adds the
     same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*.  quality: a line of scores behind
     every run; sweep = [k ..]: the k-means quality table per input and metric.  gmm = k adds a mixture with k components per input
-    (VAE.gmm, gmm_cov covariances, gmm_init restarts): cls_gmm_* / logp_gmm_*; gmm_sweep = [k ..]: the BIC / AIC table per input"""
+    (VAE.gmm, gmm_cov covariances, gmm_init restarts): cls_gmm_* / logp_gmm_*; gmm_sweep = [k ..]: the BIC / AIC table per input.
+    dbscan = eps adds the same runs with density clustering (VAE.dbscan, dbscan_min rows make a core row): cls_db_* / dist_db_*;
+    dbscan_sweep = [eps ..]: the quality table per input and metric"""
     from . import affinity
     from .eval_cluster import split_labels
     topics = np.array([p[0] for p in split_labels(labels)])
@@ -132,6 +158,20 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_ini
         x = z_sp if sampled else z
         if x is not None:
             lines += gmm_sweep_lines(vae, x, name, gmm_sweep, gmm_cov, gmm_init, seed)
+    for name, metric, dist, sampled in RUNS if dbscan else ():
+        x = z_sp if sampled else z
+        if x is None:
+            continue
+        res = vae.dbscan(x, dbscan, dbscan_min, metric)
+        lines += dbscan_lines(res, topics, order)
+        if quality:
+            lines.append(quality_line(vae, x, res['labels'], metric))
+        cols['cls_db_' + name] = res['labels']
+        cols['dist_db_' + name] = np.where(res['labels'] >= 0, affinity.dist_to_centroids(x, res['labels'], dist), np.nan)
+    for name, metric, dist, sampled in RUNS if dbscan_sweep else ():
+        x = z_sp if sampled else z
+        if x is not None:
+            lines += eps_sweep_lines(vae, x, name, metric, dbscan_sweep, dbscan_min)
     return cols, lines
 
 
@@ -148,7 +188,7 @@ def embed(vae, z, labels, out, plot=None, perplexity=40.0, max_iter=20000, seed=
 
 def write_csv(path, posts, topics, labels, cols):
     """eval_clustering_explorative.py:121-132: the id, then the columns in the reference's order (those of absent runs left out)"""
-    names = [c for c in COLUMNS + KM_COLUMNS + GMM_COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
+    names = [c for c in COLUMNS + KM_COLUMNS + GMM_COLUMNS + DB_COLUMNS if c in ('post', 'topic', 'labels') or c in cols]
     data = dict(cols, post=posts, topic=topics, labels=labels)
     with open(path, 'w', newline='') as f:
         w = csv.writer(f)
@@ -178,6 +218,24 @@ def _sweep(text):
     return ks
 
 
+def _eps(text):
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not (v > 0 and v < float('inf')):
+        raise argparse.ArgumentTypeError("must be a finite number > 0, got %r" % (text,))
+    return v
+
+
+def _eps_list(text):
+    """E1,E2,.. -> [E1, E2 ..]"""
+    vals = [_eps(t) for t in text.split(',')]
+    if len(vals) > 64:
+        raise argparse.ArgumentTypeError("at most 64 values of eps per sweep, got %d" % len(vals))
+    return vals
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--inputs', required=True, help=".npy (n, dim) float32 embeddings (eval_embed's output)")
@@ -198,6 +256,9 @@ def build_parser():
     ap.add_argument('--gmm-cov', choices=('diag', 'spherical'), default='diag', help="with --gmm / --gmm-sweep: the covariances")
     ap.add_argument('--gmm-init', type=_positive, default=1, help="with --gmm / --gmm-sweep: restarts, the best of which is listed")
     ap.add_argument('--gmm-sweep', type=_sweep, default=None, help="LO:HI[:STEP]: the BIC / AIC table of mixtures for these k per input (VAE.sweep_gmm)")
+    ap.add_argument('--dbscan', type=_eps, default=None, help="also cluster by density with this eps (VAE.dbscan)")
+    ap.add_argument('--dbscan-min', type=_positive, default=5, help="with --dbscan / --dbscan-sweep: the rows within eps, itself included, that make a row core")
+    ap.add_argument('--dbscan-sweep', type=_eps_list, default=None, help="E1,E2,..: the density-clustering quality table for these eps per input and metric (VAE.sweep_eps)")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -217,7 +278,7 @@ def main(argv=None):
     if A.tsne:
         print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
     cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init, A.quality, A.sweep, A.gmm, A.gmm_cov, A.gmm_init,
-                           A.gmm_sweep)
+                           A.gmm_sweep, A.dbscan, A.dbscan_min, A.dbscan_sweep)
     for line in lines:
         print(line)
     if A.csv:

@@ -23,6 +23,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) Gaussian mixture of latent rows (BIC, AIC)   -> VAE.gmm(z, k, ...) / VAE.gmm_score(z, model) / VAE.sweep_gmm(z, ks) / generate(prior=)
     (new) exact t-SNE of latent rows                   -> VAE.tsne(z, perplexity, ...) / tsne(vae, z, ...)
     (new) silhouette, CH and DB of many labelings      -> VAE.silhouette(z, labels, metric) / VAE.sweep_k(z, ks) / silhouette(vae, z, ...)
+    (new) density clustering of latent rows (DBSCAN)   -> VAE.dbscan(z, eps, min_samples) / VAE.kdist(z, k) / VAE.sweep_eps(z, eps_list)
 """
 import ctypes as C
 
@@ -717,6 +718,24 @@ class VAE:
         from . import gmm
         return gmm.sweep_gmm(self, z, ks, **kw)
 
+    def dbscan(self, z, eps, min_samples=5, metric='euclidean', max_rounds=0):
+        """sklearn's DBSCAN(algorithm='brute') of the rows of z in ONE device call (include/argsim_vae.h, avae_dbscan): no cluster count,
+        noise rows at -1, labels an exact function of the rows.  metric: 'euclidean' or 'cosine'
+        -> dict(labels, core_sample_indices, n_clusters, n_noise, n_border, counts, rounds) (argsim_amd/dbscan.py)"""
+        from . import dbscan
+        return dbscan.dbscan(self, z, eps, min_samples, metric, max_rounds)
+
+    def kdist(self, z, k, metric='euclidean'):
+        """the ascending curve of every row's distance to its k-th nearest other row: eps is read off its knee"""
+        from . import dbscan
+        return dbscan.kdist(self, z, k, metric)
+
+    def sweep_eps(self, z, eps_list, min_samples=5, metric='euclidean'):
+        """one dbscan call per eps, then ONE silhouette call over the labelings that can be scored (noise left out)
+        -> dict(eps, n_clusters, n_noise, score, ch, db, labels, best)"""
+        from . import dbscan
+        return dbscan.sweep_eps(self, z, eps_list, min_samples, metric)
+
 
 # avae_debug_step_route: seven scalars, then (form, T, C, pipe, ring) per kind of GRU launch, in this order
 ROUTE_GRU = ('enc_fwd', 'enc_bwd', 'top_fwd', 'top_bwd', 'dec_fwd', 'dec_bwd')
@@ -1001,3 +1020,18 @@ def gmm_score(vae, z, model, return_resp=False):
 def sweep_gmm(vae, z, ks, **kw):
     """functional form of VAE.sweep_gmm"""
     return vae.sweep_gmm(z, ks, **kw)
+
+
+def dbscan(vae, z, eps, min_samples=5, metric='euclidean', max_rounds=0):
+    """functional form of VAE.dbscan"""
+    return vae.dbscan(z, eps, min_samples, metric, max_rounds)
+
+
+def kdist(vae, z, k, metric='euclidean'):
+    """functional form of VAE.kdist"""
+    return vae.kdist(z, k, metric)
+
+
+def sweep_eps(vae, z, eps_list, min_samples=5, metric='euclidean'):
+    """functional form of VAE.sweep_eps"""
+    return vae.sweep_eps(z, eps_list, min_samples, metric)

@@ -822,6 +822,48 @@ int  avae_silhouette(avae_handle h, const float* x /* (N, dim) device */, int32_
                      int32_t* nearest /* optional (L, N) */, int32_t* count /* optional (L, Kmax) */,
                      double* cluster_mean /* optional (L, Kmax) */, double* index /* optional (L, 2): CH, DB */);
 
+/* ---- density clustering of latent rows ----------------------------------------------------------------------------------------------
+ * DBSCAN of N rows in ONE call: no cluster count, clusters of any shape, and the rows that belong to no cluster (-1, which
+ * avae_silhouette takes as "left out").  The labels are an exact, order-free function of the rows: scikit-learn's
+ * DBSCAN(algorithm='brute') gives the same ones.  Everything is enqueued on the handle's stream without a synchronisation or a host
+ * read; every stop is decided on the device.  Every pointer is device memory.  (The float64 restatement is tests/dbscan_ref.py.)
+ *   pair value p(i, j) = sum_e (v_i[e] - v_j[e])^2 in double, e ascending for every tile shape; v = double(x), for metric 1 divided by
+ *              the row's double norm sqrt(sum_e x_e^2) (a zero row stays zero).  p is symmetric by construction.  Metric 1: a pair
+ *              with a zero row and i != j has p = 2 (distance 1, sklearn's value); p(i, i) = 0.
+ *   within eps metric 0: p <= eps * eps (the product formed once, in double); metric 1: p <= 2 eps, that is 1 - cos <= eps.  Inclusive.
+ *   core       row i is core when count[i] >= min_samples; count[i] = the rows within eps of i, itself included.
+ *   clusters   core rows within eps of each other are in the same cluster (the transitive closure over core rows only); clusters are
+ *              numbered 0, 1, .. in ascending order of their lowest core row.  A non-core row with a core row within eps takes the
+ *              lowest cluster number among those core rows (a border row; it never joins two clusters); every other non-core row is
+ *              noise: -1.
+ *   outputs    label (N); count (N), optional; stat (8) = clusters, core rows, border rows, noise rows, rounds used, verify flag, 0, 0.
+ *   rounds     the components are found in rounds of hook and pointer jump over a bit matrix of the pairs within eps; max_rounds
+ *              rounds are enqueued (0: the planner's default, 2 (ceil(log2 N) + 1)), and those behind the fixed point return at once.
+ *              A last pass walks every core-core pair: verify flag 0 = each joins equal labels; 1 = not converged within max_rounds,
+ *              label then holds a partition that is too fine.  Call again with a larger max_rounds.
+ *   range      1 <= N <= 2^17; dim a multiple of 4 in [4, 1024]; x 16-byte aligned; min_samples >= 1; eps > 0 and finite;
+ *              0 <= max_rounds <= 4096.
+ *   not finite values in the rows are NOT checked: a pair whose p is NaN is not within eps.  Never a hang, never a write outside the outputs.
+ *   bits       no float atomics.  label, count and stat are a function of the arguments alone: they do not depend on how the planner
+ *              tiles the pairs (option dbscan_chunk) nor on the interleaving of the hooks (integer minima).
+ *   workspace  8 N ceil(N / 64) bytes of bit matrix (2 GiB at N = 2^17: why N stops there), 16 N of parents and numbers, 8 ceil(N / 64),
+ *              4 (max_rounds + 1) + 16, 4 N unless count is given, 8 N of norms for the cosine; + 256-byte rounding, reserved once
+ *              per call.
+ * Errors (text through avae_last_error; checked on the host, before any launch; each with its own text): a null dc, x, label or stat;
+ * N, dim, metric, min_samples, max_rounds or eps out of range; x not 16-byte aligned; reserved != 0; a workspace the device cannot give
+ * (the text names its size).
+ * Option dbscan_chunk (avae_set_option; a test aid): the low 8 bits of a value > 0 cap the rows TI of a tile (the largest of 4 .. 64
+ * within them; 0: the planner's), the bits above give the column tiles of a part (0: the planner's).  Same bits for every value.    */
+typedef struct avae_dbscan_config {
+    int32_t metric;       /* 0 euclidean, 1 cosine */
+    int32_t min_samples;  /* >= 1 */
+    int32_t max_rounds;   /* 0: the planner's default */
+    int32_t reserved;     /* 0 */
+    double  eps;          /* > 0, finite */
+} avae_dbscan_config;
+int  avae_dbscan(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_dbscan_config* dc,
+                 int32_t* label /* (N) */, int32_t* count /* optional (N) */, int32_t* stat /* (8) */);
+
 #ifdef __cplusplus
 }
 #endif
