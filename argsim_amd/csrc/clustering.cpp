@@ -1,7 +1,7 @@
 // clustering.cpp -- clustering of latent rows: the plan, the workspace and the launch sequences of avae_ward and avae_ward_cut
 // (kernels: ward.hip), of avae_affinity (kernels: affinity.hip), of avae_tsne (kernels: tsne.hip, the distances affinity.hip's) and of
 // avae_kmeans (kernels: kmeans.hip), of avae_gmm_fit and avae_gmm_score (kernels: gmm.hip), of avae_silhouette (kernels: silhouette.hip)
-// and of avae_dbscan (kernels: dbscan.hip).
+// of avae_dbscan (kernels: dbscan.hip), and of avae_pca_fit and avae_pca_transform (kernels: pca.hip).
 // Contract: include/argsim_vae.h.
 #include "ctx.h"
 
@@ -453,6 +453,65 @@ int avae_dbscan(avae_handle h, const float* x, int32_t N, int32_t dim, const ava
     // every round is enqueued; a launch that finds the fixed point reached returns at once.  Never a synchronisation
     for (int t = 0; t < rounds; ++t) AV_CHECK(db_round(h->stream, a, t));
     AV_CHECK(db_finish(h->stream, a, stat));
+    return 0;
+}
+
+int avae_pca_fit(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_pca_config* pc, double* mean, double* var, double* comp,
+                 int32_t* stat)
+{
+    if (!h) return 1;
+    if (!pc) return fail(h, "pca config is null");
+    if (!x) return fail(h, "pca: x is null");
+    if (!mean) return fail(h, "pca: mean is null");
+    if (!var) return fail(h, "pca: var is null");
+    if (!comp) return fail(h, "pca: comp is null");
+    if (!stat) return fail(h, "pca: stat is null");
+    if (N < 2 || N > kPcaMaxN) return fail(h, "pca: N must be in [2, 2^22]");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "pca: dim must be a multiple of 4 in [4, 1024]");
+    if (pc->pad < 0 || pc->pad > 3 || pc->pad >= dim) return fail(h, "pca: pad must be in [0, 3] and below dim");
+    if (pc->max_sweeps < 0 || pc->max_sweeps > kPcaMaxSweeps) return fail(h, "pca: max_sweeps must be in [0, 256]");
+    if ((uintptr_t)x & 15) return fail(h, "pca: x must be 16-byte aligned");
+    if (pc->reserved != 0 || pc->reserved2 != 0) return fail(h, "pca: the reserved fields must be 0");
+    if (h->pca_form == 1 && dim - pc->pad > kPcaResident) return fail(h, "pca: pca_form 1 (the resident solve) needs dim - pad <= 128");
+    AV_CHECK(hipSetDevice(h->device));
+    int cus = 0;
+    AV_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    const PcaPlan plan = pca_plan(N, dim, pc->pad, h->pca_chunk, h->pca_form, cus);
+    const int sweeps = pc->max_sweeps > 0 ? pc->max_sweeps : plan.sweeps;
+    // Workspace, every buffer on a 256-byte boundary: the state, the chunks' column sums (chunks, dim), their partial
+    // tiles (chunks, pairs, 64, 64), the matrix and the rotations (dreal, dreal) each -- twice each for the launched solve
+    PcaArgs a{};
+    a.x = x; a.N = N; a.dim = dim; a.dreal = plan.dreal; a.mean = mean;
+    const size_t nn = (size_t)plan.dreal * plan.dreal;
+    AV_TRY(place_ws(h, "pca", [&](Bump& b) {
+        a.st = b.take<PcaState>(1);
+        a.msum = b.take<double>((size_t)plan.chunks * dim);
+        a.part = b.take<double>((size_t)plan.chunks * plan.pairs * kPcaT * kPcaT);
+        a.A[0] = b.take<double>(nn); a.A[1] = b.take<double>(nn);      // [1]: the launched solve's other buffer, the resident one's staging
+        a.Vt[0] = b.take<double>(nn); a.Vt[1] = b.opt<double>(plan.form == 2, nn);
+    }));
+    AV_CHECK(hipMemsetAsync(a.st, 0, sizeof(PcaState), h->stream));
+    AV_CHECK(pca_cov(h->stream, a, plan));
+    AV_CHECK(pca_solve(h->stream, a, plan, sweeps));
+    AV_CHECK(pca_finish(h->stream, a, plan, var, comp, stat));
+    return 0;
+}
+
+int avae_pca_transform(avae_handle h, const float* x, int32_t n, int32_t dim, const double* mean, const double* comp, const double* scale,
+                       int32_t k, float* y)
+{
+    if (!h) return 1;
+    if (!x) return fail(h, "pca transform: x is null");
+    if (!mean) return fail(h, "pca transform: mean is null");
+    if (!comp) return fail(h, "pca transform: comp is null");
+    if (!y) return fail(h, "pca transform: y is null");
+    if (n < 1 || n > kPcaMaxN) return fail(h, "pca transform: n must be in [1, 2^22]");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "pca transform: dim must be a multiple of 4 in [4, 1024]");
+    if (k < 1 || k > dim) return fail(h, "pca transform: k must be in [1, dim]");
+    if ((uintptr_t)x & 15) return fail(h, "pca transform: x must be 16-byte aligned");
+    AV_CHECK(hipSetDevice(h->device));
+    const PcaPlan plan = pca_plan(n, dim, 0, h->pca_chunk, 2, 1);
+    AV_CHECK(pca_transform(h->stream, x, n, dim, mean, comp, scale, k, y, plan.trows));
     return 0;
 }
 

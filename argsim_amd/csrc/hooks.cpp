@@ -517,4 +517,23 @@ int avae_debug_dbscan_plan(int32_t N, int32_t dim, int32_t chunk_opt, int32_t cu
     return 0;
 }
 
+// test hook: pca_plan(N, dim, pad, chunk_opt, form_opt, cus) of avae_pca_fit; out = dreal, tiles, tile pairs, rows of a chunk, chunks, form,
+// rounds of a sweep, the default max_sweeps, the launches of a call with it, the LDS bytes of the solve, the rows of a transform tile, then
+// the workspace bytes as two 32-bit halves (low, high).  Host arithmetic only: callable without a GPU.
+int avae_debug_pca_plan(int32_t N, int32_t dim, int32_t pad, int32_t chunk_opt, int32_t form_opt, int32_t cus, int32_t* out)
+{
+    if (!out || N < 2 || N > kPcaMaxN || dim < 4 || dim > 1024 || (dim & 3) || pad < 0 || pad > 3 || pad >= dim || chunk_opt < 0 || form_opt < 0 ||
+        form_opt > 2 || cus < 1 || (form_opt == 1 && dim - pad > kPcaResident))
+        return 1;
+    const PcaPlan p = pca_plan(N, dim, pad, chunk_opt, form_opt, cus);
+    const int32_t f[11] = {p.dreal, p.tiles, p.pairs, p.rows, p.chunks, p.form, p.rounds, p.sweeps, p.launches, p.lds, p.trows};
+    std::copy(f, f + 11, out);
+    const size_t nn = (size_t)p.dreal * p.dreal;
+    Bump b{nullptr};
+    b.take<PcaState>(1); b.take<double>((size_t)p.chunks * dim); b.take<double>((size_t)p.chunks * p.pairs * kPcaT * kPcaT);
+    for (int q = 0; q < (p.form == 2 ? 4 : 3); ++q) b.take<double>(nn);
+    out[11] = (int32_t)(b.off & 0xffffffffu); out[12] = (int32_t)(b.off >> 32);
+    return 0;
+}
+
 }  // extern "C"

@@ -656,6 +656,36 @@ hipError_t db_core(hipStream_t st, const DbArgs& a);                     // the 
 hipError_t db_round(hipStream_t st, const DbArgs& a, int t);             // two launches: hook, jump
 hipError_t db_finish(hipStream_t st, const DbArgs& a, int32_t* stat);    // verify, number, label, border, stat
 
+// ---------------------------------------------------------------- principal components of latent rows (pca.hip)
+// One set of N rows per call (contract: include/argsim_vae.h, avae_pca_fit / avae_pca_transform).  Every buffer is workspace laid out by
+// the caller (clustering.cpp) or the caller's own output; st is zero-filled before the first launch.
+constexpr int kPcaMaxN = 1 << 22;
+constexpr int kPcaT = 64;             // columns of a covariance tile
+constexpr int kPcaDK = 16;            // rows per LDS stage of the covariance
+constexpr int kPcaResident = 128;     // the largest dreal whose matrix one workgroup keeps in LDS (128 KB of the 160)
+constexpr int kPcaMaxSweeps = 256;
+// the default max_sweeps: twice the most sweeps tests/pca_ref.py's model of the rule takes over the test cases and a 1024-column case
+// (tests/test_pca.py measures it again)
+constexpr int kPcaSweeps = 58;
+struct PcaPlan { int dreal, tiles, pairs, rows, chunks, form, rounds, sweeps, launches, lds, trows; };
+struct PcaState { double thr; int sweeps, converged, rotations, done, rot_sweep, pad; };
+struct PcaArgs {
+    const float* x; int N, dim, dreal;
+    double* msum;                             // (chunks, dim) column sums of the row chunks
+    double* mean;                             // (dim) the caller's: the leading dreal are written, and read by the covariance
+    double* part;                             // (chunks, pairs, 64, 64) partial tiles of the covariance
+    double* A[2];                             // (dreal, dreal) the matrix; the launched solve writes the two in turn
+    double* Vt[2];                            // (dreal, dreal) row j = column j of the accumulated rotations
+    PcaState* st;
+};
+size_t pca_resident_lds(int dreal);
+PcaPlan pca_plan(int N, int dim, int pad, int chunk_opt, int form_opt, int cus);
+hipError_t pca_cov(hipStream_t st, const PcaArgs& a, const PcaPlan& p);                      // mean and covariance: four launches
+hipError_t pca_solve(hipStream_t st, const PcaArgs& a, const PcaPlan& p, int max_sweeps);    // init, then one launch or one per round
+hipError_t pca_finish(hipStream_t st, const PcaArgs& a, const PcaPlan& p, double* var, double* comp, int32_t* stat);
+hipError_t pca_transform(hipStream_t st, const float* x, int n, int dim, const double* mean, const double* comp, const double* scale, int k,
+                         float* y, int trows);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

@@ -8,7 +8,7 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
         [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]] [--kmeans K [--kmeans-init 10]]
         [--quality] [--sweep LO:HI[:STEP]] [--gmm K [--gmm-cov diag|spherical] [--gmm-init R]] [--gmm-sweep LO:HI[:STEP]]
-        [--dbscan EPS [--dbscan-min M]] [--dbscan-sweep E1,E2,..]
+        [--dbscan EPS [--dbscan-min M]] [--dbscan-sweep E1,E2,..] [--pca K [--pca-whiten]]
 
 With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
 device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
@@ -34,7 +34,12 @@ With --dbscan EPS the same runs follow with density clustering (VAE.dbscan: --db
 each; no cluster count, rows of no cluster are noise): the purity lines over the clustered rows, "N clusters, M noise rows", with --quality
 the scores over the clustered rows, and the columns cls_db_* / dist_db_* in the CSV (noise: -1 and nan).  With --dbscan-sweep E1,E2,.. the
 table "eps clusters noise silhouette CH DB" follows per input and metric (VAE.sweep_eps: one dbscan call per eps, ONE silhouette call over
-all that can be scored), the eps with the largest silhouette marked with *.  Without these flags the output is what it was."""
+all that can be scored), the eps with the largest silhouette marked with *.  Without these flags the output is what it was.
+
+With --pca K (a count, or a fraction in (0, 1) of the variance to keep) the embeddings and, where given, those of the sampled segmentation
+are first reduced to their leading principal components (VAE.pca_reduce: ONE device call for the fit, one for the projection; --pca-whiten
+scales them to unit variance): per input the table "component variance ratio cumulative" and the line "effective dimension %.2f of D,
+rank R, kept K", and EVERY run above is made on the reduced rows.  Without the flag nothing changes."""
 import argparse
 import csv
 
@@ -102,19 +107,38 @@ def eps_sweep_lines(vae, x, name, metric, eps_list, min_samples):
     return lines
 
 
+def pca_lines(model, name):
+    """the table of --pca for one input"""
+    lines = ["pca %s" % name, "component variance ratio cumulative"]
+    cum = np.cumsum(model['explained_variance_ratio'])
+    for c, (v, r, s) in enumerate(zip(model['explained_variance'], model['explained_variance_ratio'], cum)):
+        lines.append("%d %.6g %.4f %.4f" % (c, v, r, s))
+    return lines + ["effective dimension %.2f of %d, rank %d, kept %d" % (model['effective_dim'], len(model['mean']), model['rank'],
+                                                                           len(model['explained_variance']))]
+
+
 def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10, quality=False, sweep=None, gmm=None, gmm_cov='diag',
-             gmm_init=1, gmm_sweep=None, dbscan=None, dbscan_min=5, dbscan_sweep=None):
+             gmm_init=1, gmm_sweep=None, dbscan=None, dbscan_min=5, dbscan_sweep=None, pca=None, pca_whiten=False):
     """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed.  kmeans = k adds the
     same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*.  quality: a line of scores behind
     every run; sweep = [k ..]: the k-means quality table per input and metric.  gmm = k adds a mixture with k components per input
     (VAE.gmm, gmm_cov covariances, gmm_init restarts): cls_gmm_* / logp_gmm_*; gmm_sweep = [k ..]: the BIC / AIC table per input.
     dbscan = eps adds the same runs with density clustering (VAE.dbscan, dbscan_min rows make a core row): cls_db_* / dist_db_*;
-    dbscan_sweep = [eps ..]: the quality table per input and metric"""
+    dbscan_sweep = [eps ..]: the quality table per input and metric.  pca = k (a count or a fraction): every run is made on the rows
+    reduced to their leading principal components (VAE.pca_reduce, pca_whiten: to unit variance), the variance table first"""
     from . import affinity
     from .eval_cluster import split_labels
     topics = np.array([p[0] for p in split_labels(labels)])
     order = list(dict.fromkeys(topics.tolist()))
     cols, lines = {}, []
+    if pca:
+        reduced = []
+        for name, x in (('z', z), ('z_sp', z_sp)):
+            if x is not None:
+                x, model = vae.pca_reduce(x, pca, pca_whiten)
+                lines += pca_lines(model, name)
+            reduced.append(x)
+        z, z_sp = reduced
     for name, metric, dist, sampled in RUNS:
         x = z_sp if sampled else z
         if x is None:
@@ -228,6 +252,23 @@ def _eps(text):
     return v
 
 
+def _components(text):
+    """a count >= 1, or a fraction in (0, 1)"""
+    try:
+        v = int(text)
+    except ValueError:
+        try:
+            v = float(text)
+        except ValueError:
+            v = -1.0
+        if not 0.0 < v < 1.0:
+            raise argparse.ArgumentTypeError("must be an integer >= 1 or a fraction in (0, 1), got %r" % (text,))
+        return v
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be an integer >= 1 or a fraction in (0, 1), got %r" % (text,))
+    return v
+
+
 def _eps_list(text):
     """E1,E2,.. -> [E1, E2 ..]"""
     vals = [_eps(t) for t in text.split(',')]
@@ -259,6 +300,8 @@ def build_parser():
     ap.add_argument('--dbscan', type=_eps, default=None, help="also cluster by density with this eps (VAE.dbscan)")
     ap.add_argument('--dbscan-min', type=_positive, default=5, help="with --dbscan / --dbscan-sweep: the rows within eps, itself included, that make a row core")
     ap.add_argument('--dbscan-sweep', type=_eps_list, default=None, help="E1,E2,..: the density-clustering quality table for these eps per input and metric (VAE.sweep_eps)")
+    ap.add_argument('--pca', type=_components, default=None, help="K or a fraction: first reduce the inputs to their leading principal components (VAE.pca_reduce); every run is made on the reduced rows")
+    ap.add_argument('--pca-whiten', action='store_true', help="with --pca: scale the components to unit variance")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -278,7 +321,7 @@ def main(argv=None):
     if A.tsne:
         print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
     cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init, A.quality, A.sweep, A.gmm, A.gmm_cov, A.gmm_init,
-                           A.gmm_sweep, A.dbscan, A.dbscan_min, A.dbscan_sweep)
+                           A.gmm_sweep, A.dbscan, A.dbscan_min, A.dbscan_sweep, A.pca, A.pca_whiten)
     for line in lines:
         print(line)
     if A.csv:

@@ -24,6 +24,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) exact t-SNE of latent rows                   -> VAE.tsne(z, perplexity, ...) / tsne(vae, z, ...)
     (new) silhouette, CH and DB of many labelings      -> VAE.silhouette(z, labels, metric) / VAE.sweep_k(z, ks) / silhouette(vae, z, ...)
     (new) density clustering of latent rows (DBSCAN)   -> VAE.dbscan(z, eps, min_samples) / VAE.kdist(z, k) / VAE.sweep_eps(z, eps_list)
+    (new) principal components of latent rows (PCA)    -> VAE.pca(z, n_components, whiten) / VAE.pca_transform(z, model) / VAE.pca_reduce(z, k)
 """
 import ctypes as C
 
@@ -736,6 +737,24 @@ class VAE:
         from . import dbscan
         return dbscan.sweep_eps(self, z, eps_list, min_samples, metric)
 
+    def pca(self, z, n_components=None, whiten=False, max_sweeps=0):
+        """principal components of the rows of z in ONE device call (include/argsim_vae.h, avae_pca_fit): mean, covariance and Jacobi
+        eigen-solve in double, scikit-learn's signs and variances
+        -> dict(mean, components, explained_variance, explained_variance_ratio, singular_values, noise_variance, effective_dim,
+        n_samples, rank, sweeps, whiten) (argsim_amd/pca.py)"""
+        from . import pca
+        return pca.pca(self, z, n_components, whiten, max_sweeps)
+
+    def pca_transform(self, z, model):
+        """the rows of z in the model's components (whitened if the model says so) -> (n, k) float32"""
+        from . import pca
+        return pca.transform(self, z, model)
+
+    def pca_reduce(self, z, k, whiten=False):
+        """fit + transform: the leading k principal directions of the rows of z -> (y (N, k) float32, model)"""
+        from . import pca
+        return pca.reduce(self, z, k, whiten)
+
 
 # avae_debug_step_route: seven scalars, then (form, T, C, pipe, ring) per kind of GRU launch, in this order
 ROUTE_GRU = ('enc_fwd', 'enc_bwd', 'top_fwd', 'top_bwd', 'dec_fwd', 'dec_bwd')
@@ -1035,3 +1054,18 @@ def kdist(vae, z, k, metric='euclidean'):
 def sweep_eps(vae, z, eps_list, min_samples=5, metric='euclidean'):
     """functional form of VAE.sweep_eps"""
     return vae.sweep_eps(z, eps_list, min_samples, metric)
+
+
+def pca(vae, z, n_components=None, whiten=False, max_sweeps=0):
+    """functional form of VAE.pca"""
+    return vae.pca(z, n_components, whiten, max_sweeps)
+
+
+def pca_transform(vae, z, model):
+    """functional form of VAE.pca_transform"""
+    return vae.pca_transform(z, model)
+
+
+def pca_reduce(vae, z, k, whiten=False):
+    """functional form of VAE.pca_reduce"""
+    return vae.pca_reduce(z, k, whiten)

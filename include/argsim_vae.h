@@ -864,6 +864,49 @@ typedef struct avae_dbscan_config {
 int  avae_dbscan(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_dbscan_config* dc,
                  int32_t* label /* (N) */, int32_t* count /* optional (N) */, int32_t* stat /* (8) */);
 
+/* ---- principal components of latent rows ---------------------------------------------------------------------------------------------
+ * PCA of N rows in ONE call: the mean, the covariance and its eigen-decomposition in double, everything enqueued on the handle's stream
+ * without a synchronisation or a host read; every stop is decided on the device.  Every pointer is device memory.  (The float64
+ * restatement is tests/pca_ref.py.)  dreal = dim - pad: the last pad columns of the rows are padding and are ignored.
+ *   mean       the column means in double (the fp32 rows are exact as doubles).
+ *   covariance C = sum_i (x_i - mean)(x_i - mean)^T / (N - 1) in double from the centred rows: two passes over the rows.
+ *   solve      two-sided cyclic Jacobi on the dreal x dreal matrix, the pairs in round-robin order: with m = dreal rounded up to even,
+ *              in round r = 0 .. m - 2 column m - 1 meets column r and every other column j meets (2 r - j) mod (m - 1); a partner
+ *              >= dreal is the bye.  A pair p < q is rotated iff |a_pq| > thr = 2^-52 ||C||_F / dreal (absolute), with
+ *              theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(1 + theta^2)), sign(0) = +1, c = 1 / sqrt(1 + t^2),
+ *              s = t c; afterwards a_pq = 0 exactly, a_pp -= t a_pq, a_qq += t a_pq.  All rotations of a round are read off the
+ *              matrix as it stands at the start of the round and applied together: A <- J^T A J, V <- V J.  The solve stops behind the
+ *              first sweep without a rotation (converged) or behind max_sweeps sweeps (0: the planner's default, 58).
+ *   order      eigenvalues descending, ties the smaller position on the diagonal first; var = the eigenvalues clipped below at 0.
+ *   comp       row c = eigenvector c, its entry of largest magnitude (the first of equals) positive; row stride dim.
+ *   stat (8)   sweeps run, converged 0 / 1, rotations (low 31 bits), rank = the number of var > thr, 0, 0, 0, 0.
+ *   written    the leading dreal entries of mean and var and the leading dreal x dreal block of comp; the rest is left untouched.
+ *   range      2 <= N <= 2^22; dim a multiple of 4 in [4, 1024]; 0 <= pad <= 3, pad < dim; x 16-byte aligned; 0 <= max_sweeps <= 256.
+ *   not finite values in the rows are NOT checked: a pair whose a_pq is NaN is not rotated.  Never a hang, never a write outside the outputs.
+ *   bits       no float atomics; partial sums are merged in ascending chunk order; the outputs are a function of the arguments and of
+ *              option pca_chunk alone, the same for both forms of the solve (option pca_form) and for every call.
+ *   workspace  8 (chunks dim + chunks pairs 4096 + 2 dreal^2) bytes, 4 dreal^2 for the launched solve, + 256-byte rounding; the partial
+ *              tiles are capped at 256 MiB.
+ * avae_pca_transform: y[i][c] = scale_c sum_j (x_ij - mean_j) comp[c][j], c < k, the sum over ALL dim columns in ascending order in
+ * double, rounded once to fp32 (scale null: 1): a value depends on the row and the model alone.  It has no pad: the padding columns of
+ * mean and comp must hold zeros (the Python layer allocates them so).  1 <= n <= 2^22, 1 <= k <= dim.
+ * Errors (text through avae_last_error; checked on the host, before any launch; each with its own text): a null pc, x, mean, var, comp,
+ * stat or y; N, n, dim, pad, max_sweeps or k out of range; x not 16-byte aligned; a reserved field != 0; pca_form 1 with dreal > 128;
+ * a workspace the device cannot give.
+ * Options (avae_set_option; test aids): pca_chunk > 0 caps the rows of a covariance chunk and of a transform tile; pca_form 0 the
+ * planner's solve (resident where dreal <= 128), 1 resident, 2 launched.                                                              */
+typedef struct avae_pca_config {
+    int32_t pad;          /* the last 0..3 columns of the rows are padding */
+    int32_t max_sweeps;   /* 0: the planner's default; else 1..256 */
+    int32_t reserved;     /* 0 */
+    int32_t reserved2;    /* 0 */
+} avae_pca_config;
+int  avae_pca_fit(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_pca_config* pc,
+                  double* mean /* (dim) */, double* var /* (dim) descending */, double* comp /* (dim, dim) row c = component c */,
+                  int32_t* stat /* (8) */);
+int  avae_pca_transform(avae_handle h, const float* x /* (n, dim) device */, int32_t n, int32_t dim, const double* mean /* (dim) */,
+                        const double* comp /* (k, dim) */, const double* scale /* (k) or null */, int32_t k, float* y /* (n, k) */);
+
 #ifdef __cplusplus
 }
 #endif
