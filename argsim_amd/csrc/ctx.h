@@ -114,6 +114,9 @@ struct avae_ctx {
     // fill hint: the real source positions of an earlier call, copied to pinned host memory without a synchronisation (whatever has
     // arrived is read; it only ever decides the LAYOUT, never a value) and the padded positions of the call that issued the copy
     int32_t* hint_dev = nullptr; volatile int32_t* hint_host = nullptr;
+    // what had arrived where the current call began (latch_hint, build_row_orders): every decision of ONE call reads this pair, so a call's own
+    // copy landing while the call is still being enqueued cannot give its forward one hint and its backward another
+    uint64_t hint_seen = 0xffffffffull;
     const int32_t *cnt_src = nullptr, *cnt_tgt = nullptr;     // present-id counts of the last forward (table-fed layers), device
     // The route of the last avae_forward_backward (avae_debug_step_route), noted by the step where it decides (note_gru, model.cpp): the first
     // layers table-fed (use_table), Ws::compact / compact_d / Bx, the BPTT form rs_pick gave, whether the top encoder layer ran its one-job

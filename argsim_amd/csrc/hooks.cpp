@@ -137,6 +137,16 @@ int avae_debug_step_route(avae_handle h, int32_t out[37])
         for (int f = 0; f < 5; ++f) out[7 + 5 * k + f] = r.tab_src < 0 ? -1 : r.gru[k][f];
     return 0;
 }
+// test hook: the row expectations the LAST call left behind (build_compact: what the host expects the compact layout's device-side counts to be
+// -- the fill of an earlier call scaled to the call's rows; they shape the launches of the GEMMs over those counts, gemm_plan's dyn_expect).
+// out = the real source positions, the decoder's real positions, the unmasked decoder tokens; 0 where the call took no layout or nothing had
+// arrived.  Reads host memory only: no launch, no synchronisation.
+int avae_debug_row_expect(avae_handle h, int32_t out[3])
+{
+    if (!h || !out) return 1;
+    for (int i = 0; i < 3; ++i) out[i] = h->expect_ptr[i] ? h->expect_val[i] : 0;
+    return 0;
+}
 // test hook: the per-token cross-entropy (model.py:180 loss_gen_samp) of the LAST avae_forward_backward / avae_train_step -- the
 // TRAIN forward, word dropout and the latent draw live -- copied to out (device memory, max_n floats); *n_out = its token count.
 // (The workspace layout is a pure function of the call geometry, so the array is found again without keeping a pointer.)

@@ -318,10 +318,18 @@ static bool top_one_step(const avae_ctx* h) { return h->enc_top1 && h->cfg.rnn_l
 // The asynchronous fill hint of build_row_orders: real source positions and padded rows of an EARLIER call (no synchronisation;
 // real < 0 or rows <= 0 while nothing has arrived).  Both words in ONE 8-byte load: the copy that lands them is 8 bytes, so a
 // pair is never half of one call and half of another.  Shapes launches only, never a value.
+// The pinned words are read ONCE per call, before the call enqueues a copy of its own (latch_hint): the layout, the row expectations, the
+// BPTT form and the exchange protocol of one call all follow the same earlier call.  (Read where each is decided, the backward of a call
+// saw the call's own fill whenever the copy had landed by then and the previous call's otherwise -- a FULL batch behind a long-tailed one
+// took the compact layout of the one and the BPTT form of the other, by timing.)
 struct FillHint { int32_t real, rows; };
+static void latch_hint(avae_ctx* h)
+{
+    h->hint_seen = h->hint_host ? *reinterpret_cast<const volatile uint64_t*>(h->hint_host) : 0xffffffffull;
+}
 static FillHint fill_hint(const avae_ctx* h)
 {
-    const uint64_t pair = h->hint_host ? *reinterpret_cast<const volatile uint64_t*>(h->hint_host) : 0xffffffffull;
+    const uint64_t pair = h->hint_seen;
     return {(int32_t)(uint32_t)(pair & 0xffffffffull), (int32_t)(uint32_t)(pair >> 32)};
 }
 // the share of the padded source positions that are real, as the host last saw it (1.0 while nothing has arrived)
@@ -367,6 +375,7 @@ void gru_common(avae_ctx* h, const Ws& w, GruArgs& a, int njobs, int S, int B, i
 // with_enc = false: a call that runs the decoder alone (score_rows_dev).
 int build_row_orders(avae_ctx* h, Ws& w, int B, int Ss, int T, bool with_dec, bool with_enc)
 {
+    latch_hint(h);
     if (!h->skip_pad || !h->persistent || w.Bx % 16) return 0;
     if (w.Bx != B && !h->compact) return 0;                   // (phantom rows need the compact layout)
     const int D = h->cfg.dim_emb;

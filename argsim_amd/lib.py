@@ -177,6 +177,7 @@ SIGNATURES = {
     'avae_debug_present_ids': (C.c_int, [_P, C.POINTER(C.c_int32)]),
     'avae_debug_step_route': (C.c_int, [_P, C.POINTER(C.c_int32)]),
     'avae_debug_score_plan':(C.c_int, [_P, C.POINTER(C.c_int32)]),
+    'avae_debug_row_expect': (C.c_int, [_P, C.POINTER(C.c_int32)]),
     'avae_debug_team_batch': (C.c_int, [C.c_int32]),
     'avae_debug_gemm_plan': (C.c_int, [_P, C.c_int32, _P]),
     'avae_debug_gemm_call': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, _P]),

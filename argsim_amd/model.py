@@ -214,6 +214,13 @@ class VAE:
         self._ck(self._l.avae_debug_step_route(self._h, out))
         return route_dict(list(out))
 
+    def row_expect(self):
+        """(source rows, decoder rows, decoder tokens) the last call expected behind its compact layout -- an earlier call's fill scaled to
+        its own rows; zeros where it took no layout (test hook avae_debug_row_expect)"""
+        out = (C.c_int32 * 3)()
+        self._ck(self._l.avae_debug_row_expect(self._h, out))
+        return tuple(out)
+
     def train_ce(self, max_n=1 << 22):
         """per-token cross-entropy (loss_gen_samp, model.py:180) of the last forward_backward / train_step: the TRAIN forward,
         dropout and the latent draw live (test hook)"""

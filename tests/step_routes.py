@@ -7,14 +7,18 @@ VAE.step_route() reports it (Case.route: the expectation lives HERE, as gru_ref.
 tests/test_step_routes.py holds the GRU plans of the table against avae_debug_gru_plan and Bx against avae_debug_team_batch without a GPU;
 every GPU case compares step_route() with its entry before it compares a number.
 
-No case relies on the fill hint (the asynchronous copy that decides compact = 2, bwd_rs = 2 and gru_spec = 2): every case forces those three,
-"default" to what the hint gives once it has arrived (the batch's own fill), except AUTO, which leaves compact and bwd_rs at 2, runs
-twice and is asserted on what the second call took."""
+No case HERE relies on the fill hint (the asynchronous copy that decides compact = 2, bwd_rs = 2 and gru_spec = 2): every case forces those
+three, "default" to what the hint gives once it has arrived (the batch's own fill), except AUTO, which leaves compact and bwd_rs at 2, runs
+twice and is asserted on what the second call took.  What the hint of ANOTHER batch does to a step -- the three options left at their
+defaults, one handle over many shapes -- is tests/step_history.py and tests/test_gpu_step_history.py.
+
+check_step is what a step is held to against the float64 oracle, in both GPU files."""
 import dataclasses
 
 import numpy as np
 
 import helpers
+from helpers import grad_blocks_ratio, grads_bad, rel_l2
 
 D, R, STEP = 512, 32, 20000
 
@@ -172,3 +176,49 @@ def launches(c):
     return [(k, fwd, njobs, steps) for k, fwd, njobs, steps in
             (('enc_fwd', 1, 2, S), ('enc_bwd', 0, 2, S), ('top_fwd', 1, 1, S), ('top_bwd', 0, 1, S), ('dec_fwd', 1, 1, S + 1), ('dec_bwd', 0, 1, S + 1))
             if c.want()[k] is not None]
+
+
+# ------------------------------------------------------------------------------------------ what a step is held to
+#        losses rel, mu / lv abs, CE abs, gradients
+TOLS = {'f32': (2e-5, 2e-5, 1e-4, 2e-4), 'f32s': (2e-5, 2e-5, 1e-4, 2e-4), 'bf16': (1e-2, 3e-2, 6e-2, 5e-2)}
+
+
+def block_ratios(got, want, tol):
+    """{variable: worst block error over its bound}; the embedding: the worse of its 16-row blocks and its single rows"""
+    r = {k: grad_blocks_ratio(got[k], want[k], tol) for k in want}
+    r['embed/embedding'] = max(r['embed/embedding'], grad_blocks_ratio(got['embed/embedding'], want['embed/embedding'], tol, rows=1))
+    return r
+
+
+def check_step(tag, dtype, t, losses, ce, got, mu, lv, head=None):
+    """One training step against the float64 oracle of its batch.  t: the batch's truth (cfg, outs, grads of vt.loss_and_grads in float64, f32:
+    {tolerance: block_ratios of the float32 oracle}); losses, ce (float64), got, mu, lv: losses(), train_ce(), get_grads() and encode() of the
+    step.  Prints a RATIO line per variable and one line that starts with `head` (default: the ROUTE line), then asserts with TOLS[dtype]."""
+    tl, tz, tc, tg = TOLS[dtype]
+    outs, grads = t['outs'], t['grads']
+    ratios = block_ratios(got, grads, tg)
+    for k in grads:
+        print('RATIO %s %s %s block %.4f (float32 oracle %.2g) rel_l2 %.3g' % (tag, dtype, k, ratios[k], t['f32'][tg][k], rel_l2(got[k], grads[k])))
+    worst = max(ratios, key=ratios.get)
+    if head is None:
+        head = 'ROUTE %s %s worst block ratio %.4f %s' % (tag, dtype, ratios[worst], worst)
+    else:
+        head = '%s worst block ratio %.4f (float32 oracle %.2g) %s' % (head, ratios[worst], t['f32'][tg][worst], worst)
+    print('%s; CE %.3g mu %.3g lv %.3g' % (
+        head, np.abs(ce - outs['loss_gen_samp']).max() if ce.shape == outs['loss_gen_samp'].shape else -1.0,
+        np.abs(mu - outs['mu']).max(), np.abs(lv - outs['lv']).max()))
+
+    for got_l, key in zip(losses, ('loss_gen', 'loss_kld', 'loss')):
+        assert abs(got_l - outs[key]) <= tl * abs(outs[key]), (tag, key, got_l, float(outs[key]))
+    assert np.abs(mu - outs['mu']).max() <= tz and np.abs(lv - outs['lv']).max() <= tz, tag
+    assert ce.shape == outs['loss_gen_samp'].shape, (tag, ce.shape)
+    assert np.abs(ce - outs['loss_gen_samp']).max() <= tc, (tag, float(np.abs(ce - outs['loss_gen_samp']).max()))
+    zeros = [k for k in grads if not grads[k].any()]
+    assert zeros == ['encode/rnn%d/bwd/R' % t['cfg']['rnn_layers']], zeros      # (the top layer's backward direction is read at its first step alone, from h = 0)
+    for k in zeros:
+        assert not got[k].any(), (tag, k)
+    bad = {k: rel_l2(got[k], grads[k]) for k in grads if not rel_l2(got[k], grads[k]) <= tg}
+    assert not bad, (tag, bad)
+    bad = grads_bad(got, grads, tg)
+    assert not bad, (tag, bad)
+    return ratios[worst], worst

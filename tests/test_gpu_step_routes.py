@@ -24,14 +24,12 @@ import numpy as np
 import pytest
 
 import step_routes as SR
-from helpers import grad_blocks_ratio, grads_bad, rel_l2
 from oracle import vae_torch as vt
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ('dim_tgt', 'dim_emb', 'dim_rep', 'rnn_layers', 'accelerate', 'learn_rate', 'bos', 'eos')
-#        losses rel, mu / lv abs, CE abs, gradients
-TOLS = {'f32': (2e-5, 2e-5, 1e-4, 2e-4), 'f32s': (2e-5, 2e-5, 1e-4, 2e-4), 'bf16': (1e-2, 3e-2, 6e-2, 5e-2)}
+TOLS = SR.TOLS      # losses rel, mu / lv abs, CE abs, gradients
 _LATCH = []
 _TRUTH = {}         # batch -> the batch, the float64 oracle, the float32 oracle's ratios
 _MODELS = {}        # (batch, dtype) -> VAE; the models of one batch at a time
@@ -47,11 +45,7 @@ def trip(what):
     pytest.fail(what)
 
 
-def block_ratios(got, want, tol):
-    """{variable: worst block error over its bound}; the embedding: the worse of its 16-row blocks and its single rows"""
-    r = {k: grad_blocks_ratio(got[k], want[k], tol) for k in want}
-    r['embed/embedding'] = max(r['embed/embedding'], grad_blocks_ratio(got['embed/embedding'], want['embed/embedding'], tol, rows=1))
-    return r
+block_ratios = SR.block_ratios
 
 
 def truth(name):
@@ -106,32 +100,10 @@ def test_step_route(c):
         trip('%s: non-finite losses %s' % (c.id, (losses,)))
     assert route == c.want(), (c.id, route)
 
-    tl, tz, tc, tg = TOLS[c.dtype]
-    outs, grads = t['outs'], t['grads']
     try:
         ce, got = m.train_ce().astype(np.float64), m.get_grads()
         mu, lv = m.encode(t['src'], return_lv=True)
         torch.cuda.synchronize()
     except Exception as e:          # noqa: BLE001
         trip('%s: %s' % (c.id, e))
-    ratios = block_ratios(got, grads, tg)
-    for k in grads:
-        print('RATIO %s %s %s block %.4f (float32 oracle %.2g) rel_l2 %.3g' % (c.id, c.dtype, k, ratios[k], t['f32'][tg][k], rel_l2(got[k], grads[k])))
-    worst = max(ratios, key=ratios.get)
-    print('ROUTE %s %s worst block ratio %.4f %s; CE %.3g mu %.3g lv %.3g' % (
-        c.id, c.dtype, ratios[worst], worst, np.abs(ce - outs['loss_gen_samp']).max() if ce.shape == outs['loss_gen_samp'].shape else -1.0,
-        np.abs(mu - outs['mu']).max(), np.abs(lv - outs['lv']).max()))
-
-    for got_l, key in zip(losses, ('loss_gen', 'loss_kld', 'loss')):
-        assert abs(got_l - outs[key]) <= tl * abs(outs[key]), (c.id, key, got_l, float(outs[key]))
-    assert np.abs(mu - outs['mu']).max() <= tz and np.abs(lv - outs['lv']).max() <= tz, c.id
-    assert ce.shape == outs['loss_gen_samp'].shape, (c.id, ce.shape)
-    assert np.abs(ce - outs['loss_gen_samp']).max() <= tc, (c.id, float(np.abs(ce - outs['loss_gen_samp']).max()))
-    zeros = [k for k in grads if not grads[k].any()]
-    assert zeros == ['encode/rnn%d/bwd/R' % t['cfg']['rnn_layers']], zeros      # (the top layer's backward direction is read at its first step alone, from h = 0)
-    for k in zeros:
-        assert not got[k].any(), (c.id, k)
-    bad = {k: rel_l2(got[k], grads[k]) for k in grads if not rel_l2(got[k], grads[k]) <= tg}
-    assert not bad, (c.id, bad)
-    bad = grads_bad(got, grads, tg)
-    assert not bad, (c.id, bad)
+    SR.check_step(c.id, c.dtype, t, losses, ce, got, mu, lv)
