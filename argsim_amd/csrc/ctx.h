@@ -85,6 +85,7 @@ struct avae_ctx {
     int sil_chunk = 0;  // avae_silhouette test aid: caps the rows and columns of a tile and the bin columns of a pass (small tests run ragged tiles and several passes); 0: sil_plan decides
     int dbscan_chunk = 0;  // avae_dbscan test aid: the low 8 bits cap the rows of a tile, the bits above give the column tiles of a part (small tests run several tile shapes and parts); 0: db_plan decides
     int pca_chunk = 0;     // avae_pca_fit / avae_pca_transform test aid: caps the rows of a covariance chunk and of a transform tile (small tests run several chunks); 0: pca_plan decides
+    int mmd_chunk = 0;     // avae_mmd test aid: caps the rows of a tile and the relabelings of a pass (small tests run ragged tiles and several passes); 0: mmd_plan decides
     int pca_form = 0;      // avae_pca_fit: 0 the planner's solve, 1 the resident one (one workgroup, dreal <= 128), 2 the launched one (a launch per round); same bits
     int gru_bf16 = 1;     // compute_dtype 1 only: the recurrent product of the team kernels takes bf16 operands too (0: fp32 recurrence)
     // offsets

@@ -273,6 +273,7 @@ int avae_set_option(avae_handle h, const char* key, int value)
     if (!strcmp(key, "sil_chunk")) { if (value < 0) return fail(h, "sil_chunk must be >= 0"); h->sil_chunk = value; return 0; }
     if (!strcmp(key, "dbscan_chunk")) { if (value < 0) return fail(h, "dbscan_chunk must be >= 0"); h->dbscan_chunk = value; return 0; }
     if (!strcmp(key, "pca_chunk")) { if (value < 0) return fail(h, "pca_chunk must be >= 0"); h->pca_chunk = value; return 0; }
+    if (!strcmp(key, "mmd_chunk")) { if (value < 0) return fail(h, "mmd_chunk must be >= 0"); h->mmd_chunk = value; return 0; }
     if (!strcmp(key, "pca_form")) { if (value < 0 || value > 2) return fail(h, "pca_form must be 0 (planner), 1 (resident) or 2 (launched)"); h->pca_form = value; return 0; }
     if (!strcmp(key, "kmeans_chunk")) { if (value < 0) return fail(h, "kmeans_chunk must be >= 0"); h->kmeans_chunk = value; return 0; }
     if (!strcmp(key, "gmm_chunk")) { if (value < 0) return fail(h, "gmm_chunk must be >= 0"); h->gmm_chunk = value; return 0; }

@@ -509,6 +509,23 @@ int avae_debug_sil_plan(int32_t N, int32_t dim, int32_t L, const int32_t* K, int
     return 0;
 }
 
+// test hook: mmd_plan(N, dim, G, P, chunk_opt, cus) of avae_mmd; out = TI, the relabelings of a full pass, the number of passes, the LDS
+// limit, the row tiles, the most slots of a pass, the LDS bytes of the witness pass, then for the first min(passes, cap) passes the first
+// relabeling and the LDS bytes (7 + 2 cap values at most).  Host arithmetic only: callable without a GPU.
+int avae_debug_mmd_plan(int32_t N, int32_t dim, int32_t G, int32_t P, int32_t chunk_opt, int32_t cus, int32_t* out, int32_t cap)
+{
+    if (!out || N < 2 || N > kMmdMaxN || G < 1 || G > kMmdMaxG || P < 0 || (long long)G * (1LL + P) > kMmdMaxQ || chunk_opt < 0 || cus < 1 || cap < 0)
+        return 1;
+    const MmdPlan p = mmd_plan(N, dim, G, P, chunk_opt, cus);
+    const int Q = G * (1 + P);
+    out[0] = p.TI; out[1] = p.nq; out[2] = p.npass; out[3] = kMmdLds; out[4] = p.tiles; out[5] = p.cap; out[6] = (int32_t)mmd_lds(p.TI, 2 * G, p.W);
+    for (int q = 0; q < p.npass && q < cap; ++q) {
+        const int q0 = q * p.nq, nq = std::min(p.nq, Q - q0);
+        out[7 + 2 * q] = q0; out[8 + 2 * q] = (int32_t)mmd_pass_lds(p, q0, nq, P);
+    }
+    return 0;
+}
+
 // test hook: db_plan(N, dim, chunk_opt, cus) of avae_dbscan; out = TI, row tiles, column parts, column tiles per part, W, the LDS bytes of
 // the pair pass, the default max_rounds, then the workspace bytes of a cosine call without count as two 32-bit halves (low, high).  Host
 // arithmetic only: callable without a GPU.

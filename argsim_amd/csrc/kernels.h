@@ -686,6 +686,36 @@ hipError_t pca_finish(hipStream_t st, const PcaArgs& a, const PcaPlan& p, double
 hipError_t pca_transform(hipStream_t st, const float* x, int n, int dim, const double* mean, const double* comp, const double* scale, int k,
                          float* y, int trows);
 
+// ---------------------------------------------------------------- kernel two-sample test of latent rows (mmd.hip)
+// One set of N rows, G comparisons of 1 + P relabelings per call (contract: include/argsim_vae.h, avae_mmd / avae_mmd_relabel).  Every
+// buffer is workspace laid out by the caller (scoring.cpp) or the caller's own output.
+constexpr int kMmdMaxN = 1 << 17, kMmdMaxG = 64, kMmdMaxQ = 16384, kMmdMaxBw = 8;
+constexpr int kMmdLds = 160 * 1024;   // the LDS one workgroup may take on gfx950
+constexpr int kMmdDK = 32;            // row elements per LDS stage
+// TI rows x 64 columns per tile; pass q covers the relabelings [q nq, q nq + nq) of the G (1 + P); cap = the most slots (relabelings +
+// their comparisons) of a pass; lds = the most LDS bytes of a pass
+struct MmdPlan { int TI, nq, npass, tiles, W, cap, lds; };
+struct MmdArgs {
+    const float* x; const double* rnorm;      // rows; their norms (cosine) or null
+    const unsigned long long* valid;          // (G, W)
+    const unsigned long long* inA;            // (G, 1 + P, W)
+    int N, dim, W, G, P, kernel, nbw, cap;
+    double gamma[kMmdMaxBw];
+    double* part;                             // (row tiles, 2, cap) the row tiles' sums of a pass: A side, B side
+    double* sums;                             // (G, 1 + P, 2) U_AA, U_BB: the caller's, or workspace
+    double* ull;                              // (G) U_LL: the caller's, or workspace
+    const int* counts;                        // (G, 2) m, n of relabeling 0
+    double* witness;                          // (G, N) or null
+};
+size_t mmd_lds(int TI, int slots, int W);
+size_t mmd_pass_lds(const MmdPlan& p, int q0, int nq, int P);
+MmdPlan mmd_plan(int N, int dim, int G, int P, int chunk_opt, int cus);
+hipError_t mmd_relabel(hipStream_t st, const unsigned long long* valid, unsigned long long* inA, int N, int G, int P, uint64_t seed);
+hipError_t mmd_prepare(hipStream_t st, const MmdArgs& a, int* counts);     // row norms (cosine), m and n
+hipError_t mmd_pairs(hipStream_t st, const MmdArgs& a, const MmdPlan& p);  // two launches per pass: sums, ull
+hipError_t mmd_witness(hipStream_t st, const MmdArgs& a, const MmdPlan& p);
+hipError_t mmd_stats(hipStream_t st, const MmdArgs& a, double* stat, double* pvalue, unsigned* bad, int32_t* stat_out);
+
 // ---------------------------------------------------------------- greedy decoding (decode.hip)
 // the whole loop of model.py:204-219 in one persistent launch; every pointer is device memory
 struct DecodeArgs {

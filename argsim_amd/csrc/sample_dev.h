@@ -21,7 +21,8 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)
 
 // the generator itself: value = f(seed, stream, index).  Streams: 1 word dropout, 2 epsilon (ops.hip), 3 Gumbel (below),
 // 4 the draws of the importance-weighted score (score.hip), 5 the perturbation of the affinity-propagation similarities (affinity.hip),
-// 6 the random start of the t-SNE embedding (tsne.hip), 7 the k-means++ draws (kmeans.hip)
+// 6 the random start of the t-SNE embedding (tsne.hip), 7 the k-means++ draws (kmeans.hip), 8 the keys of the generated relabelings of
+// the two-sample test (mmd.hip; the 64-bit keys themselves, not uniform01)
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t stream, uint64_t idx)
 {
     uint64_t r = mix64(mix64(seed ^ (stream * 0xD6E8FEB86659FD93ULL)) + idx);

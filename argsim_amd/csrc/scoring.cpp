@@ -1,5 +1,6 @@
 // scoring.cpp -- scoring and search over latent rows: the importance-weighted likelihood (avae_score, avae_score_z; score.hip) and
-// nearest neighbours (avae_knn; knn.hip) and the aggregate-posterior diagnostics (avae_agg_logq, avae_latent_moments; agg.hip).
+// nearest neighbours (avae_knn; knn.hip), the aggregate-posterior diagnostics (avae_agg_logq, avae_latent_moments; agg.hip) and the
+// kernel two-sample test (avae_mmd, avae_mmd_relabel; mmd.hip).
 #include "ctx.h"
 
 using namespace avae;
@@ -179,6 +180,83 @@ int avae_latent_moments(avae_handle h, const float* mu, const float* lv, int32_t
     double *mean = nullptr, *part = nullptr;
     AV_TRY(place_ws(h, "moments", [&](Bump& b) { mean = b.take<double>((size_t)dim); part = b.take<double>((size_t)moments_blocks(N) * 3 * dim); }));
     AV_CHECK(latent_moments(h->stream, mu, lv, N, dim, out, mean, part));
+    return 0;
+}
+
+// ---------------------------------------------------------------- kernel two-sample test (contract: include/argsim_vae.h, avae_mmd /
+// avae_mmd_relabel; kernels: mmd.hip)
+int avae_mmd(avae_handle h, const float* x, int32_t N, int32_t dim, const avae_mmd_config* mc, const uint64_t* valid, const uint64_t* inA,
+             double* stat, double* pvalue, int32_t* counts, double* sums, double* ull, double* witness, int32_t* stat_out)
+{
+    if (!h) return 1;
+    if (!mc) return fail(h, "mmd config is null");
+    if (!x) return fail(h, "mmd: x is null");
+    if (!valid || !inA) return fail(h, "mmd: valid and inA must be given");
+    if (!stat || !pvalue || !counts || !stat_out) return fail(h, "mmd: stat, pvalue, counts and stat_out must be given");
+    if (N < 2 || N > kMmdMaxN) return fail(h, "mmd: N must be in [2, 2^17]");
+    if (dim < 4 || dim > 1024 || (dim & 3)) return fail(h, "mmd: dim must be a multiple of 4 in [4, 1024]");
+    if (mc->G < 1 || mc->G > kMmdMaxG) return fail(h, "mmd: G must be in [1, 64]");
+    if (mc->P < 0 || (long long)mc->G * (1LL + mc->P) > kMmdMaxQ) return fail(h, "mmd: P must be >= 0 with G (1 + P) <= 16384");
+    if (mc->kernel < 0 || mc->kernel > 1) return fail(h, "mmd: kernel must be 0 (rbf) or 1 (energy)");
+    if (mc->metric < 0 || mc->metric > 1) return fail(h, "mmd: metric must be 0 (euclidean) or 1 (cosine)");
+    if (mc->kernel == 0) {
+        if (mc->nbw < 1 || mc->nbw > kMmdMaxBw) return fail(h, "mmd: nbw must be in [1, 8]");
+        for (int b = 0; b < mc->nbw; ++b)
+            if (!(mc->gamma[b] > 0.0) || !std::isfinite(mc->gamma[b])) return fail(h, "mmd: gamma[" + std::to_string(b) + "] must be finite and > 0");
+    }
+    if ((uintptr_t)x & 15) return fail(h, "mmd: x must be 16-byte aligned");
+    if (mc->reserved != 0) return fail(h, "mmd: the reserved field must be 0");
+    AV_CHECK(hipSetDevice(h->device));
+    int cus = 0, lds = 0;
+    AV_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    AV_CHECK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+    if (lds < kMmdLds) return fail(h, "mmd: the device gives a workgroup less than the 160 KiB of LDS the pair pass is planned for");
+    const int G = mc->G, P = mc->P;
+    const MmdPlan plan = mmd_plan(N, dim, G, P, h->mmd_chunk, cus);
+    // Workspace, every buffer on a 256-byte boundary: m and n (G, 2) int, the word of the first bad relabeling, with the
+    // cosine the row norms (N), the row tiles' partial sums of a pass (tiles, 2, cap), U_AA and U_BB (G, 1 + P, 2) unless the caller gives
+    // sums, U_LL (G) unless the caller gives ull
+    MmdArgs a{};
+    a.x = x; a.valid = reinterpret_cast<const unsigned long long*>(valid); a.inA = reinterpret_cast<const unsigned long long*>(inA);
+    a.N = N; a.dim = dim; a.W = plan.W; a.G = G; a.P = P; a.kernel = mc->kernel; a.nbw = mc->kernel == 0 ? mc->nbw : 0; a.cap = plan.cap;
+    for (int b = 0; b < a.nbw; ++b) a.gamma[b] = mc->gamma[b];
+    a.witness = witness;
+    int* dcounts = nullptr; unsigned* bad = nullptr; double* rnorm = nullptr;
+    AV_TRY(place_ws(h, "mmd", [&](Bump& b) {
+        dcounts = b.take<int>(2 * (size_t)G);
+        bad = b.take<unsigned>(1);
+        rnorm = b.opt<double>(mc->metric == 1, (size_t)N);
+        a.part = b.take<double>((size_t)plan.tiles * 2 * plan.cap);
+        a.sums = sums ? sums : b.take<double>(2 * (size_t)G * (1 + P));
+        a.ull = ull ? ull : b.take<double>((size_t)G);
+    }));
+    a.rnorm = rnorm; a.counts = dcounts;
+    AV_CHECK(mmd_prepare(h->stream, a, dcounts));
+    // m, n >= 2 is the one check that needs the masks: G pairs of counts come to the host before anything is written
+    std::vector<int> hc(2 * (size_t)G);
+    AV_CHECK(hipMemcpyAsync(hc.data(), dcounts, hc.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    AV_CHECK(hipStreamSynchronize(h->stream));
+    for (int g = 0; g < G; ++g)
+        if (hc[2 * g] < 2 || hc[2 * g + 1] < 2)
+            return fail(h, "mmd: comparison " + std::to_string(g) + " has " + std::to_string(hc[2 * g]) + " rows in A and " + std::to_string(hc[2 * g + 1]) +
+                               " in B; both samples need at least 2");
+    AV_CHECK(hipMemcpyAsync(counts, dcounts, hc.size() * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    AV_CHECK(hipMemsetAsync(bad, 0xff, sizeof(unsigned), h->stream));
+    AV_CHECK(mmd_pairs(h->stream, a, plan));
+    if (witness) AV_CHECK(mmd_witness(h->stream, a, plan));
+    AV_CHECK(mmd_stats(h->stream, a, stat, pvalue, bad, stat_out));
+    return 0;
+}
+
+int avae_mmd_relabel(avae_handle h, int32_t N, int32_t G, int32_t P, const uint64_t* valid, uint64_t* inA, uint64_t seed)
+{
+    if (!h) return 1;
+    if (!valid || !inA) return fail(h, "mmd relabel: valid and inA must be given");
+    if (N < 2 || N > kMmdMaxN) return fail(h, "mmd relabel: N must be in [2, 2^17]");
+    if (G < 1 || G > kMmdMaxG) return fail(h, "mmd relabel: G must be in [1, 64]");
+    if (P < 0 || (long long)G * (1LL + P) > kMmdMaxQ) return fail(h, "mmd relabel: P must be >= 0 with G (1 + P) <= 16384");
+    AV_CHECK(hipSetDevice(h->device));
+    AV_CHECK(mmd_relabel(h->stream, reinterpret_cast<const unsigned long long*>(valid), reinterpret_cast<unsigned long long*>(inA), N, G, P, seed));
     return 0;
 }
 

@@ -8,7 +8,7 @@ centroid, written with the cluster numbers as CSV.  Every run is ONE device call
         [--inputs-sp data/test_data_emb_sample.npy] [--posts data/test_posts.npy] [--csv trial/clustering.csv]
         [--tsne trial/tsne.npy [--tsne-plot trial/tsne.png] [--perplexity 40] [--tsne-iter 20000]] [--kmeans K [--kmeans-init 10]]
         [--quality] [--sweep LO:HI[:STEP]] [--gmm K [--gmm-cov diag|spherical] [--gmm-init R]] [--gmm-sweep LO:HI[:STEP]]
-        [--dbscan EPS [--dbscan-min M]] [--dbscan-sweep E1,E2,..] [--pca K [--pca-whiten]]
+        [--dbscan EPS [--dbscan-min M]] [--dbscan-sweep E1,E2,..] [--pca K [--pca-whiten]] [--mmd stance [--mmd-perm P]]
 
 With --tsne the script first does what lines 45-66 of the reference do: the exact t-SNE of the embeddings into two dimensions in ONE
 device call (VAE.tsne, a random start as in the reference's sklearn), written as .npy and, with --tsne-plot, scattered by topic.
@@ -39,7 +39,11 @@ all that can be scored), the eps with the largest silhouette marked with *.  Wit
 With --pca K (a count, or a fraction in (0, 1) of the variance to keep) the embeddings and, where given, those of the sampled segmentation
 are first reduced to their leading principal components (VAE.pca_reduce: ONE device call for the fit, one for the projection; --pca-whiten
 scales them to unit variance): per input the table "component variance ratio cumulative" and the line "effective dimension %.2f of D,
-rank R, kept K", and EVERY run above is made on the reduced rows.  Without the flag nothing changes."""
+rank R, kept K", and EVERY run above is made on the reduced rows.  Without the flag nothing changes.
+
+With --mmd stance the table "topic m n mmd2 p" follows per input: per topic, do the rows of its first stance and those of its second come
+from the same distribution?  The kernel two-sample test (VAE.mmd: the rbf kernel at the median bandwidth, --mmd-perm relabelings, all
+topics in ONE device call); a topic with fewer than two rows of either stance is listed as n/a.  Without the flag nothing changes."""
 import argparse
 import csv
 
@@ -117,15 +121,41 @@ def pca_lines(model, name):
                                                                            len(model['explained_variance']))]
 
 
+def mmd_lines(vae, x, name, labels, n_perm, seed):
+    """the table of --mmd stance for one input: per topic its first stance (A) against its second (B)"""
+    from .eval_cluster import split_labels
+    parts = split_labels(labels)
+    topics, stances = np.array([p[0] for p in parts]), np.array([p[1] for p in parts])
+    lines = ["mmd stance %s" % name, "topic m n mmd2 p"]
+    rows, names = [], []
+    for topic in dict.fromkeys(topics.tolist()):
+        on = topics == topic
+        kinds = list(dict.fromkeys(stances[on].tolist()))[:2]
+        g = np.full(len(topics), -1, np.int64)
+        for side, kind in enumerate(kinds):
+            g[on & (stances == kind)] = side
+        if min(int((g == 0).sum()), int((g == 1).sum())) < 2:
+            lines.append("%s %d %d n/a" % (topic, int((g == 0).sum()), int((g == 1).sum())))
+        else:
+            rows.append(g)
+            names.append(topic)
+    for i0 in range(0, len(rows), 64):
+        t = vae.mmd(x, np.stack(rows[i0:i0 + 64]), n_perm=n_perm, seed=seed)
+        for topic, m, n, s, p in zip(names[i0:i0 + 64], t['m'], t['n'], t['stat'], t['pvalue']):
+            lines.append("%s %d %d %.6f %.4f" % (topic, m, n, s, p))
+    return lines
+
+
 def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_init=10, quality=False, sweep=None, gmm=None, gmm_cov='diag',
-             gmm_init=1, gmm_sweep=None, dbscan=None, dbscan_min=5, dbscan_sweep=None, pca=None, pca_whiten=False):
+             gmm_init=1, gmm_sweep=None, dbscan=None, dbscan_min=5, dbscan_sweep=None, pca=None, pca_whiten=False, mmd=None, mmd_perm=999):
     """-> (columns {name: array}, lines): cls_* / dist_* of the runs that have their inputs, and what is printed.  kmeans = k adds the
     same runs with k-means into k clusters (VAE.kmeans, kmeans_init restarts): cls_km_* / dist_km_*.  quality: a line of scores behind
     every run; sweep = [k ..]: the k-means quality table per input and metric.  gmm = k adds a mixture with k components per input
     (VAE.gmm, gmm_cov covariances, gmm_init restarts): cls_gmm_* / logp_gmm_*; gmm_sweep = [k ..]: the BIC / AIC table per input.
     dbscan = eps adds the same runs with density clustering (VAE.dbscan, dbscan_min rows make a core row): cls_db_* / dist_db_*;
     dbscan_sweep = [eps ..]: the quality table per input and metric.  pca = k (a count or a fraction): every run is made on the rows
-    reduced to their leading principal components (VAE.pca_reduce, pca_whiten: to unit variance), the variance table first"""
+    reduced to their leading principal components (VAE.pca_reduce, pca_whiten: to unit variance), the variance table first.  mmd =
+    'stance': per input the two-sample table of every topic's two stances (VAE.mmd, mmd_perm relabelings)"""
     from . import affinity
     from .eval_cluster import split_labels
     topics = np.array([p[0] for p in split_labels(labels)])
@@ -196,6 +226,10 @@ def evaluate(vae, z, z_sp, labels, seed=0, max_iter=200, kmeans=None, kmeans_ini
         x = z_sp if sampled else z
         if x is not None:
             lines += eps_sweep_lines(vae, x, name, metric, dbscan_sweep, dbscan_min)
+    for name, sampled in GMM_RUNS if mmd == 'stance' else ():
+        x = z_sp if sampled else z
+        if x is not None:
+            lines += mmd_lines(vae, x, name, labels, mmd_perm, seed)
     return cols, lines
 
 
@@ -302,6 +336,8 @@ def build_parser():
     ap.add_argument('--dbscan-sweep', type=_eps_list, default=None, help="E1,E2,..: the density-clustering quality table for these eps per input and metric (VAE.sweep_eps)")
     ap.add_argument('--pca', type=_components, default=None, help="K or a fraction: first reduce the inputs to their leading principal components (VAE.pca_reduce); every run is made on the reduced rows")
     ap.add_argument('--pca-whiten', action='store_true', help="with --pca: scale the components to unit variance")
+    ap.add_argument('--mmd', choices=('stance',), default=None, help="stance: per topic, the kernel two-sample test of its two stances (VAE.mmd, all topics in one call)")
+    ap.add_argument('--mmd-perm', type=_positive, default=999, help="with --mmd: the relabelings of the permutation null")
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', type=int, default=0)
     return ap
@@ -321,7 +357,7 @@ def main(argv=None):
     if A.tsne:
         print(embed(vae, z, labels, A.tsne, A.tsne_plot, A.perplexity, A.tsne_iter, A.seed)[1])
     cols, lines = evaluate(vae, z, z_sp, labels, A.seed, A.max_iter, A.kmeans, A.kmeans_init, A.quality, A.sweep, A.gmm, A.gmm_cov, A.gmm_init,
-                           A.gmm_sweep, A.dbscan, A.dbscan_min, A.dbscan_sweep, A.pca, A.pca_whiten)
+                           A.gmm_sweep, A.dbscan, A.dbscan_min, A.dbscan_sweep, A.pca, A.pca_whiten, A.mmd, A.mmd_perm)
     for line in lines:
         print(line)
     if A.csv:

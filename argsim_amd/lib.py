@@ -107,6 +107,11 @@ class AvaePcaConfig(C.Structure):
     _fields_ = [('pad', C.c_int32), ('max_sweeps', C.c_int32), ('reserved', C.c_int32), ('reserved2', C.c_int32)]
 
 
+class AvaeMmdConfig(C.Structure):
+    _fields_ = [('kernel', C.c_int32), ('metric', C.c_int32), ('G', C.c_int32), ('P', C.c_int32), ('nbw', C.c_int32), ('reserved', C.c_int32),
+                ('gamma', C.c_double * 8)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the declarations of include/argsim_vae.h
 SIGNATURES = {
@@ -157,6 +162,8 @@ SIGNATURES = {
     'avae_dbscan': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeDbscanConfig), _P, _P, _P]),
     'avae_pca_fit': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaePcaConfig), _P, _P, _P, _P]),
     'avae_pca_transform': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P]),
+    'avae_mmd': (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.POINTER(AvaeMmdConfig)] + [_P] * 9),
+    'avae_mmd_relabel': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_uint64]),
     # knobs used by tests / bench (not part of the reference-facing surface)
     'avae_set_option': (C.c_int, [_P, C.c_char_p, C.c_int]),
     'avae_debug_gemm': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_int]),
@@ -190,6 +197,7 @@ SIGNATURES = {
     'avae_debug_decode_plan': (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'avae_debug_gru': (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int64)]),
     'avae_debug_sil_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    'avae_debug_mmd_plan': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_int32]),
     'avae_debug_dbscan_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     'avae_debug_pca_plan': (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)]),
     'avae_bucket_count': (C.c_int, [_P]),

@@ -25,6 +25,7 @@ The reference's feed -> fetch pairs map to methods:
     (new) silhouette, CH and DB of many labelings      -> VAE.silhouette(z, labels, metric) / VAE.sweep_k(z, ks) / silhouette(vae, z, ...)
     (new) density clustering of latent rows (DBSCAN)   -> VAE.dbscan(z, eps, min_samples) / VAE.kdist(z, k) / VAE.sweep_eps(z, eps_list)
     (new) principal components of latent rows (PCA)    -> VAE.pca(z, n_components, whiten) / VAE.pca_transform(z, model) / VAE.pca_reduce(z, k)
+    (new) kernel two-sample test of latent rows (MMD)  -> VAE.mmd(z, groups) / VAE.mmd2(za, zb) / VAE.prior_match(z) / mmd(vae, z, ...)
 """
 import ctypes as C
 
@@ -762,6 +763,25 @@ class VAE:
         from . import pca
         return pca.reduce(self, z, k, whiten)
 
+    def mmd(self, z, groups, kernel='rbf', gamma='median', metric='euclidean', n_perm=999, seed=0, return_null=False, return_witness=False):
+        """do the rows with groups == 0 and those with groups == 1 come from the same distribution?  The unbiased kernel two-sample
+        statistic MMD^2_u with a permutation null in ONE device call for every row of groups, (N,) or (G, N) integers (negative: left
+        out) (include/argsim_vae.h, avae_mmd).  kernel: 'rbf' or 'energy'; gamma: 'median', a number or up to 8 numbers
+        -> dict(stat, pvalue, m, n[, null, witness]) (argsim_amd/mmd.py)"""
+        from . import mmd
+        return mmd.mmd(self, z, groups, kernel, gamma, metric, n_perm, seed, return_null, return_witness)
+
+    def mmd2(self, za, zb, kernel='rbf', gamma='median', metric='euclidean', n_perm=999, seed=0, return_null=False, return_witness=False):
+        """VAE.mmd for two arrays of rows: za against zb"""
+        from . import mmd
+        return mmd.mmd2(self, za, zb, kernel, gamma, metric, n_perm, seed, return_null, return_witness)
+
+    def prior_match(self, z, n_perm=999, seed=0):
+        """does the aggregate posterior match the prior that generate samples from?  The rows of z against as many N(0, I) rows
+        (the InfoVAE diagnostic MMD(q(z), p(z))) -> dict(stat, pvalue, m, n)"""
+        from . import mmd
+        return mmd.prior_match(self, z, n_perm, seed)
+
 
 # avae_debug_step_route: seven scalars, then (form, T, C, pipe, ring) per kind of GRU launch, in this order
 ROUTE_GRU = ('enc_fwd', 'enc_bwd', 'top_fwd', 'top_bwd', 'dec_fwd', 'dec_bwd')
@@ -1076,3 +1096,18 @@ def pca_transform(vae, z, model):
 def pca_reduce(vae, z, k, whiten=False):
     """functional form of VAE.pca_reduce"""
     return vae.pca_reduce(z, k, whiten)
+
+
+def mmd(vae, z, groups, kernel='rbf', gamma='median', metric='euclidean', n_perm=999, seed=0, return_null=False, return_witness=False):
+    """functional form of VAE.mmd"""
+    return vae.mmd(z, groups, kernel, gamma, metric, n_perm, seed, return_null, return_witness)
+
+
+def mmd2(vae, za, zb, kernel='rbf', gamma='median', metric='euclidean', n_perm=999, seed=0, return_null=False, return_witness=False):
+    """functional form of VAE.mmd2"""
+    return vae.mmd2(za, zb, kernel, gamma, metric, n_perm, seed, return_null, return_witness)
+
+
+def prior_match(vae, z, n_perm=999, seed=0):
+    """functional form of VAE.prior_match"""
+    return vae.prior_match(z, n_perm, seed)

@@ -907,6 +907,70 @@ int  avae_pca_fit(avae_handle h, const float* x /* (N, dim) device */, int32_t N
 int  avae_pca_transform(avae_handle h, const float* x /* (n, dim) device */, int32_t n, int32_t dim, const double* mean /* (dim) */,
                         const double* comp /* (k, dim) */, const double* scale /* (k) or null */, int32_t k, float* y /* (n, k) */);
 
+/* ---- kernel two-sample test of latent rows -------------------------------------------------------------------------------------------
+ * Do two sets of rows come from the same distribution?  The unbiased kernel two-sample statistic MMD^2_u with a permutation null, for
+ * G comparisons of 1 + P relabelings each over the SAME N rows in ONE call: every kernel value is formed once per pass and added for
+ * all relabelings of the pass; nothing of size (N, N) or (N, G (1 + P)) reaches memory.  With kernel 1 the statistic is the energy
+ * distance.  Every pointer is device memory; gamma is part of the config, which the host reads.  All arithmetic is double; the rows
+ * are fp32.  (The float64 restatement of this contract is tests/mmd_ref.py.)
+ *   rows       X = double(x); for metric 1 X_i = x_i / sqrt(sum_e x_ie^2), a division in double; a zero row stays zero.
+ *   distance   d2(i, j) = sum_e (X_ie - X_je)^2, e ascending for every tile shape.  Duplicate rows give exactly 0.
+ *   kernel     k(i, j): kernel 0 (rbf) sum_b exp(-(gamma[b] d2)) over b = 0 .. nbw - 1 ascending; kernel 1 (energy) -sqrt(d2).
+ *   masks      W = ceil(N / 64) 64-bit words per bit row; bit i % 64 of word i / 64 is row i.  valid (G, W): the rows that take part
+ *              in comparison g.  inA (G, 1 + P, W): A = valid & inA, B = valid & ~inA.  Relabeling 0 is the observed split; the
+ *              others are the null (avae_mmd_relabel writes them).  Bits beyond N and inA bits outside valid are ignored.  A row
+ *              that is valid in no comparison is never read as a number: it may hold NaN.
+ *   statistic  per (g, p), over the unordered pairs i < j: U_AA = sum of k over the pairs with both rows in A, U_BB likewise for B;
+ *              per comparison U_LL = the same over the valid rows; U_AB = U_LL - U_AA - U_BB.  With m = |A|, n = |B| of relabeling 0
+ *              stat = 2 U_AA / (m (m - 1)) + 2 U_BB / (n (n - 1)) - 2 U_AB / (m n), evaluated left to right.
+ *   order      a row's sum runs over its columns j > i in ascending j (only the columns on the row's own side); the 64 rows of a
+ *              mask word are summed by the balanced binary tree over adjacent rows; the words in ascending order.
+ *   outputs    stat (G, 1 + P); pvalue (G) = (1 + #{p >= 1: stat[g][p] >= stat[g][0]}) / (1 + P), 1 when P = 0; counts (G, 2) = m, n.
+ *              Optional (may be null): sums (G, 1 + P, 2) = U_AA, U_BB; ull (G) = U_LL; witness (G, N) for relabeling 0, w_i = the
+ *              mean of k(i, j) over the j in A, j != i, minus the mean over the j in B, j != i (columns ascending), 0 for a row
+ *              that is not valid in g.  stat_out (1): 0, or 1 + g (1 + P) + p of the first relabeling whose |A| is not m (its stat
+ *              is then computed with m and n all the same; nothing is read past a mask).
+ *   range      2 <= N <= 2^17; dim a multiple of 4 in [4, 1024]; x 16-byte aligned; 1 <= G <= 64; 0 <= P; G (1 + P) <= 16384;
+ *              1 <= nbw <= 8 and every gamma finite and > 0 (kernel 0); m >= 2 and n >= 2 in every comparison.
+ *   bits       no float atomics.  Every output is a function of the arguments alone: the same bits however the planner tiles the
+ *              rows or groups the relabelings (option mmd_chunk) and on every CU count.
+ *   plan       a workgroup owns TI in {8, 16, 32, 64} rows and walks the column tiles of 64 from its own word on; the accumulators
+ *              of a pass (TI x (relabelings + comparisons of the pass) x 8 bytes) and the staging lie in the workgroup's LDS
+ *              (160 KiB); a pass forms the kernel values once for its relabelings.  A column tile is skipped when no comparison of
+ *              the pass has valid rows in both the row tile and the column tile: per-topic comparisons of rows sorted by topic
+ *              cost what their own rows cost.
+ *   sync       m and n are checked on the host: the call waits once, for G pairs of counts, before the pair passes are enqueued.
+ *              Everything else is enqueued on the handle's stream without a synchronisation.
+ *   workspace  8 N of norms for the cosine, 8 G of counts, 16 (row tiles) (slots of a pass) of partial sums, 16 G (1 + P) unless sums
+ *              is given, 8 G unless ull is given; + 256-byte rounding, reserved once per call.
+ * avae_mmd_relabel writes the relabelings 1 .. P of every comparison from valid, relabeling 0 and a seed; the caller never builds the
+ * masks on the host.  With mix64 the mixer of the library's generator, base = mix64(seed ^ (8 * 0xD6E8FEB86659FD93)) (stream 8),
+ * c = mix64(base + ((g << 32) | p)) and key(i) = mix64(c + i), A of (g, p) is the m valid rows with the smallest (key, i) pairs, m =
+ * |A| of relabeling 0.  The masks are an exact function of (valid, m, seed, g, p).  One launch, no synchronisation.
+ * Errors (text through avae_last_error; checked on the host, before any output is written; each with its own text): a null mc, x,
+ * valid, inA, stat, pvalue, counts or stat_out; N, dim, G, P, G (1 + P), nbw, kernel, metric or a gamma out of range; x not 16-byte
+ * aligned; reserved != 0; a comparison with fewer than 2 rows in A or in B; a device whose workgroups get less than 160 KiB of LDS;
+ * a workspace the device cannot give.
+ * Option mmd_chunk (avae_set_option; a test aid): a value > 0 caps TI (the largest of 8 .. 64 within it, at least 8; the CU
+ * preference is then off) and the relabelings of a pass, so that small tests run ragged tiles and several passes; 0 lets the planner
+ * decide.  Same bits for every value.                                                                                                */
+typedef struct avae_mmd_config {
+    int32_t kernel;    /* 0 rbf, 1 energy */
+    int32_t metric;    /* 0 euclidean, 1 cosine */
+    int32_t G;         /* comparisons, 1 .. 64 */
+    int32_t P;         /* relabelings behind the observed one, >= 0 */
+    int32_t nbw;       /* bandwidths of the rbf kernel, 1 .. 8 (ignored for kernel 1) */
+    int32_t reserved;  /* 0 */
+    double  gamma[8];  /* the first nbw are read */
+} avae_mmd_config;
+int  avae_mmd(avae_handle h, const float* x /* (N, dim) device */, int32_t N, int32_t dim, const avae_mmd_config* mc,
+              const uint64_t* valid /* (G, W) */, const uint64_t* inA /* (G, 1 + P, W) */,
+              double* stat /* (G, 1 + P) */, double* pvalue /* (G) */, int32_t* counts /* (G, 2) */,
+              double* sums /* optional (G, 1 + P, 2) */, double* ull /* optional (G) */, double* witness /* optional (G, N) */,
+              int32_t* stat_out /* (1) */);
+int  avae_mmd_relabel(avae_handle h, int32_t N, int32_t G, int32_t P, const uint64_t* valid /* (G, W) */,
+                      uint64_t* inA /* (G, 1 + P, W): relabeling 0 is read, 1 .. P are written */, uint64_t seed);
+
 #ifdef __cplusplus
 }
 #endif
