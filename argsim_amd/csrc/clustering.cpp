@@ -63,7 +63,7 @@ int avae_ward(avae_handle h, const float* x, int32_t dim, const int32_t* group_o
     std::vector<WardGroup> gs((size_t)G);
     WardGroup* dev = nullptr;
     AV_TRY(place_ws(h, "ward", [&](Bump& b) { ward_layout(b, gs, &dev, group_off, G, dim); }));
-    AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardGroup), hipMemcpyHostToDevice, h->stream));
+    AV_TRY(stage_h2d(h, dev, gs.data(), gs.size() * sizeof(WardGroup)));                // (gs dies at return, nothing below synchronises)
     AV_CHECK(ward_init(h->stream, dev, G, nmax, x, dim));
     const int form = h->ward_form ? h->ward_form : (nmax <= kWardOneWgMax ? 1 : 2);
     if (form == 1) {
@@ -91,7 +91,7 @@ int avae_ward_cut(avae_handle h, const int32_t* pair, const int32_t* group_off, 
     AV_CHECK(hipSetDevice(h->device));
     WardCutGroup* dev = nullptr; int32_t* parent = nullptr;
     AV_TRY(place_ws(h, "ward cut", [&](Bump& b) { dev = b.take<WardCutGroup>((size_t)G); parent = b.take<int32_t>((size_t)group_off[G]); }));
-    AV_CHECK(hipMemcpyAsync(dev, gs.data(), gs.size() * sizeof(WardCutGroup), hipMemcpyHostToDevice, h->stream));
+    AV_TRY(stage_h2d(h, dev, gs.data(), gs.size() * sizeof(WardCutGroup)));             // (gs dies at return, nothing below synchronises)
     AV_CHECK(ward_cut(h->stream, dev, G, nmax, pair, parent, label));
     return 0;
 }
@@ -396,7 +396,7 @@ int avae_silhouette(avae_handle h, const float* x, int32_t N, int32_t dim, const
     }));
     a.meta = dmeta; a.rnorm = rnorm;
     const SilPlan plan = sil_plan(N, dim, sc->L, K, h->sil_chunk, cus);
-    AV_CHECK(hipMemcpyAsync(dmeta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    AV_TRY(stage_h2d(h, dmeta, meta.data(), meta.size() * sizeof(int)));                // (meta dies at return, nothing below synchronises)
     AV_CHECK(hipMemsetAsync(a.cnt, 0, sumk * sizeof(int), h->stream));
     AV_CHECK(sil_prepare(h->stream, a));
     AV_CHECK(sil_pairs(h->stream, a, plan));

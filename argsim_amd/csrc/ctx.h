@@ -118,6 +118,9 @@ struct avae_ctx {
     // what had arrived where the current call began (latch_hint, build_row_orders): every decision of ONE call reads this pair, so a call's own
     // copy landing while the call is still being enqueued cannot give its forward one hint and its backward another
     uint64_t hint_seen = 0xffffffffull;
+    // pinned staging of the small host tables a call uploads and does not wait for (stage_h2d): it outlives the call, stage_ev says when the
+    // last upload from it has been read
+    void* stage_host = nullptr; size_t stage_cap = 0; hipEvent_t stage_ev = nullptr;
     const int32_t *cnt_src = nullptr, *cnt_tgt = nullptr;     // present-id counts of the last forward (table-fed layers), device
     // The route of the last avae_forward_backward (avae_debug_step_route), noted by the step where it decides (note_gru, model.cpp): the first
     // layers table-fed (use_table), Ws::compact / compact_d / Bx, the BPTT form rs_pick gave, whether the top encoder layer ran its one-job
@@ -136,6 +139,27 @@ namespace avae { namespace host {
 #define AV_TRY(expr) do { int r_ = (expr); if (r_) return r_; } while (0)
 
 inline int fail(avae_ctx* h, const std::string& m) { h->err = m; return 1; }
+// Upload a small host table on the handle's stream from a call that returns WITHOUT synchronising: the caller's array (a function-local
+// vector) may die at return, while a stream that is still busy reads the source only when it gets there.  The bytes go through pinned
+// memory the handle owns; the event says when the previous upload has been read, so the wait is over at once unless the stream is
+// still in front of that copy.
+inline int stage_h2d(avae_ctx* h, void* dst, const void* src, size_t bytes)
+{
+    if (!bytes) return 0;
+    if (!h->stage_ev) AV_CHECK(hipEventCreateWithFlags(&h->stage_ev, hipEventDisableTiming));
+    else AV_CHECK(hipEventSynchronize(h->stage_ev));
+    if (bytes > h->stage_cap) {
+        if (h->stage_host) AV_CHECK(hipHostFree(h->stage_host));
+        h->stage_host = nullptr; h->stage_cap = 0;
+        const size_t cap = (bytes + 4095) & ~(size_t)4095;
+        AV_CHECK(hipHostMalloc(&h->stage_host, cap, hipHostMallocDefault));
+        h->stage_cap = cap;
+    }
+    memcpy(h->stage_host, src, bytes);
+    AV_CHECK(hipMemcpyAsync(dst, h->stage_host, bytes, hipMemcpyHostToDevice, h->stream));
+    AV_CHECK(hipEventRecord(h->stage_ev, h->stream));
+    return 0;
+}
 // the rule every latent-row entry has for its row operands: dim a multiple of 4 in [4, 1024], the pointers in `ptrs` (which `names`
 // names in the message) 16-byte aligned
 inline int check_rows(avae_ctx* h, const char* what, int dim, const char* names, std::initializer_list<const void*> ptrs)

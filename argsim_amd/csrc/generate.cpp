@@ -118,6 +118,7 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
     AV_TRY(avae_decode_init(h, z, b, sb.state[0]));
     std::vector<int32_t> host((size_t)(steps + 1) * b);
     for (int i = 0; i < b; ++i) host[i] = h->cfg.bos;
+    // (host lives to the end of the function, and the first pass of the loop below -- steps >= 1 -- synchronises behind this copy)
     AV_CHECK(hipMemcpyAsync(sb.ids_tm, host.data(), b * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     int done = 0, kept = steps, cur = 0;
     const int chunk = 16;
@@ -149,6 +150,8 @@ static int decode_stepwise(avae_handle h, const float* z, int32_t b, int32_t ste
     }
     if (kept > done) kept = done;
     // transpose (kept, b) time-major -> (b, steps) row-major on the host (tiny), eos-fill the rest
+    // outv, lpv and nkv are function-local and copied from asynchronously: the synchronise in front of `*n_steps = kept` completes all three
+    // copies before they go out of scope
     const std::vector<int32_t> outv = rows_major(host.data() + b, kept, b, steps, (int32_t)h->cfg.eos);
     AV_CHECK(hipMemcpyAsync(out_ids, outv.data(), outv.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     std::vector<float> lpv;
@@ -230,7 +233,7 @@ static int decode_loop(avae_handle h, const float* z, int32_t b, int32_t steps, 
     a.out_ids = out_ids; a.err = h->errw;
     a.b = b; a.steps = steps; a.D = D; a.V = V; a.L = L; a.eos = h->cfg.eos; a.isd = 1.f / sqrtf((float)D);
     AV_TRY(avae_decode_init(h, z, b, a.state[0]));
-    std::vector<int32_t> bos((size_t)b, h->cfg.bos);
+    std::vector<int32_t> bos((size_t)b, h->cfg.bos);        // (lives to the end of the function; check_gru_err below synchronises behind the copy)
     AV_CHECK(hipMemcpyAsync(a.ids_tm, bos.data(), b * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     AV_CHECK(hipMemsetAsync(a.kept, 0, sizeof(int32_t), h->stream));
     AV_CHECK(hipMemsetAsync(a.bar, 0, sizeof(unsigned), h->stream));

@@ -14,8 +14,10 @@ namespace avae { namespace host {
 int grow_scratch(avae_ctx* h, size_t need, const char* what)
 {
     if (h->scratch_n >= (int64_t)need) return 0;
-    AV_CHECK(hipStreamSynchronize(h->stream));
-    if (h->scratch) AV_CHECK(hipFree(h->scratch));
+    if (h->scratch) {                                         // (work enqueued on the old buffer; a first buffer has nothing to wait for)
+        AV_CHECK(hipStreamSynchronize(h->stream));
+        AV_CHECK(hipFree(h->scratch));
+    }
     h->scratch = nullptr; h->scratch_n = 0;
     if (hipMalloc(reinterpret_cast<void**>(&h->scratch), need) != hipSuccess) {
         (void)hipGetLastError();
@@ -121,7 +123,8 @@ int dyn_fraction(avae_ctx* h, const avae_ctx::Stamp& s, std::vector<std::pair<co
     int c = -1;
     for (auto& e : seen) if (e.first == s.dyn) c = e.second;
     if (c < 0) {
-        AV_CHECK(hipMemcpy(&c, s.dyn, sizeof(int), hipMemcpyDeviceToHost));
+        AV_CHECK(hipMemcpyAsync(&c, s.dyn, sizeof(int), hipMemcpyDeviceToHost, h->stream));      // behind the step that wrote the count
+        AV_CHECK(hipStreamSynchronize(h->stream));
         if (c < 0) c = 0;
         seen.push_back({s.dyn, c});
     }
@@ -170,6 +173,8 @@ void avae_destroy(avae_handle h)
     if (h->errw) (void)hipFree(h->errw);
     if (h->hint_host) (void)hipHostFree(const_cast<int32_t*>(h->hint_host));
     if (h->counters) (void)hipFree(h->counters);
+    if (h->stage_host) (void)hipHostFree(h->stage_host);
+    if (h->stage_ev) (void)hipEventDestroy(h->stage_ev);
     if (h->scratch) (void)hipFree(h->scratch);
     if (h->bfA) (void)hipFree(h->bfA);
     if (h->slab) (void)hipFree(h->slab);

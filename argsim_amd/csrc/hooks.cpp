@@ -186,9 +186,10 @@ int avae_debug_timing(avae_handle h, double* out, int max_n, int* n)
 int avae_debug_stamps(avae_handle h, unsigned long long* out)
 {
     if (!h || !out) return 1;
+    // both on the handle's stream: the read sees every launch enqueued before it, the clear is ordered before every launch after it
+    AV_CHECK(hipMemcpyAsync(out, h->errw + 16, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    AV_CHECK(hipMemsetAsync(h->errw + 16, 0, 32 * sizeof(unsigned long long), h->stream));
     AV_CHECK(hipStreamSynchronize(h->stream));
-    AV_CHECK(hipMemcpy(out, h->errw + 16, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    AV_CHECK(hipMemset(h->errw + 16, 0, 32 * sizeof(unsigned long long)));
     return 0;
 }
 // test hook: the MFMA GEMM on caller buffers (see kernels.h for the operand conventions)

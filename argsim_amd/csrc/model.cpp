@@ -117,8 +117,10 @@ void layout(avae_ctx* h, Bump& b, Ws& w, int B, int Ss, int St, bool train)
 int reserve_ws(avae_ctx* h, size_t need)
 {
     if (need > h->ws_cap) {
-        AV_CHECK(hipStreamSynchronize(h->stream));
-        if (h->ws) AV_CHECK(hipFree(h->ws));
+        if (h->ws) {                                          // (work enqueued on the old arena; a first arena has nothing to wait for)
+            AV_CHECK(hipStreamSynchronize(h->stream));
+            AV_CHECK(hipFree(h->ws));
+        }
         h->ws = nullptr; h->ws_cap = 0;
         h->cnt_src = h->cnt_tgt = nullptr;                    // (pointed into the old arena)
         for (auto& sp : h->stamps) sp.dyn = nullptr;
@@ -137,8 +139,10 @@ int get_ws(avae_ctx* h, Ws& w, int B, int Ss, int St, bool train)
 static int grow_bf16(avae_ctx* h, unsigned short** buf, size_t* cap, size_t need)
 {
     if (need <= *cap) return 0;
-    AV_CHECK(hipStreamSynchronize(h->stream));
-    if (*buf) AV_CHECK(hipFree(*buf));
+    if (*buf) {
+        AV_CHECK(hipStreamSynchronize(h->stream));
+        AV_CHECK(hipFree(*buf));
+    }
     *buf = nullptr; *cap = 0;
     size_t n = need + need / 8;
     AV_CHECK(hipMalloc(reinterpret_cast<void**>(buf), n * sizeof(unsigned short)));

@@ -14,7 +14,10 @@ that is held against float64 with a WRONG hint -- that of another batch.
 One model configuration (KW), so that one handle runs every batch.  PROBES are compared with the float64 oracle; PRIMERS only leave their
 hint and their workspace behind.  A sequence is a list of calls (kind, batch); every 'fb' on a probe is a checked step.  The route a checked
 step must take (expected_route) is derived HERE from the fill of the call before it and the three thresholds -- nothing is read back from the
-library; tests/test_step_history.py holds the table against the planners without a GPU."""
+library; tests/test_step_history.py holds the table against the planners without a GPU.
+
+LATE_SEQUENCES (below SEQUENCES) are the steps of a loop that does NOT synchronise, for tests/test_gpu_stream.py: what a step plans from when
+the hint of the call in front of it has not arrived."""
 import numpy as np
 
 import helpers
@@ -136,6 +139,51 @@ def steps(name):
         out.append((kind, batch, prev, route, expected_rows(batch, prev, route['compact'][0]) if route else None))
         if kind in FEEDS:
             prev = fill(batch)
+    return out
+
+
+# ------------------------------------------------------------------------------------------ sequences whose hint is LATE
+# tests/test_gpu_stream.py part C: the steps of a training loop that does not synchronise.  A call's hint lands when the stream reaches its
+# copy, so a step enqueued behind a busy stream plans from whatever had landed when IT began -- the fill of an earlier call, or nothing.
+# Third field of a call, `when`:
+#   'sync'    the stream is synchronised behind the call: its hint has arrived before the next call starts (every call of SEQUENCES)
+#   'late'    the call is enqueued on a stalled stream, and nothing synchronises behind it unless the NEXT call is not 'late' (then the run of late
+#             calls is over: the test synchronises there to read the last step).  Every call of one run sees what had arrived before the run.
+#   'nohint'  the call runs with option compact forced to 1 (the hint is sent under compact = 2 alone, build_row_orders), synchronised, and
+#             the option goes back to 2: the handle has been used and nothing is on its way.  The first forward_backward of a handle
+#             synchronises once by itself (model.cpp first_step_checked), so a step that is to see NOTHING cannot be the second call behind a
+#             first step that feeds -- that first step's hint has always arrived.
+# The step that is checked against the oracle is the LAST of a run of late calls and every 'sync' fb on a probe: losses(), train_ce() and the
+# gradient hold the last step only.
+LATE_SEQUENCES = {
+    # 1. a used handle, nothing arrived: `low`'s hint sits behind the stall, so the FULL batch takes no layout and the gather BPTT --
+    #    with low's hint it would take the compact layout and the reduce-scatter form ('low-full' above)
+    'late-nothing':      ('f32', [('fb', 'low', 'nohint'), ('fb', 'low', 'late'), ('fb', 'b64full', 'late')]),
+    'late-nothing-bf16': ('bf16', [('fb', 'low', 'nohint'), ('fb', 'low', 'late'), ('fb', 'b64full', 'late')]),
+    # 2. one step stale: b20 plans from low's fill (reduce-scatter BPTT, a fifth of the rows expected), not from b64full's 1.0 (gather, all
+    #    rows) whose copy is still queued.  3. caught up: the last hint copied in stream order is that of the run's LAST call, b20 itself
+    #    (each call's copy overwrites the pinned pair when the stream reaches it; b64full's landed first and b20's over it)
+    'late-stale':        ('f32', [('fb', 'low', 'sync'), ('fb', 'b64full', 'late'), ('fb', 'b20', 'late'), ('fb', 'b20', 'sync')]),
+}
+
+
+def late_steps(name):
+    """the calls of a late sequence with what the table derives for each: [(kind, batch, when, fill that HAD ARRIVED or None, expected route,
+    expected row expectations, checked)] -- route and rows for every fb on a probe, checked: the step is read back and held to the oracle"""
+    dtype, calls = LATE_SEQUENCES[name]
+    out, arrived, queued = [], None, None
+    for i, (kind, batch, when) in enumerate(calls):
+        assert when in ('sync', 'late', 'nohint'), when
+        probe = kind == 'fb' and batch in PROBES
+        forced = when == 'nohint'           # compact = 1: the layout whatever the hint, zero expectations if nothing has arrived
+        route = expected_route(batch, arrived, dtype) if probe and not forced else None
+        ends_run = when != 'late' or i + 1 == len(calls) or calls[i + 1][2] != 'late'
+        out.append((kind, batch, when, arrived, route, expected_rows(batch, arrived, route['compact'][0]) if route else None,
+                    bool(route) and ends_run))
+        if kind in FEEDS and not forced:
+            queued = fill(batch)
+        if ends_run:
+            arrived = queued
     return out
 
 

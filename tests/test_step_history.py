@@ -90,13 +90,20 @@ def test_sequences_cover_what_they_are_written_for():
     assert any(b == 'b64full' and p is not None and p < SH.RS_BELOW for b, p, *_ in seen['epoch'])
 
 
-@pytest.mark.parametrize('name', list(SH.SEQUENCES))
+def _table(name):
+    """(dtype, [(kind, batch, the fill the step plans from, route, rows)]) of a sequence of either table"""
+    if name in SH.SEQUENCES:
+        return SH.SEQUENCES[name][0], SH.steps(name)
+    return SH.LATE_SEQUENCES[name][0], [(k, b, p, w, r) for k, b, _, p, w, r, _ in SH.late_steps(name)]
+
+
+@pytest.mark.parametrize('name', list(SH.SEQUENCES) + list(SH.LATE_SEQUENCES))
 def test_expected_routes_match_the_planners(name):
     """every GRU plan of every checked step is what gru_plan answers for the launch shape gru_common fills, and Bx what gru_team_batch answers"""
     from argsim_amd import lib
     l = lib.load()
-    dtype = SH.SEQUENCES[name][0]
-    for kind, batch, prev, w, _ in SH.steps(name):
+    dtype, steps = _table(name)
+    for kind, batch, prev, w, _ in steps:
         if w is None:
             continue
         B, S = SH.shape(batch)
@@ -154,3 +161,36 @@ def test_row_expectations_are_the_stale_fill_scaled_to_the_step():
     assert rows['fresh'] == [('b64', (0, 0, 0)), ('b64', (int(SH.fill('b64') * 384), int(SH.fill('b64') * 448), int(SH.fill('b64') * 448)))]
     assert rows['full-ragged'] == [('b64', (0, 0, 0))]
     assert ('b100v', (1100, 1200, 1200)) in rows['epoch']
+
+
+def test_late_sequences_plan_from_what_had_arrived():
+    """the "late" column: a call of a run of unsynchronised calls plans from the fill that had arrived BEFORE the run, not from the call
+    in front of it; behind the run's synchronise the next call plans from the run's last feeding call"""
+    assert not set(SH.LATE_SEQUENCES) & set(SH.SEQUENCES)
+    col = {n: [(b, w, p, None if r is None else (r['compact'], r['bwd_rs']), rows, chk) for _, b, w, p, r, rows, chk in SH.late_steps(n)]
+           for n in SH.LATE_SEQUENCES}
+    low, b20 = SH.fill('low'), SH.fill('b20')
+    for n in ('late-nothing', 'late-nothing-bf16'):
+        # the primer leaves no hint, low's own is queued behind the stall: the FULL batch sees nothing -- no layout, no expectation
+        assert col[n] == [('low', 'nohint', None, None, None, False), ('low', 'late', None, None, None, False),
+                          ('b64full', 'late', None, ((0, 0), 0), (0, 0, 0), True)], col[n]
+    assert SH.LATE_SEQUENCES['late-nothing'][0] == 'f32' and SH.LATE_SEQUENCES['late-nothing-bf16'][0] == 'bf16'
+    B, S = SH.shape('b20')
+    stale = (int(low * S * B), int(low * (S + 1) * B), int(low * (S + 1) * B))
+    own = (int(b20 * S * B), int(b20 * (S + 1) * B), int(b20 * (S + 1) * B))
+    assert col['late-stale'] == [('low', 'sync', None, None, None, False),
+                                 ('b64full', 'late', low, ((1, 1), 1), (73, 85, 85), False),
+                                 ('b20', 'late', low, ((1, 1), 1), stale, True),          # NOT from b64full's 1.0: that would be bwd_rs 0, every row
+                                 ('b20', 'sync', b20, ((1, 1), 0), own, True)], col['late-stale']
+    # the stale and the caught-up step differ in what the GPU test can see: the BPTT form and the row expectations
+    assert stale != own and stale != (B * S, B * (S + 1), B * (S + 1))
+    # what each late step WOULD take had the call in front of it been waited for is another route: the test can tell the two apart
+    assert SH.expected_route('b64full', low, 'f32') != SH.expected_route('b64full', None, 'f32')
+    assert SH.expected_route('b20', 1.0, 'f32') != SH.expected_route('b20', low, 'f32')
+    # a run of late calls holds at most one checked step, its last; a 'nohint' call is a primer
+    for n in SH.LATE_SEQUENCES:
+        calls = SH.late_steps(n)
+        for i, (k, b, w, p, r, rows, chk) in enumerate(calls):
+            assert k == 'fb' and (w != 'nohint' or b in SH.PRIMERS), (n, i)
+            if chk:
+                assert w != 'late' or i + 1 == len(calls) or calls[i + 1][2] != 'late', (n, i)
